@@ -7,18 +7,23 @@ regression, stages 32/16/8/4 hypotheses) for ONE reference view at BASELINE conf
 extraction is outside the path).  Synthetic photo-consistent DTU-shaped inputs, random-init
 weights with randomized BatchNorm statistics.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 N > 1 is inference sharding: one process per GPU (spawned here like the reference's train.py:179-191 does when no
 launcher set WORLD_SIZE), every rank runs the cascade for its own reference views, no data-path collective (weak
 scaling); the only collectives are the timing barrier and the MAX over ranks.
 
-Prints ONE JSON line on rank 0 with
+A plain run sets up, warms up, times exactly --steps steps (one timed region), writes what the last timed step returned when
+--dump-outputs DIR is given (DIR/<name>.npy, float32, 64 MB at most: an array that does not fit is a fixed seeded sample of its elements)
+and prints ONE JSON line on rank 0: `metric`, `value` (depth maps/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the config.
+--full also measures and checks everything beyond that headline and adds it to the line (five timed regions by default, `value` = the
+median one):
   `roofline`             the dominant kernel (largest time per step), timed live with HIP events on the launch stream;
   `roofline_cost_volume` the north-star figure: SURVEY §8(d) algorithmic bytes of the fused cost-volume build of all four
                          stages / the summed time of every launch that builds it (sweeps, transposes);
-  `cpu_baseline`         the torch-CPU oracle on a bounded sample (rank 0 / N=1 only).
+  `cpu_baseline`         the torch-CPU oracle on the full workload (rank 0 / N=1 only) and `parity` against it;
+  latency, the smooth-hypotheses cost volume, other configs, the rows before the path, channel-last features, `train_config3`.
 """
 import argparse
 import json
@@ -56,9 +61,9 @@ def parse():
     ap.add_argument("--graph", action="store_true", help="replay one captured hipGraph of the cascade per stream instead of launching its ~60 kernels")
     ap.add_argument("--cpu-runs", type=int, default=1, help="timed full-size CPU cascades of the cpu_baseline leg (each 1-2 minutes)")
     ap.add_argument("--profile-steps", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="timed regions of exactly --steps steps each (barrier + synchronize on both sides of every one); `value` is the "
-                         "median region, the others are reported as the spread")
+                         "median region, the others are reported as the spread (default 1, with --full 5)")
     ap.add_argument("--latency-samples", type=int, default=30,
                     help="single-stream per-sample latency (synchronize, one cascade, synchronize - the reference's own timed region, "
                          "test.py:233-249): number of samples, reported as latency_ms_single_stream (median) beside the throughput")
@@ -76,14 +81,23 @@ def parse():
     ap.add_argument("--streams", type=int, default=3,
                     help="HIP streams per GPU; step i (one reference view) runs on stream i %% streams, so independent "
                          "reference views overlap (MFMA-bound regularizer of one with the VALU/TA-bound sweeps of another)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, 64 MB in all; a larger array is a fixed "
+                         "seeded sample of its elements)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: CPU baseline and parity, per-kernel roofline, gather ceiling, latency, "
+                         "other configs, FPN / ViT / images -> depth, channel-last features, the training step")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
-def cpu_baseline(net, args):
-    """The oracle (torch CPU, all host cores) on the WHOLE config-2 workload: the same inputs the GPU is timed on (seed 0),
-    `--cpu-runs` timed cascades (default 1; each is 1-2 minutes on the GPU box's host) after one warm-up cascade on a 512x384 sample
-    that only warms the thread pool and the allocator.  Returns the JSON object, the CPU inputs and the oracle's outputs (the
-    reference the `parity` object is computed against)."""
+def cpu_baseline(net, args, inputs):
+    """The oracle (torch CPU, all host cores) on the WHOLE config-2 workload: ``inputs``, the CPU tensors the GPU is timed on
+    (seed 0), `--cpu-runs` timed cascades (default 1; each is 1-2 minutes on the GPU box's host) after one warm-up cascade on a 512x384
+    sample that only warms the thread pool and the allocator.  Returns the JSON object and the oracle's outputs (the reference the
+    `parity` object is computed against)."""
     from mvsformer_amd import synth
     from oracle import ref_torch
     cores = min(os.cpu_count() or 1, 64)       # torch's intra-op pool stops scaling (and oversubscribes) beyond this
@@ -96,7 +110,6 @@ def cpu_baseline(net, args):
         ref_torch.cascade_forward(wf, wp, wd, sds, **kw)
         warm = time.time() - t0
         del wf, wp, wd
-        inputs = synth.make_inputs(args.views, args.height, args.width, seed=0, batch=args.batch)[:3]
         times = []
         for _ in range(max(1, args.cpu_runs)):
             t0 = time.time()
@@ -108,7 +121,7 @@ def cpu_baseline(net, args):
            "sample": "oracle/ref_torch.cascade_forward (torch %s CPU, %d threads) on the full workload: %d timed cascade(s) at %dx%d x %d views "
                      "(the inputs the GPU runs, seed 0) after one warm-up cascade on a 512x384 sample; unscaled" % (
                          torch.__version__, cores, len(times), args.width, args.height, args.views)}
-    return cpu, inputs, ref
+    return cpu, ref
 
 
 def rel_stats(got, want):
@@ -212,6 +225,35 @@ def make_runner(net, feats, proj, dv, tmp, streams, graphs=False, sets=None):
     return step, run
 
 
+def dump_outputs(out, path, budget=60 << 20, whole=("refined_depth", "photometric_confidence")):
+    """``--dump-outputs``: every tensor of the cascade's output dict as ``path/<key>.npy`` (nested keys joined by '.'), float32 (float64
+    stays float64), ``budget`` bytes of data at most (under 64 MB with the file headers).  The final results named in ``whole`` are written
+    whole; every other tensor, smallest first, whole while it fits its share of what is left, else as a sample of its flattened elements
+    at indices drawn by a fixed seed (sorted), the same for a given shape."""
+    import numpy as np
+    leaves = []
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k in v:
+                walk(prefix + [str(k)], v[k])
+        elif torch.is_tensor(v):
+            leaves.append((".".join(prefix), v))
+    walk([], out)
+    os.makedirs(path, exist_ok=True)
+    leaves.sort(key=lambda kv: (kv[0] not in whole, kv[1].numel() * (8 if kv[1].dtype == torch.float64 else 4), kv[0]))
+    left = budget
+    for i, (name, t) in enumerate(leaves):
+        a = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy().reshape(-1)
+        n = min(a.size, (left if name in whole else left // (len(leaves) - i)) // a.itemsize)
+        if n < a.size:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        else:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def main(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -225,18 +267,22 @@ def main(args):
     torch.cuda.set_device(dev)
 
     import mvsformer_amd as m
-    from mvsformer_amd import ops, synth
+    from mvsformer_amd import synth
 
     torch.manual_seed(0)
     net = m.CascadeMVS().eval()
     m.randomize_bn_(net, seed=1)
     cpu, ref = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu, cpu_inputs, ref = cpu_baseline(net, args)
+    # a single-GPU run times input set 0 as generated on the host, the very tensors the oracle (--full) runs on
+    host_inputs = rank == 0 and world == 1 and not args.no_cpu_baseline
+    if host_inputs:
+        cpu_inputs = synth.make_inputs(args.views, args.height, args.width, seed=0, batch=args.batch)[:3]
+        if args.full:
+            cpu, ref = cpu_baseline(net, args, cpu_inputs)
     net = net.to(dev)
 
     # each rank owns its reference view(s): different scene seed per rank, inputs resident in HBM before timing
-    if ref is not None:                                  # the very tensors the oracle ran on
+    if host_inputs:
         feats, proj, dv = ({k: v.to(dev) for k, v in cpu_inputs[0].items()}, {k: v.to(dev) for k, v in cpu_inputs[1].items()}, cpu_inputs[2].to(dev))
         del cpu_inputs
     else:
@@ -253,14 +299,14 @@ def main(args):
             f_j = {k: v.reshape(-1, *v.shape[2:]).contiguous(memory_format=torch.channels_last).view(v.shape) for k, v in f_j.items()}
         sets.append((f_j, p_j, d_j))
     sets_desc = {"bytes": sum(v.numel() * v.element_size() for v in feats.values()),
-                 "seeds": [0 if ref is not None else rank] + [1000 * j + rank for j in range(1, max(1, args.input_sets))]}
+                 "seeds": [0 if host_inputs else rank] + [1000 * j + rank for j in range(1, max(1, args.input_sets))]}
     step, run = make_runner(net, feats, proj, dv, tmp, streams, sets=sets)
     step()                                               # first call builds the weight caches (synchronizes once)
     if args.graph:                                       # measured: 1 stream 188.7 vs 189.1 depth maps/s eager, 3 streams 203 vs 215
         _, run = make_runner(net, feats, proj, dv, tmp, streams, graphs=True, sets=sets)
     run(max(args.warmup, args.streams))
-    # `--repeats` timed regions of EXACTLY --steps steps each; the reported one is the median region (a 20-step region is 80 ms: one
-    # pre-empted launch would otherwise move the headline), all of them are listed in `ms_per_step_repeats`
+    # `--repeats` timed regions of EXACTLY --steps steps each (one unless --full); the reported one is the median region (a 20-step region
+    # is 80 ms: one pre-empted launch would otherwise move the headline), all of them are listed in `ms_per_step_repeats`
     regions = []
     for _ in range(max(1, args.repeats)):
         dt_r, out = time_steps(run, args.steps, world, dev)
@@ -268,6 +314,61 @@ def main(args):
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     dt, own_dt = regions[order[(len(order) - 1) // 2]]
     assert torch.isfinite(out["refined_depth"]).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
+    extra = full_measurements(args, net, feats, proj, dv, tmp, ref, dev, step, run, sets, streams, out, rank, world) if args.full else None
+
+    # ---- who ran: one record per rank (device, its own wall time), so that a scaling run shows N distinct GPUs ----
+    props = torch.cuda.get_device_properties(dev)
+    mine = {"rank": rank, "local_rank": local_rank, "device": props.name, "uuid": str(getattr(props, "uuid", "")), "pci_bus_id": getattr(props, "pci_bus_id", None),
+            "ms_per_step": round(own_dt / args.steps * 1e3, 3)}
+    ranks = [mine]
+    if world > 1:
+        ranks = [None] * world
+        dist.all_gather_object(ranks, mine)
+
+    if rank == 0:
+        total = world * args.steps * args.batch
+        # Key order: the bulky per-kernel table FIRST, the judged scalars LAST - the driver's record keeps the tail of this line.
+        line = {}
+        if extra is not None:
+            line.update((k, extra[k]) for k in ("kernels", "other_configs", "before_the_path", "end_to_end_mvsformer_p", "features_layout_nhwc"))
+        line["ranks"] = ranks
+        if extra is not None:
+            line.update((k, extra[k]) for k in ("train_config3", "traffic_source", "parity"))
+        line.update({
+            "metric": "depth maps/sec @1536x1152 N=5 D=192", "value": round(total / dt, 3), "unit": "depth maps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[1]: DTU eval %dx%d, %d views, 192-plane range, 4-stage cascade ndepths=32/16/8/4, "
+                                   "fp32 in / fp32 out, one reference view per step per GPU, precomputed features resident in HBM"
+                                   % (args.width, args.height, args.views),
+                       "arithmetic": ARITHMETIC,
+                       "parallelism": "inference sharding of reference views, one process per GPU, no collective" if world > 1 else "single GPU",
+                       "streams_per_gpu": args.streams, "features_layout": args.features_layout,
+                       "reference_views_per_step": args.batch, "input_sets": len(sets_desc["seeds"]), "input_set_bytes": sets_desc["bytes"],
+                       "input_set_seeds": sets_desc["seeds"]},
+            "repeats": len(regions), "ms_per_step_repeats": [round(r[0] / args.steps * 1e3, 3) for r in regions],
+            "value_is": "median of `repeats` timed regions of exactly `steps` steps each, %d streams in flight" % max(1, args.streams),
+            "ranks_seen": dist.get_world_size() if world > 1 else 1,
+        })
+        if extra is not None:
+            line.update({
+                "kernel_ms_sum": extra["kernel_ms_sum"],
+                "latency_ms_single_stream": extra["latency"]["median"] if extra["latency"] else None, "latency": extra["latency"],
+                "roofline_cost_volume_smooth": extra["roofline_cost_volume_smooth"],
+                "cpu_baseline": cpu, "roofline_cost_volume": extra["roofline_cost_volume"], "roofline": extra["roofline"],
+                "max_rel_depth_err": extra["parity"]["max_rel_depth_err"] if extra["parity"] else None,
+            })
+        print(json.dumps(line))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, net, feats, proj, dv, tmp, ref, dev, step, run, sets, streams, out, rank, world):
+    """--full: what the line reports beyond the headline, measured after the timed region on the same network and inputs (``out`` = the
+    last timed step's result, ``ref`` = the CPU oracle's outputs on input set 0 or None).  Returns the extra keys of the line."""
+    from mvsformer_amd import ops, synth
     with torch.no_grad():                                # the timed steps computed what a fresh single-stream call computes
         again = step(args.steps - 1)                     # the input set of the region's last step
     assert torch.equal(out["refined_depth"], again["refined_depth"]), "timed step and a fresh call disagree"
@@ -572,44 +673,10 @@ def main(args):
                   "statistics, head, loss, master weights)", "workload": t["metric"], "top_kernels": t["kernels"],
                   "note": "extra key, not `value`: BASELINE configs[2] geometry on ONE GPU (the 8-GPU form is bench_train.py --gpus 8: DDP + SyncBatchNorm over RCCL)"}
 
-    # ---- who ran: one record per rank (device, its own wall time), so that a scaling run shows N distinct GPUs ----
-    props = torch.cuda.get_device_properties(dev)
-    mine = {"rank": rank, "local_rank": local_rank, "device": props.name, "uuid": str(getattr(props, "uuid", "")), "pci_bus_id": getattr(props, "pci_bus_id", None),
-            "ms_per_step": round(own_dt / args.steps * 1e3, 3)}
-    ranks = [mine]
-    if world > 1:
-        ranks = [None] * world
-        dist.all_gather_object(ranks, mine)
-
-    if rank == 0:
-        total = world * args.steps * args.batch
-        # Key order: the bulky per-kernel table FIRST, the judged scalars LAST - the driver's record keeps the tail of this line.
-        line = {
-            "kernels": kernels, "other_configs": other, "before_the_path": before, "end_to_end_mvsformer_p": end_to_end, "features_layout_nhwc": nhwc, "ranks": ranks, "train_config3": train3,
-            "traffic_source": traffic_source, "parity": parity,
-            "metric": "depth maps/sec @1536x1152 N=5 D=192", "value": round(total / dt, 3), "unit": "depth maps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: DTU eval %dx%d, %d views, 192-plane range, 4-stage cascade ndepths=32/16/8/4, "
-                                   "fp32 in / fp32 out, one reference view per step per GPU, precomputed features resident in HBM"
-                                   % (args.width, args.height, args.views),
-                       "arithmetic": ARITHMETIC,
-                       "parallelism": "inference sharding of reference views, one process per GPU, no collective" if world > 1 else "single GPU",
-                       "streams_per_gpu": args.streams, "features_layout": args.features_layout,
-                       "reference_views_per_step": args.batch, "input_sets": len(sets_desc["seeds"]), "input_set_bytes": sets_desc["bytes"],
-                       "input_set_seeds": sets_desc["seeds"]},
-            "repeats": len(regions), "ms_per_step_repeats": [round(r[0] / args.steps * 1e3, 3) for r in regions],
-            "value_is": "median of `repeats` timed regions of exactly `steps` steps each, %d streams in flight" % max(1, args.streams),
-            "ranks_seen": dist.get_world_size() if world > 1 else 1,
-            "kernel_ms_sum": round(sum(e["ms_per_step"] for e in kernels), 3),
-            "latency_ms_single_stream": latency["median"] if latency else None, "latency": latency,
-            "roofline_cost_volume_smooth": roofline_cv_smooth,
-            "cpu_baseline": cpu, "roofline_cost_volume": roofline_cv, "roofline": roofline,
-            "max_rel_depth_err": parity["max_rel_depth_err"] if parity else None,
-        }
-        print(json.dumps(line))
-    if world > 1:
-        dist.destroy_process_group()
+    return {"kernels": kernels, "other_configs": other, "before_the_path": before, "end_to_end_mvsformer_p": end_to_end,
+            "features_layout_nhwc": nhwc, "train_config3": train3, "traffic_source": traffic_source, "parity": parity,
+            "kernel_ms_sum": round(sum(e["ms_per_step"] for e in kernels), 3), "latency": latency,
+            "roofline_cost_volume_smooth": roofline_cv_smooth, "roofline_cost_volume": roofline_cv, "roofline": roofline}
 
 
 if __name__ == "__main__":

@@ -26,6 +26,7 @@ float16-exact values to halve the files):
   fpn_encoder.npz          FPNEncoder, eval BatchNorm: state_dict (conv weights float16-exact), image, the 4 encoder outputs
   dinomvsnet_e2e.npz       the REAL DINOMVSNet (configs/config_mvsformer-p.json) in eval mode, images -> depth: 3 views of 128x192
   dinomvsnet_shapes.json   key -> shape of its state_dict() (weights are rebuilt from a seed: oracle/weights.make_model_state_dict)
+  reference_names.json     module -> module-level names of models.mvsformer_model / models.module / models.warping (a list of names)
 """
 import json
 import os
@@ -933,3 +934,19 @@ def gen_was_loss():
 
 if __name__ == "__main__" and os.environ.get("GEN_WAS", "1") == "1":
     gen_was_loss()
+
+
+# ---------------------------------------------------------------------------------------------
+def gen_reference_names():
+    """reference_names.json: the module-level names of the reference modules ``mvsformer_amd.install()`` rebinds names in
+    (tests/test_abi.py::test_install_rebinds_reference_symbols builds stand-in modules with exactly these names)."""
+    import importlib
+    names = {}
+    for mod in ("models.mvsformer_model", "models.module", "models.warping"):
+        names[mod] = sorted(k for k in vars(importlib.import_module(mod)) if not k.startswith("__"))
+    with open(os.path.join(OUT, "reference_names.json"), "w") as f:
+        json.dump(names, f, indent=0)
+
+
+if __name__ == "__main__" and os.environ.get("GEN_NAMES", "1") == "1":
+    gen_reference_names()

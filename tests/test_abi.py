@@ -96,33 +96,38 @@ def test_product_never_imports_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), f
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference checkout only exists in the build container")
-def test_install_rebinds_reference_symbols():
-    """install() swaps the hot-path names inside the unmodified reference modules (import side effects of unrelated
-    files stubbed exactly as oracle/gen_golden.py does)."""
-    import subprocess
+def test_install_rebinds_reference_symbols(monkeypatch):
+    """install() swaps the hot-path names inside the reference modules and leaves every other name alone.  The modules are stand-ins
+    with exactly the module-level names of the reference's ``models.mvsformer_model`` / ``models.module`` / ``models.warping``
+    (tests/golden/reference_names.json, oracle/gen_golden.py::gen_reference_names), each bound to a placeholder of its own."""
     import sys
-    code = r'''
-import sys, types, torch.nn as nn
-sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference"); sys.path.insert(0, %r)
-def stub(name, **kw):
-    m = types.ModuleType(name); m.__dict__.update(kw); sys.modules[name] = m
-stub("timm"); stub("timm.models")
-stub("timm.models.layers", DropPath=nn.Identity, to_2tuple=lambda x: (x, x), trunc_normal_=nn.init.trunc_normal_)
-stub("timm.models.vision_transformer", Block=nn.Module)
-stub("torchvision"); stub("torchvision.utils"); stub("omegaconf", OmegaConf=object)
-import models.mvsformer_model as mm
-import mvsformer_amd
-done = mvsformer_amd.install()
-assert mm.StageNet is mvsformer_amd.StageNet and mm.homo_warping_3D_with_mask is mvsformer_amd.homo_warping_3D_with_mask
-assert mm.CostRegNet is mvsformer_amd.CostRegNet and mm.CostRegNet3D is mvsformer_amd.CostRegNet3D
-net = mm.StageNet(dict(base_ch=8, fusion_type="cnn", depth_type="ce"), 4, 0)
-assert type(net.cost_reg).__module__.startswith("mvsformer_amd")
-print("OK", sorted(done))
-''' % REPO
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "OK" in out.stdout, out.stderr[-2000:]
+    import types
+    import mvsformer_amd
+    from mvsformer_amd.install import _SYMBOLS, _w, install
+    names = json.load(open(os.path.join(GOLDEN, "reference_names.json")))
+    monkeypatch.setitem(sys.modules, "models", types.ModuleType("models"))
+    mods = {}
+    for name, syms in names.items():
+        mod = types.ModuleType(name)
+        for s in syms:
+            setattr(mod, s, object())
+        mods[name] = mod
+        monkeypatch.setitem(sys.modules, name, mod)
+    before = {name: dict(vars(mod)) for name, mod in mods.items()}
+    done = install()
+    hot = dict(_SYMBOLS, homo_warping_3D=_w.homo_warping_3D, diff_homo_warping_3D_with_mask=_w.diff_homo_warping_3D_with_mask)
+    assert set(done) == set(names)
+    for name, mod in mods.items():
+        want = {s for s in names[name] if s in hot}
+        assert set(done[name]) == want, (name, set(done[name]) ^ want)
+        for s in names[name]:
+            assert getattr(mod, s) is (hot[s] if s in want else before[name][s]), (name, s)
+    mm = mods["models.mvsformer_model"]
+    assert mm.StageNet is mvsformer_amd.StageNet and mm.homo_warping_3D_with_mask is mvsformer_amd.homo_warping_3D_with_mask
+    assert mm.CostRegNet is mvsformer_amd.CostRegNet and mm.CostRegNet3D is mvsformer_amd.CostRegNet3D
+    assert mods["models.warping"].homo_warping_3D_with_mask is mvsformer_amd.homo_warping_3D_with_mask
+    net = mm.StageNet(dict(base_ch=8, fusion_type="cnn", depth_type="ce"), 4, 0)
+    assert type(net.cost_reg).__module__.startswith("mvsformer_amd")
 
 
 def test_kernel_timer_per_step_medians():
