@@ -44,7 +44,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 40
+#define MVS_ABI_VERSION 41
 
 typedef void* mvs_stream_t;
 
@@ -677,6 +677,7 @@ int mvs_ce_loss_bwd_scale(const float* grad_unscaled, float* grad, int64_t numel
  * matrix cores in the three-term split form (fp32-equivalent, see "Arithmetic" above).
  *   mvs_gemm_x3: C[b1][b2] = epi(alpha * A[b1][b2] . B[b1][b2]^T) for nb1 x nb2 batches with element strides s?1 / s?2 per operand;
  *       A [M][K] rows lda apart; B [N][K] rows ldb apart (b_kn = 0) or [K][N] (b_kn = 1); C [M][N] rows ldc apart.
+ *       a_mode 3: A stored transposed, [K][M] with rows lda apart (a linear layer's weight gradient dW = dY^T X reads dY [rows][out] as is).
  *       a_mode 1: A is the implicit im2col of a 3x3 / pad-1 convolution over a channel-last map [H][W][Cp] (M = H*W, K = 9*Cp, k = tap*Cp + c);
  *       a_mode 2: the 2x2 taps of output-parity class b2 (ph = b2 / 2, pw = b2 % 2; nb2 = 4) of a ConvTranspose2d(kernel 4, stride 2,
  *       padding 1) over [H][W][Cp] (M = H*W input pixels, K = 4*Cp; class output (y, x) is output pixel (2y + ph, 2x + pw)).  Cp % 8 == 0.
@@ -699,6 +700,37 @@ int mvs_layernorm(const float* x, const float* gamma, const float* beta, float* 
 int mvs_softmax_rows(const float* x, float* y, int64_t rows, int N, float scale, mvs_stream_t stream);
 int mvs_bicubic_resize(const float* in, float* out, int planes, int H, int W, int Ho, int Wo, float rscale_h, float rscale_w,
                        mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Training mode of the DINO ViT (csrc/vit_train.hip; "fix": false, models/mvsformer_model.py:216-219 runs vit.forward_with_last_att with
+ * gradients; the blocks are models/vision_transformer.py:122-150 Attention, :104-119 Mlp, :194-214 Block, :394-431 the position table and
+ * prepare_tokens, :442-451 forward_with_last_att).  The matrix products of the forward and the backward are mvs_gemm_x3 (data gradients
+ * b_kn = 1, weight gradients a_mode 3); these are the other pieces.  fp32; every reduction in a fixed order (bitwise reproducible).
+ *   mvs_layernorm_stats: mvs_layernorm (vision_transformer.py:199,207,449 norm1 / norm2 / norm) that also writes mean[rows], rstd[rows].
+ *   mvs_layernorm_bwd: dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)) + res, g = dy * gamma, xhat = (x - mean) * rstd (res may be NULL).
+ *   mvs_colsum: column sums over rows of [rows][C]: x == NULL: out[C] = sum dy (a bias gradient, nn.Linear :107,:109,:139,:140);
+ *       x given: out[2C] = [sum dy * xhat | sum dy] (LayerNorm's dgamma | dbeta).  workspace: mvs_colsum_workspace_floats(rows, C, x != NULL)
+ *       floats of per-64-row partials, added in a fixed order.
+ *   mvs_gelu_fwd / mvs_gelu_bwd: y = GELU(erf)(x) (Mlp.act, vision_transformer.py:108) / dx = dy * GELU'(x) on the saved fc1 output.
+ *   mvs_attention_softmax_bwd: the backward of att = softmax(scale * Q K^T) (vision_transformer.py:144-145) per row of P [BH][N][N]:
+ *       dS = scale * P * (g - sum_k P_k g_k), g = dP + dA where dA [BH][da_rows][N] is the gradient of the returned attention matrix:
+ *       da_rows = N (every row) or 1 (the CLS query row 0 only: mvsformer_model.py:223,253 read vit_att[:, :, 0, 1:]); dA may be NULL.
+ *   mvs_bicubic_resize_bwd: the adjoint of mvs_bicubic_resize (same arguments; interpolate_pos_encoding's gradient into pos_embed,
+ *       vision_transformer.py:407-411), gather form in two separable passes; tmp holds planes * Ho * W floats.
+ * ------------------------------------------------------------------------------------------------------- */
+int mvs_layernorm_stats(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t rows, int C, float eps,
+                        mvs_stream_t stream);
+int mvs_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* res, float* dx,
+                      int64_t rows, int C, mvs_stream_t stream);
+int64_t mvs_colsum_workspace_floats(int64_t rows, int64_t C, int with_x);
+int mvs_colsum(const float* dy, const float* x, const float* mean, const float* rstd, int64_t rows, int64_t C, float* out, float* workspace,
+               mvs_stream_t stream);
+int mvs_gelu_fwd(const float* x, float* y, int64_t n, mvs_stream_t stream);
+int mvs_gelu_bwd(const float* dy, const float* x, float* dx, int64_t n, mvs_stream_t stream);
+int mvs_attention_softmax_bwd(const float* P, const float* dP, const float* dA, int da_rows, float* dS, int64_t BH, int N, float scale,
+                              mvs_stream_t stream);
+int mvs_bicubic_resize_bwd(const float* dout, float* din, float* tmp, int planes, int H, int W, int Ho, int Wo, float rscale_h, float rscale_w,
+                           mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The transformer blocks on PRE-SPLIT ("packed") operands (csrc/vit_packed.hip; models/vision_transformer.py:123-154,194-214): every matrix

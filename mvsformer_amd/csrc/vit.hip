@@ -37,7 +37,7 @@ struct GemmArgs {
     long long sA1, sA2, sB1, sB2, sC1, sC2;                  // batch strides (elements) of the two batch axes
     int M, N, K, lda, ldb, ldc, nb2;
     int b_kn;                 // 0: B[n][k] (k contiguous), 1: B[k][n] (n contiguous)
-    int a_mode;               // 0 plain; 1 conv3x3 pad 1 over [H][W][Cp] (k = tap*Cp + c, m = y*W + x); 2 ConvTranspose2d k4 s2 p1 parity class
+    int a_mode;               // 0 plain; 3 plain stored [K][M]; 1 conv3x3 pad 1 over [H][W][Cp] (k = tap*Cp + c, m = y*W + x); 2 ConvTranspose2d k4 s2 p1 parity class
     int H, W, Cp;             //    (class = second batch index: ph = class / 2, pw = class % 2; k = (th*2 + tw)*Cp + c; m = y*W + x of the INPUT grid)
     int act;                  // 0 none, 1 GELU (erf), 2 Swish
     float alpha;
@@ -74,6 +74,13 @@ __device__ __forceinline__ void load_a8(const GemmArgs& a, const float* __restri
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = 0.0f;
     if (m >= a.M || k0 >= a.K) return;
+    if (a.a_mode == 3) {                                     // A stored transposed, [K][M] with rows lda apart (dW = dY^T X of a linear layer)
+        const float* q = Ab + (size_t)k0 * a.lda + m;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (k0 + e < a.K) v[e] = q[(size_t)e * a.lda];
+        return;
+    }
     const float* p;
     if (a.a_mode == 0) {
         p = Ab + (size_t)m * a.lda + k0;
@@ -686,7 +693,7 @@ extern "C" int mvs_gemm_x3(const float* A, const float* B, float* C, int M, int 
                            mvs_stream_t stream) {
     MVS_REQUIRE(A && B && C && M >= 1 && N >= 1 && K >= 1 && nb1 >= 1 && nb2 >= 1, "mvs_gemm_x3: bad shape M=%d N=%d K=%d", M, N, K);
     MVS_REQUIRE((int64_t)nb1 * nb2 <= 65535 && (b_kn == 0 || b_kn == 1) && act >= 0 && act <= 3, "mvs_gemm_x3: bad batch / flags");
-    MVS_REQUIRE(a_mode == 0 || ((a_mode == 1 || a_mode == 2) && H >= 1 && W >= 1 && Cp >= 8 && Cp % 8 == 0 && M == H * W &&
+    MVS_REQUIRE(a_mode == 0 || a_mode == 3 || ((a_mode == 1 || a_mode == 2) && H >= 1 && W >= 1 && Cp >= 8 && Cp % 8 == 0 && M == H * W &&
                                 K == (a_mode == 1 ? 9 : 4) * Cp && (a_mode == 1 || nb2 == 4)),
                 "mvs_gemm_x3: implicit convolution needs M = H*W, K = taps*Cp, Cp a multiple of 8 (and nb2 = 4 parity classes for the transposed form)");
     GemmArgs a{};

@@ -7,9 +7,12 @@ Composition only: every piece is a HIP-backed module of this package (``FPNEncod
 ViT-small branch csrc/vit_packed.hip, the four ``StageNet``s).  Eval mode runs the V views of all B samples as ONE batch through the 2-D
 networks (the reference loops over views, mvsformer_model.py:238-271; with eval BatchNorm the results per image are the same) and hands the
 feature maps to the cascade channel-last.  Only what the shipped MVSFormer-P config builds is built: ``multi_scale=False``, ``att_fusion=True``,
-``vit_arch='vit_small'``; Twins (``TwinMVSNet``) needs ``timm``.
+``vit_arch='vit_small'``; Twins (``TwinMVSNet``) needs ``timm``.  ``"fix": false`` trains the ViT too (mvsformer_model.py:219), and
+``vit_args['vit_path']`` loads the pretrained DINO weights (mvsformer_model.py:182-193).
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -18,6 +21,23 @@ from . import _lib
 from .cascade import CascadeMVS
 from .fpn import FPNDecoder, FPNEncoder
 from .vit import VITDecoderStage4Single, vit_branch, vit_small
+
+
+def _load_vit_weights(vit, path: str) -> None:
+    """mvsformer_model.py:182-193: the pretrained DINO weights at ``vit_args['vit_path']`` when the file exists - a plain checkpoint (its
+    ``'model'`` entry when there is one) or a trained ``model_best.pth`` (``state_dict`` with ``vit.``-prefixed keys) - loaded non-strictly
+    with the missing / unexpected keys reported (utils.py torch_init_model); otherwise the reference's warning."""
+    if not path or not os.path.exists(path):
+        print('!!!No weight in', path, 'testing should neglect this.')
+        return
+    sd = torch.load(path, map_location="cpu")
+    if os.path.basename(path) == "model_best.pth" and "state_dict" in sd:
+        sd = {k[len("vit."):]: v for k, v in sd["state_dict"].items() if k.startswith("vit.")}
+    if "model" in sd:
+        sd = sd["model"]
+    res = vit.load_state_dict(sd, strict=False)
+    print("missing keys:{}".format(list(res.missing_keys)))
+    print("unexpected keys:{}".format(list(res.unexpected_keys)))
 
 
 class DINOMVSNet(CascadeMVS):
@@ -33,6 +53,7 @@ class DINOMVSNet(CascadeMVS):
         self.encoder = FPNEncoder(feat_chs=a["feat_chs"])
         self.decoder = FPNDecoder(feat_chs=a["feat_chs"])
         self.vit = vit_small(patch_size=va["patch_size"], qk_scale=va["qk_scale"])
+        _load_vit_weights(self.vit, va.get("vit_path", ""))
         self.decoder_vit = VITDecoderStage4Single(va)
         fusions = self.fusions                               # registered last, as the reference does (state_dict key ORDER too)
         del self.fusions
@@ -52,9 +73,11 @@ class DINOMVSNet(CascadeMVS):
         x = imgs.reshape(B * V, 3, H, W)
         conv01, conv11, conv21, conv31 = self.encoder(x) if self.training else self.encoder(x, conv01_channels_last=True)
         if self.training and not self.args.get("fix", False):
-            raise _lib.MvsHipError("DINOMVSNet: training the ViT itself (fix=False) is not built; MVSFormer-P freezes it (\"fix\": true)")
-        with torch.no_grad():                                # the frozen ViT (mvsformer_model.py:216-218,248-250)
-            vb = vit_branch(self.vit, self.decoder_vit if not self.training else None, x, self.vit_args["rescale"])
+            # fine-tuning the ViT (mvsformer_model.py:219): one autograd node (vit._ViTTrainFn) from the resized image to tokens + CLS attention
+            vb = vit_branch(self.vit, None, x, self.vit_args["rescale"])
+        else:
+            with torch.no_grad():                            # the frozen ViT (mvsformer_model.py:216-218,248-250)
+                vb = vit_branch(self.vit, self.decoder_vit if not self.training else None, x, self.vit_args["rescale"])
         if self.training:
             P = self.vit.patch_size
             hp, wp = int(H * self.vit_args["rescale"]) // P, int(W * self.vit_args["rescale"]) // P

@@ -1802,6 +1802,86 @@ def bicubic_resize(x: torch.Tensor, Ho: int, Wo: int, rscale_h: float, rscale_w:
     return out
 
 
+# ------------------------------------------------------------------ ViT training mode (csrc/vit_train.hip; the matrix products are gemm_x3)
+def layernorm_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float):
+    """:func:`layernorm` that also returns each row's mean and 1 / std -> ``(y, mean [rows], rstd [rows])``."""
+    _chk(x, "x"), _chk(gamma, "gamma"), _chk(beta, "beta")
+    rows = x.numel() // x.shape[-1]
+    y = torch.empty_like(x)
+    mean, rstd = (torch.empty(rows, device=x.device, dtype=torch.float32) for _ in range(2))
+    _call("mvs_layernorm_stats", "layernorm_stats", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), rows, x.shape[-1], float(eps),
+          _stream())
+    return y, mean, rstd
+
+
+def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor,
+                  res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm's input gradient (+ ``res``, the residual branch's gradient)."""
+    _chk(dy, "dy"), _chk(x, "x"), _chk(mean, "mean"), _chk(rstd, "rstd"), _chk(gamma, "gamma"), _opt(res, "res")
+    dx = torch.empty_like(x)
+    _call("mvs_layernorm_bwd", "layernorm_bwd", _ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(res), _ptr(dx),
+          x.numel() // x.shape[-1], x.shape[-1], _stream())
+    return dx
+
+
+def colsum(dy: torch.Tensor, x: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None,
+           cols: Optional[int] = None) -> torch.Tensor:
+    """Column sums of ``dy`` viewed as ``[rows, cols]`` (default ``cols`` = last axis): a bias gradient; with ``x``, ``mean``, ``rstd`` (a
+    LayerNorm's input and statistics) ``[2*cols]`` = (dgamma | dbeta).  Fixed-order, bitwise reproducible."""
+    _chk(dy, "dy"), _opt(x, "x"), _opt(mean, "mean"), _opt(rstd, "rstd")
+    C = cols or dy.shape[-1]
+    rows = dy.numel() // C
+    n = getattr(_lib.load(), "mvs_colsum_workspace_floats")(rows, C, int(x is not None))
+    if n < 0:
+        raise _lib.MvsHipError("colsum: bad shape %s" % (tuple(dy.shape),))
+    ws = torch.empty(int(n), device=dy.device, dtype=torch.float32)
+    out = torch.empty(C * (2 if x is not None else 1), device=dy.device, dtype=torch.float32)
+    _call("mvs_colsum", "colsum", _ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), rows, C, _ptr(out), _ptr(ws), _stream())
+    return out
+
+
+def gelu(x: torch.Tensor) -> torch.Tensor:
+    _chk(x, "x")
+    y = torch.empty_like(x)
+    _call("mvs_gelu_fwd", "gelu_fwd", _ptr(x), _ptr(y), x.numel(), _stream())
+    return y
+
+
+def gelu_bwd(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """``dy * GELU'(x)`` (GELU(erf)); ``x`` = the activation's input."""
+    _chk(dy, "dy"), _chk(x, "x")
+    dx = torch.empty_like(x)
+    _call("mvs_gelu_bwd", "gelu_bwd", _ptr(dy), _ptr(x), _ptr(dx), x.numel(), _stream())
+    return dx
+
+
+def attention_softmax_bwd(p: torch.Tensor, dp: torch.Tensor, scale: float, da: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``p = softmax(scale * S)`` ``[..., N, N]``, ``dp`` = dL/dp through ``P V`` -> dL/dS.  ``da``: the gradient of ``p`` as a returned output,
+    ``[..., N, N]`` (every row) or ``[..., N]`` (the CLS query's row 0 only)."""
+    _chk(p, "p"), _chk(dp, "dp"), _opt(da, "da")
+    N = p.shape[-1]
+    BH = p.numel() // (N * N)
+    da_rows = 0
+    if da is not None:
+        da_rows = N if da.shape == p.shape else 1
+        if da_rows == 1 and da.numel() != BH * N:
+            raise _lib.MvsHipError("attention_softmax_bwd: da %s for p %s" % (tuple(da.shape), tuple(p.shape)))
+    ds = torch.empty_like(p)
+    _call("mvs_attention_softmax_bwd", "attention_softmax_bwd", _ptr(p), _ptr(dp), _ptr(da), da_rows, _ptr(ds), BH, N, float(scale), _stream())
+    return ds
+
+
+def bicubic_resize_bwd(dout: torch.Tensor, H: int, W: int, rscale_h: float, rscale_w: float) -> torch.Tensor:
+    """The adjoint of :func:`bicubic_resize` (same ``rscale`` arguments): ``dout [..., Ho, Wo]`` -> ``[..., H, W]``."""
+    _chk(dout, "dout")
+    Ho, Wo = dout.shape[-2:]
+    planes = dout.numel() // (Ho * Wo)
+    din = torch.empty(tuple(dout.shape[:-2]) + (H, W), device=dout.device, dtype=torch.float32)
+    tmp = torch.empty(planes * Ho * W, device=dout.device, dtype=torch.float32)
+    _call("mvs_bicubic_resize_bwd", "bicubic_bwd", _ptr(dout), _ptr(din), _ptr(tmp), planes, H, W, Ho, Wo, float(rscale_h), float(rscale_w), _stream())
+    return din
+
+
 # ------------------------------------------------------------------ FPN training mode (csrc/vit.hip mvs_conv2d_gemm_x3, csrc/fpn_train.hip)
 # ----------------------------------------------------------------------------------------------- pre-split ("packed") operands (csrc/vit_packed.hip)
 class Packed:

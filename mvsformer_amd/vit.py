@@ -1,7 +1,8 @@
 """The DINO ViT-small feature branch of MVSFormer-P on the MI355X path: ``vit_small`` / ``VisionTransformer`` with the
 interface and the ``state_dict`` keys of the reference's ``models/vision_transformer.py`` (:340-451, ``vit_small`` :610-614) and
 ``VITDecoderStage4Single`` / ``AttentionFusionSimple`` of ``models/module.py`` (:353-368, :450-466), so the checkpoint of the shipped
-``configs/config_mvsformer-p.json`` loads with ``strict=True``.  The ViT itself is eval-only (the reference freezes it: ``"fix": true``); the
+``configs/config_mvsformer-p.json`` loads with ``strict=True``.  The ViT runs in eval mode and, for ``"fix": false``, in training mode
+(``_ViTTrainFn``: one autograd node, the backward in ``csrc/vit_train.hip`` + ``mvs_gemm_x3``; DESIGN.md §8 "Fine-tuning the DINO ViT"); the
 decoder also runs in training mode (batch-statistics BatchNorm, every gradient; ``_forward_train``).  In eval every
 matrix product - patch embedding, QKV, attention scores, attention x V, projections, MLP, the decoder's 3x3 convolutions and transposed
 convolutions as implicit GEMMs - runs in ``csrc/vit.hip`` on the bf16 matrix cores in three-term split form (fp32-equivalent), LayerNorm,
@@ -14,6 +15,7 @@ from __future__ import annotations
 import math
 import os
 from functools import partial
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -73,6 +75,7 @@ class VisionTransformer(nn.Module):
         self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches + 1, embed_dim))
         self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, qkv_bias, norm_layer) for _ in range(depth)])
         self.norm = norm_layer(embed_dim)
+        self._drop = tuple(float(kwargs.get(k, 0.0)) for k in ("drop_rate", "attn_drop_rate", "drop_path_rate"))
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
         nn.init.trunc_normal_(self.cls_token, std=0.02)
         self._cache = None
@@ -80,7 +83,8 @@ class VisionTransformer(nn.Module):
 
     # ---- position table resized to the token grid (vision_transformer.py:394-416; prepare_tokens passes (h, w) as (w, h)) ----
     def _pos(self, hp: int, wp: int) -> torch.Tensor:
-        key = (self.pos_embed.data_ptr(), self.pos_embed._version, hp, wp)
+        # the weights epoch too: an optimizer step through raw pointers (FusedAdamW) does not move pos_embed._version
+        key = (ops.weights_epoch(), self.pos_embed.data_ptr(), self.pos_embed._version, hp, wp)
         if self._pos_cache.get("key") != key:
             pe = _f(self.pos_embed)
             N = pe.shape[1] - 1
@@ -163,7 +167,10 @@ class VisionTransformer(nn.Module):
         """``want_att``: False, True (the last block's whole attention matrix, ``forward_with_last_att``'s contract) or ``"cls"`` (only the CLS
         query's row ``[B, heads, N]``: what ``vit_branch`` needs)."""
         if self.training:
-            raise _lib.MvsHipError("VisionTransformer: only eval mode is built on the HIP path (the reference freezes the ViT: \"fix\": true)")
+            if not want_att:
+                raise _lib.MvsHipError("VisionTransformer.forward: training mode is built for forward_with_last_att / forward_with_cls_att, what "
+                                       "DINOMVSNet calls (mvsformer_model.py:216-220); the plain forward is eval only")
+            return self._run_train(x, want_att)
         if want_att is not True and self._packed_ok():
             return self._run_packed(x, want_att == "cls")
         pw, pb, blocks, nw, nb, cls = self._prepared()[:6]
@@ -214,6 +221,27 @@ class VisionTransformer(nn.Module):
             return out, scores[:, :, 0].contiguous()
         return (out, scores) if want_att else out
 
+    def _train_params(self):
+        """Every parameter in the order ``_ViTTrainFn`` takes them."""
+        ps = [self.patch_embed.proj.weight, self.patch_embed.proj.bias, self.cls_token, self.pos_embed]
+        for b in self.blocks:
+            ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias, b.norm2.weight,
+                   b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
+        return ps + [self.norm.weight, self.norm.bias]
+
+    def _run_train(self, x: torch.Tensor, want_att):
+        """Training mode (``"fix": false``, mvsformer_model.py:216-219): the whole ViT is ONE autograd node (``_ViTTrainFn``) whose forward
+        keeps each block's activations and whose backward produces the gradient of every parameter.  Under bf16 autocast it stays
+        fp32-equivalent: every matrix product is ``mvs_gemm_x3`` in split form on fp32 operands.  The image gets no gradient."""
+        if any(self._drop):
+            raise _lib.MvsHipError("VisionTransformer: training with drop_rate / attn_drop_rate / drop_path_rate %r is not built (vit_small uses 0)"
+                                   % (self._drop,))
+        if self.embed_dim // self.num_heads * self.num_heads != self.embed_dim or self.embed_dim > 1024:
+            raise _lib.MvsHipError("VisionTransformer: training needs embed_dim <= 1024 divisible by the heads")
+        if x.requires_grad:
+            raise _lib.MvsHipError("VisionTransformer: training mode gives the image no gradient; pass it detached")
+        return _ViTTrainFn.apply(self, want_att == "cls", x.detach().to(torch.float32).contiguous(), *self._train_params())
+
     def forward(self, x, src_epipoles=None):
         return self._run(x, False)
 
@@ -225,6 +253,189 @@ class VisionTransformer(nn.Module):
         """-> (tokens ``[B, 1+hw, C]``, the CLS query's attention row of the last block ``[B, heads, 1+hw]``) = what mvsformer_model.py:246-257
         uses of ``forward_with_last_att`` (``vit_att[:, :, 0, 1:]``) without writing the other 1+hw rows."""
         return self._run(x, "cls")
+
+
+def _pos_resize(vit: VisionTransformer, hp: int, wp: int):
+    """The position table's resize as ``VisionTransformer._pos`` does it -> (n, rscale_h, rscale_w) or None when the table is used as is."""
+    N = vit.pos_embed.shape[1] - 1
+    n = int(math.sqrt(N))
+    if hp * wp == N and hp == wp:
+        return None
+    sh, sw = (hp + 0.1) / n, (wp + 0.1) / n
+    if int(n * sh) != hp or int(n * sw) != wp:
+        raise _lib.MvsHipError("position table resize: %dx%d does not come out of scale factors %.4f, %.4f" % (hp, wp, sh, sw))
+    return n, 1.0 / sh, 1.0 / sw
+
+
+def attention_train_fwd(qkv: torch.Tensor, heads: int):
+    """Attention (vision_transformer.py:139-150) of packed ``qkv [B,N,3C]`` in materialized form -> (P = softmax(Q K^T / sqrt(hd))
+    ``[B,heads,N,N]``, P V ``[B,N,C]``): what the backward reads."""
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    hd = C // heads
+    p = torch.empty(B, heads, N, N, device=qkv.device, dtype=torch.float32)
+    ops.gemm_x3(qkv, qkv, p, N, N, hd, C3, C3, N, nb1=B, nb2=heads, sA=(N * C3, hd), sB=(N * C3, hd), sC=(heads * N * N, N * N), b_off=C)
+    ops.softmax_rows_(p, hd ** -0.5)
+    out = torch.empty(B, N, C, device=qkv.device, dtype=torch.float32)
+    ops.gemm_x3(p, qkv, out, N, hd, N, N, C3, C, nb1=B, nb2=heads, sA=(heads * N * N, N * N), sB=(N * C3, hd), sC=(N * C, hd), b_kn=True, b_off=2 * C)
+    return p, out
+
+
+def attention_train_bwd(qkv: torch.Tensor, p: torch.Tensor, dout: torch.Tensor, heads: int, da: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of :func:`attention_train_fwd` -> dqkv ``[B,N,3C]``: dP = dO V^T, dS = ``mvs_attention_softmax_bwd`` (with ``da``, the
+    gradient of P itself: ``[B,heads,N,N]`` or its CLS row ``[B,heads,N]``; the softmax scale is inside dS), dQ = dS K, dK = dS^T Q (A
+    transposed), dV = P^T dO (A transposed), each written into its third of dqkv."""
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    hd = C // heads
+    dev = qkv.device
+    dp = torch.empty(B, heads, N, N, device=dev, dtype=torch.float32)
+    sS, sQ = (heads * N * N, N * N), (N * C3, hd)
+    ops.gemm_x3(dout, qkv, dp, N, N, hd, C, C3, N, nb1=B, nb2=heads, sA=(N * C, hd), sB=sQ, sC=sS, b_off=2 * C)
+    ds = ops.attention_softmax_bwd(p, dp, hd ** -0.5, da)
+    del dp
+    dqkv = torch.empty(B, N, C3, device=dev, dtype=torch.float32)
+    ops.gemm_x3(ds, qkv, dqkv, N, hd, N, N, C3, C3, nb1=B, nb2=heads, sA=sS, sB=sQ, sC=sQ, b_kn=True, b_off=C)
+    ops.gemm_x3(ds, qkv, dqkv, N, hd, N, N, C3, C3, nb1=B, nb2=heads, sA=sS, sB=sQ, sC=sQ, b_kn=True, a_mode=3, c_off=C)
+    ops.gemm_x3(p, dout, dqkv, N, hd, N, N, C, C3, nb1=B, nb2=heads, sA=sS, sB=(N * C, hd), sC=sQ, b_kn=True, a_mode=3, c_off=2 * C)
+    return dqkv
+
+
+class _ViTTrainFn(torch.autograd.Function):
+    """``VisionTransformer.forward_with_last_att`` / ``forward_with_cls_att`` in training mode and its backward
+    (models/vision_transformer.py:104-154,194-214,394-451).
+
+    Forward: the eval path's materialized form (csrc/vit.hip ``mvs_gemm_x3`` for every product, ``mvs_softmax_rows``), with LayerNorm writing
+    its row statistics (``mvs_layernorm_stats``) and fc1's pre-activation kept for GELU's backward.  Saved per block: the block input, both
+    LayerNorm outputs and statistics, qkv, the attention matrix P, the attention output, the mid-block tokens, fc1 before and after GELU.
+    Backward, per block in reverse: linear data gradients = ``mvs_gemm_x3`` with ``b_kn = 1``, weight gradients dW = dY^T X with ``a_mode = 3``,
+    bias / LayerNorm parameter gradients = ``mvs_colsum`` (fixed-order column sums), the attention backward dP = dO V^T, dS =
+    ``mvs_attention_softmax_bwd`` (which folds in the gradient of the returned attention: all rows, or the CLS row only), dQ = dS K,
+    dK = dS^T Q, dV = P^T dO written into one dqkv.  The position table's gradient goes through ``mvs_bicubic_resize_bwd``.  No atomics: two
+    runs give bitwise-equal gradients.
+
+    ``cls_only``: return the last block's CLS query row ``[B, heads, N]`` instead of its whole attention matrix."""
+
+    @staticmethod
+    def forward(ctx, vit, cls_only, x, *params):
+        f = [p.detach().to(torch.float32).contiguous() for p in params]
+        pw, pb, cls, pe = f[0].reshape(f[0].shape[0], -1), f[1], f[2], f[3]
+        blocks = [f[4 + 12 * i:16 + 12 * i] for i in range(len(vit.blocks))]
+        nw, nb = f[-2], f[-1]
+        B, nc, h, w = x.shape
+        P, C, NH = vit.patch_size, vit.embed_dim, vit.num_heads
+        hd = C // NH
+        hp, wp = h // P, w // P
+        n = hp * wp
+        N, M, K0 = n + 1, B * (hp * wp + 1), nc * P * P
+        scale = hd ** -0.5
+        eps = vit.norm.eps
+        dev = x.device
+        patches = x[:, :, :hp * P, :wp * P].reshape(B, nc, hp, P, wp, P).permute(0, 2, 4, 1, 3, 5).reshape(B * n, K0).contiguous()
+        tok = torch.empty(B, N, C, device=dev, dtype=torch.float32)
+        tok[:, 0] = cls[0, 0]
+        ops.gemm_x3(patches, pw, tok, n, C, K0, K0, K0, C, nb1=B, sA=(n * K0, 0), sC=(N * C, 0), shift=pb, c_off=C)
+        rs = _pos_resize(vit, hp, wp)
+        if rs is None:
+            pos = pe
+        else:
+            nn_, rh, rw = rs
+            grid = pe[0, 1:].reshape(nn_, nn_, C).permute(2, 0, 1).contiguous()
+            grid = ops.bicubic_resize(grid, hp, wp, rh, rw)
+            pos = torch.cat([pe[:, :1], grid.permute(1, 2, 0).reshape(1, n, C)], dim=1)
+        t = (tok + pos).contiguous()
+        saved = []
+        for (n1w, n1b, qw, qb, prw, prb, n2w, n2b, f1w, f1b, f2w, f2b) in blocks:
+            hid = f1w.shape[0]
+            y1, m1, r1 = ops.layernorm_stats(t, n1w, n1b, eps)
+            qkv = torch.empty(B, N, 3 * C, device=dev, dtype=torch.float32)
+            ops.gemm_x3(y1, qw, qkv, M, 3 * C, C, C, C, 3 * C, shift=qb)
+            p_att, att = attention_train_fwd(qkv, NH)
+            t2 = torch.empty_like(t)
+            ops.gemm_x3(att, prw, t2, M, C, C, C, C, C, shift=prb, res=t)
+            y2, m2, r2 = ops.layernorm_stats(t2, n2w, n2b, eps)
+            hpre = torch.empty(B, N, hid, device=dev, dtype=torch.float32)
+            ops.gemm_x3(y2, f1w, hpre, M, hid, C, C, C, hid, shift=f1b)
+            hact = ops.gelu(hpre)
+            tn = torch.empty_like(t)
+            ops.gemm_x3(hact, f2w, tn, M, C, hid, hid, hid, C, shift=f2b, res=t2)
+            saved.append((t, y1, m1, r1, qkv, p_att, att, t2, y2, m2, r2, hpre, hact))
+            t = tn
+        out, mf, rf = ops.layernorm_stats(t, nw, nb, eps)
+        last = saved[-1][5]
+        att_out = last[:, :, 0].contiguous() if cls_only else last.clone()
+        ctx.cfg = ( B, N, C, NH, hd, n, hp, wp, K0, scale, rs, [tuple(p.shape) for p in params])
+        ctx.state = (f, patches, saved, t, mf, rf)
+        return out, att_out
+
+    @staticmethod
+    def backward(ctx, dout, datt):
+        B, N, C, NH, hd, n, hp, wp, K0, scale, rs, shapes = ctx.cfg
+        f, patches, saved, t_last, mf, rf = ctx.state
+        dev = dout.device
+        M = B * N
+        blocks = [f[4 + 12 * i:16 + 12 * i] for i in range(len(saved))]
+        dout = dout.to(torch.float32).contiguous()
+        da = datt.to(torch.float32).contiguous()
+        gn = ops.colsum(dout, t_last, mf, rf)
+        dt = ops.layernorm_bwd(dout, t_last, mf, rf, f[-2])
+        block_grads = []
+        for i in reversed(range(len(saved))):
+            n1w, n1b, qw, qb, prw, prb, n2w, n2b, f1w, f1b, f2w, f2b = blocks[i]
+            t, y1, m1, r1, qkv, p_att, att, t2, y2, m2, r2, hpre, hact = saved[i]
+            hid = f1w.shape[0]
+            # mlp.fc2 (+ the residual: dt flows on to t2 unchanged)
+            dh = torch.empty(B, N, hid, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dt, f2w, dh, M, hid, C, C, hid, hid, b_kn=True)
+            dw2 = torch.empty(C, hid, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dt, hact, dw2, C, hid, M, C, hid, hid, b_kn=True, a_mode=3)
+            db2 = ops.colsum(dt)
+            # GELU, mlp.fc1
+            dhp = ops.gelu_bwd(dh, hpre)
+            dy2 = torch.empty(B, N, C, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dhp, f1w, dy2, M, C, hid, hid, C, C, b_kn=True)
+            dw1 = torch.empty(hid, C, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dhp, y2, dw1, hid, C, M, hid, C, C, b_kn=True, a_mode=3)
+            db1 = ops.colsum(dhp)
+            # norm2 (+ residual)
+            g2 = ops.colsum(dy2, t2, m2, r2)
+            dt2 = ops.layernorm_bwd(dy2, t2, m2, r2, n2w, res=dt)
+            # attn.proj
+            datt_o = torch.empty(B, N, C, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dt2, prw, datt_o, M, C, C, C, C, C, b_kn=True)
+            dwp = torch.empty(C, C, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dt2, att, dwp, C, C, M, C, C, C, b_kn=True, a_mode=3)
+            dbp = ops.colsum(dt2)
+            dqkv = attention_train_bwd(qkv, p_att, datt_o, NH, da if i == len(saved) - 1 else None)
+            # attn.qkv
+            dy1 = torch.empty(B, N, C, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dqkv, qw, dy1, M, C, 3 * C, 3 * C, C, C, b_kn=True)
+            dwq = torch.empty(3 * C, C, device=dev, dtype=torch.float32)
+            ops.gemm_x3(dqkv, y1, dwq, 3 * C, C, M, 3 * C, C, C, b_kn=True, a_mode=3)
+            dbq = ops.colsum(dqkv)
+            # norm1 (+ residual)
+            g1 = ops.colsum(dy1, t, m1, r1)
+            dt = ops.layernorm_bwd(dy1, t, m1, r1, n1w, res=dt2)
+            block_grads.append((g1[:C], g1[C:], dwq, dbq, dwp, dbp, g2[:C], g2[C:], dw1, db1, dw2, db2))
+        # tokens = [cls | patch embedding] + position table
+        dpos = ops.colsum(dt, cols=N * C).view(N, C)
+        if rs is None:
+            dpe = dpos.view(1, N, C)
+        else:
+            nn_, rh, rw = rs
+            dgrid = ops.bicubic_resize_bwd(dpos[1:].reshape(hp, wp, C).permute(2, 0, 1).contiguous(), nn_, nn_, rh, rw)
+            dpe = torch.cat([dpos[:1], dgrid.permute(1, 2, 0).reshape(nn_ * nn_, C)], dim=0).view(1, nn_ * nn_ + 1, C)
+        dcls = dpos[:1].reshape(1, 1, C).clone()
+        dpatch = dt[:, 1:].reshape(B * n, C).contiguous()
+        dwpe = torch.empty(C, K0, device=dev, dtype=torch.float32)
+        ops.gemm_x3(dpatch, patches, dwpe, C, K0, B * n, C, K0, K0, b_kn=True, a_mode=3)
+        dbpe = ops.colsum(dpatch)
+        grads = [dwpe, dbpe, dcls, dpe]
+        for g in reversed(block_grads):
+            grads += list(g)
+        grads += [gn[:C], gn[C:]]
+        grads = [g.reshape(s) for g, s in zip(grads, shapes)]
+        return (None, None, None) + tuple(grads)
 
 
 def vit_small(patch_size=16, **kwargs):
