@@ -44,7 +44,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 41
+#define MVS_ABI_VERSION 42
 
 typedef void* mvs_stream_t;
 
@@ -256,7 +256,11 @@ int mvs_conv3d_wino_fwd(const float* x, const float* wpacked, const float* scale
  * scale = shift = NULL, relu = 0) -> mvs_bn_stats -> [all-reduce of sums across ranks = SyncBatchNorm] -> mvs_bn_finalize
  * -> mvs_affine_act, and the backward is mvs_bn_bwd_reduce -> [all-reduce] -> mvs_bn_bwd_apply -> data gradient through
  * the same MFMA conv kernels with re-packed weights -> mvs_conv3d_wgrad.  Tensors are [B,C,N], N = D*H*W or H*W.
- *   mvs_bn_stats:      sums[c] = sum x, sums[C+c] = sum x^2.  Like every per-channel reduction here it runs in two launches -
+ *   mvs_bn_stats:      sums[c] = sum x, sums[C+c] = sum x^2, both DOUBLE (ABI 42) from the lane accumulators to mvs_bn_finalize, which
+ *                      forms var = sum x^2 / n - mean^2: with fp32 sums a channel whose mean is 100 standard deviations from zero
+ *                      keeps no digit of its variance.  SyncBatchNorm all-reduces the doubles (a plain sum).  The bf16 twins
+ *                      (mvs_bf16_bn_stats, mvs_bf16_conv3d_stats) add their fp32 block rows in double and return doubles too.
+ *                      Like every per-channel reduction here it runs in two launches -
  *                      one partial row per block into `workspace` (mvs_bn_reduce_workspace_bytes), then a fixed-order sum -
  *                      so the statistics repeat bit-exactly run to run (no float atomics) and `sums` needs no zeroing
  *   mvs_bn_finalize:   mean/var from sums and count -> scale = gamma*invstd, shift = beta - mean*scale, mean, invstd;
@@ -275,13 +279,13 @@ int mvs_conv3d_wino_fwd(const float* x, const float* wpacked, const float* scale
  *   mvs_softmax_bwd, mvs_prob1_bwd (dwb[C+1] zeroed by the caller: dW then dbias), mvs_sigmoid_fwd/bwd, mvs_nhwc_to_nchw
  * ------------------------------------------------------------------------------------------------------- */
 int64_t mvs_bn_reduce_workspace_bytes(int B, int C, int64_t N);
-int mvs_bn_stats(const float* x, int B, int C, int64_t N, float* sums, void* workspace, mvs_stream_t stream);
-int mvs_bn_finalize(const float* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
+int mvs_bn_stats(const float* x, int B, int C, int64_t N, double* sums, void* workspace, mvs_stream_t stream);
+int mvs_bn_finalize(const double* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
                     float momentum, float eps, double count, const float* count_dev, int C, float* scale, float* shift, float* mean,
                     float* invstd, mvs_stream_t stream);
 /* `groups` BatchNorm calls of one module laid side by side as channels g*C + c (sums [2*groups*C], gamma/beta/running [C],
  * scale/shift/mean/invstd [groups*C]); running statistics receive the groups' updates in order, as separate calls would. */
-int mvs_bn_finalize_grouped(const float* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
+int mvs_bn_finalize_grouped(const double* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
                             float momentum, float eps, double count, const float* count_dev, int C, int groups, float* scale,
                             float* shift, float* mean, float* invstd, mvs_stream_t stream);
 int mvs_affine_act(const float* x, const float* scale, const float* shift, const float* residual, int relu, int B, int C,
@@ -328,14 +332,14 @@ int mvs_bf16_conv3d(const void* x, const void* wpacked, const float* scale, cons
  * sums [2*groups*Cout]; workspace = mvs_bf16_conv3d_stats_workspace_bytes(B, Cout, Do, Ho, Wo) of the OUTPUT grid */
 int64_t mvs_bf16_conv3d_stats_workspace_bytes(int B, int Cout, int Do, int Ho, int Wo);
 int mvs_bf16_conv3d_stats(const void* x, const void* wpacked, void* y, int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd,
-                          int shw, int groups, float* sums, void* workspace, mvs_stream_t stream);
+                          int shw, int groups, double* sums, void* workspace, mvs_stream_t stream);
 int64_t mvs_bf16_conv3d_wgrad_workspace_bytes(int nbatch, int CA, int CB, int Dp, int Hp, int Wp);
 int mvs_bf16_conv3d_wgrad(const void* A, const void* Bt, float* dW, void* workspace, int nbatch, int CA, int CB, int Dp, int Hp, int Wp,
                           int Db, int Hb, int Wb, int sd, int shw, mvs_stream_t stream);
 int mvs_bf16_from_f32_ncdhw(const float* in, void* out, int B, int C, int64_t N, mvs_stream_t stream);
 int mvs_bf16_to_f32_ncdhw(const void* in, float* out, int B, int C, int64_t N, mvs_stream_t stream);
 int64_t mvs_bf16_bn_reduce_workspace_bytes(int C, int64_t R, int groups, int64_t rows_per_sample);
-int mvs_bf16_bn_stats(const void* x, int C, int64_t R, int groups, int64_t rows_per_sample, float* sums, void* workspace,
+int mvs_bf16_bn_stats(const void* x, int C, int64_t R, int groups, int64_t rows_per_sample, double* sums, void* workspace,
                       mvs_stream_t stream);
 int mvs_bf16_affine_act(const void* x, const float* scale, const float* shift, const void* residual, int relu, int C, int64_t R,
                         int groups, int64_t rows_per_sample, void* y, mvs_stream_t stream);

@@ -24,8 +24,9 @@ def _sync_sums(sums: torch.Tensor, count: float, bn):
 
     Returns ``(sums, count_dev)``.  ``count_dev`` is None when nothing was reduced (plain BatchNorm, or world size 1: the
     caller keeps its host count); otherwise it is a 2-element DEVICE tensor ``[n / 4096, n % 4096]`` summed over the ranks in
-    the SAME collective as the sums (one all-reduce of 2C+2 floats per layer, identical on every rank whatever the local
-    batch shapes are; each half stays exact in fp32 up to 2^36 elements) - the BatchNorm kernels read the global count from
+    the SAME collective as the sums (one all-reduce of 2C+2 values per layer - doubles for the forward statistics, whose
+    two sums ``bn_finalize`` subtracts - identical on every rank whatever the local batch shapes are; each half stays exact
+    in fp32 up to 2^36 elements) - the BatchNorm kernels read the global count from
     device memory, so the step never synchronizes with the host and no rank has to guess whether counts are equal.
     ``count == 0`` (backward: the caller already holds the forward's ``count_dev``) reduces only the sums."""
     if not (isinstance(bn, nn.SyncBatchNorm) and dist.is_available() and dist.is_initialized()):
@@ -37,9 +38,9 @@ def _sync_sums(sums: torch.Tensor, count: float, bn):
         red = sums.clone()                         # out of place: the caller's tensor keeps this rank's values (dgamma / dbeta)
         dist.all_reduce(red, group=bn.process_group)
         return red, None
-    packed = torch.cat([sums, _count_halves(sums.device, int(count))])
+    packed = torch.cat([sums, _count_halves(sums.device, int(count)).to(sums.dtype)])
     dist.all_reduce(packed, group=bn.process_group)
-    return packed[:-2], packed[-2:]
+    return packed[:-2], packed[-2:].float()                # the kernels read the count halves as floats whatever the sums' type is
 
 
 _COUNT_HALVES = {}

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "reduce_f64.h"
 
 namespace {
 
@@ -643,13 +644,17 @@ __global__ __launch_bounds__(256) void bf16_bn_reduce_kernel(const __bf16* __res
                                                              int C, size_t RS, int groups, float* __restrict__ part, int rpb) {
     // grid = (blocks per sample, samples); RS = rows per sample; rpb = rows per block.  Plain BatchNorm: one "sample" of all R rows.  Grouped (the batch
     // holds `groups` independent calls, sample n belongs to group n % groups): parameters of group g live at [g*C, (g+1)*C).
-    __shared__ float red[4][2 * 64];
+    // The forward statistics (sum x, sum x^2) are accumulated in DOUBLE up to the block's row, which is rounded to fp32 ONCE: the finalize
+    // forms sum x^2 / n - mean^2, and fp32 chains over like-sized terms (a channel far from zero) round with a common bias that does not
+    // average out over the rows.  The backward sums are centred and stay fp32.
+    using acc_t = typename std::conditional<BWD, float, double>::type;
+    __shared__ acc_t red[4][2 * 64];
     const int CQ = C / 8;
     const int cq = threadIdx.x % CQ, rsub = threadIdx.x / CQ, rstep = 256 / CQ;
     const int gofs = (int)(blockIdx.y % groups) * C;
-    float s[8], q[8];
+    acc_t s[8], q[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.0f;
+    for (int e = 0; e < 8; ++e) s[e] = q[e] = 0;
     float sc[8], sh[8], mu[8], is[8];
     if (BWD) {
 #pragma unroll
@@ -667,9 +672,9 @@ __global__ __launch_bounds__(256) void bf16_bn_reduce_kernel(const __bf16* __res
         if (!BWD) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float f = (float)xv[e];
+                const acc_t f = (acc_t)(float)xv[e];
                 s[e] += f;
-                q[e] = fmaf(f, f, q[e]);
+                q[e] = fma(f, f, q[e]);
             }
         } else {
             const bf16x8 gv = *reinterpret_cast<const bf16x8*>(dy + r * C + cq * 8);
@@ -703,7 +708,7 @@ __global__ __launch_bounds__(256) void bf16_bn_reduce_kernel(const __bf16* __res
     __syncthreads();
     if (threadIdx.x < 2 * C)
         part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+            (float)((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
 }
 
 // y = [relu](x*scale[c] + shift[c]) [+ residual]
@@ -891,7 +896,7 @@ extern "C" int mvs_bf16_pack_table_run(const void* dev_table, int njobs, int tot
 // gather: 0 = Conv3d (out = (in - 1)/stride + 1), 1 = ConvTranspose3d k3 p1 op(stride-1) (out = in*stride)
 static int bf16_conv3d_impl(const void* x, const void* wpacked, const float* scale, const float* shift, const void* residual, void* y,
                             int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd, int shw, int relu, float* stats_part,
-                            int groups, float* sums, mvs_stream_t stream, bool block_rows = false, int taps = 27, const void* bn_y = nullptr,
+                            int groups, double* sums, mvs_stream_t stream, bool block_rows = false, int taps = 27, const void* bn_y = nullptr,
                             const float* bn4 = nullptr, int bn_relu = 0, int bn_groups = 1);
 
 extern "C" int mvs_bf16_conv3d(const void* x, const void* wpacked, const float* scale, const float* shift, const void* residual, void* y,
@@ -917,7 +922,7 @@ extern "C" int64_t mvs_bf16_conv3d_stats_workspace_bytes(int B, int Cout, int Do
 }
 
 extern "C" int mvs_bf16_conv3d_stats(const void* x, const void* wpacked, void* y, int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather,
-                                     int sd, int shw, int groups, float* sums, void* workspace, mvs_stream_t stream) {
+                                     int sd, int shw, int groups, double* sums, void* workspace, mvs_stream_t stream) {
     MVS_REQUIRE(sums && workspace && groups >= 1 && B % groups == 0, "mvs_bf16_conv3d_stats: bad statistics arguments (B=%d groups=%d)", B, groups);
     return bf16_conv3d_impl(x, wpacked, nullptr, nullptr, nullptr, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 0,
                             reinterpret_cast<float*>(workspace), groups, sums, stream);
@@ -925,7 +930,7 @@ extern "C" int mvs_bf16_conv3d_stats(const void* x, const void* wpacked, void* y
 
 static int bf16_conv3d_impl(const void* x, const void* wpacked, const float* scale, const float* shift, const void* residual, void* y,
                             int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd, int shw, int relu, float* stats_part,
-                            int groups, float* sums, mvs_stream_t stream, bool block_rows, int taps, const void* bn_y, const float* bn4,
+                            int groups, double* sums, mvs_stream_t stream, bool block_rows, int taps, const void* bn_y, const float* bn4,
                             int bn_relu, int bn_groups) {
     MVS_REQUIRE(x && wpacked && y, "mvs_bf16_conv3d: null pointer");
     MVS_REQUIRE(taps == 27 || (taps == 9 && gather == 0 && sd == 1 && shw == 1 && Cin <= 16 && Cout <= 16),
@@ -1201,7 +1206,7 @@ extern "C" int64_t mvs_bf16_bn_reduce_workspace_bytes(int C, int64_t R, int grou
     return (int64_t)sh.bps * sh.nsamples * 2 * C * (int64_t)sizeof(float);
 }
 
-extern "C" int mvs_bf16_bn_stats(const void* x, int C, int64_t R, int groups, int64_t rows_per_sample, float* sums, void* workspace,
+extern "C" int mvs_bf16_bn_stats(const void* x, int C, int64_t R, int groups, int64_t rows_per_sample, double* sums, void* workspace,
                                  mvs_stream_t stream) {
     BnShape sh;
     MVS_REQUIRE(x && sums && workspace && bn_shape(C, R, groups, rows_per_sample, &sh), "mvs_bf16_bn_stats: bad arguments");
@@ -1255,11 +1260,11 @@ __global__ __launch_bounds__(256) void bf16_bn_reduce_finalize_kernel(const floa
     const float g = gamma ? gamma[c] : 1.0f, bt = beta ? beta[c] : 0.0f;
     float rm = running_mean ? running_mean[c] : 0.0f, rv = running_var ? running_var[c] : 0.0f;
     for (int q = 0; q < groups; ++q) {
-        float s1 = 0.0f, s2 = 0.0f;
+        double s1 = 0.0, s2 = 0.0;                           // the rows (fp32, one block's share each) are added in double: see bn_stats_kernel
         for (int i = lane; i < per; i += 64) {
             const size_t row = (size_t)(q + (i / bps) * groups) * bps + (i % bps);
-            s1 += part[row * 2 * C + c];
-            s2 += part[row * 2 * C + C + c];
+            s1 += (double)part[row * 2 * C + c];
+            s2 += (double)part[row * 2 * C + C + c];
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
@@ -1267,13 +1272,14 @@ __global__ __launch_bounds__(256) void bf16_bn_reduce_finalize_kernel(const floa
             s2 += __shfl_xor(s2, m, 64);
         }
         const int cc = q * C + c;
-        const double mean = (double)s1 / count;
-        double var = (double)s2 / count - mean * mean;
+        const double mean = s1 / count;
+        double var = s2 / count - mean * mean;
         if (var < 0.0) var = 0.0;
         const float invstd = (float)(1.0 / sqrt(var + (double)eps));
         if (lane == 0) {
-            out4[cc] = g * invstd;                           // scale
-            out4[CT + cc] = bt - (float)mean * g * invstd;   // shift
+            const float sc = g * invstd;
+            out4[cc] = sc;                                   // scale
+            out4[CT + cc] = (float)((double)bt - mean * (double)sc);   // shift (against the rounded scale, as bn_finalize_kernel)
             out4[2 * CT + cc] = (float)mean;
             out4[3 * CT + cc] = invstd;
             out4[4 * CT + cc] = g;                          // the affine weight per (group, channel): what the backward's apply kernel reads
@@ -1365,7 +1371,7 @@ __global__ __launch_bounds__(256) void bf16_bn_rows_finalize_kernel(const float*
                                                                     float* __restrict__ running_mean, float* __restrict__ running_var,
                                                                     float momentum, float eps, double count, float* __restrict__ out4,
                                                                     long long* __restrict__ num_batches_tracked) {
-    __shared__ float red[2][4];
+    __shared__ double red[2][4];
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (num_batches_tracked && c == 0 && tid == 0) num_batches_tracked[0] += groups;
     const int CT = C * groups, per = (nsamples / groups) * rps;
@@ -1374,11 +1380,11 @@ __global__ __launch_bounds__(256) void bf16_bn_rows_finalize_kernel(const float*
     const float* p1 = part + (size_t)c * nrows;
     const float* p2 = part + (size_t)(C + c) * nrows;
     for (int q = 0; q < groups; ++q) {
-        float s1 = 0.0f, s2 = 0.0f;
+        double s1 = 0.0, s2 = 0.0;                           // block rows (fp32 sums of <= 256 voxels) added in double: see bn_stats_kernel
         for (int i = tid; i < per; i += 256) {
             const int row = (q + (i / rps) * groups) * rps + (i % rps);
-            s1 += p1[row];
-            s2 += p2[row];
+            s1 += (double)p1[row];
+            s2 += (double)p2[row];
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
@@ -1394,13 +1400,14 @@ __global__ __launch_bounds__(256) void bf16_bn_rows_finalize_kernel(const float*
         s1 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
         s2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
         const int cc = q * C + c;
-        const double mean = (double)s1 / count;
-        double var = (double)s2 / count - mean * mean;
+        const double mean = s1 / count;
+        double var = s2 / count - mean * mean;
         if (var < 0.0) var = 0.0;
         const float invstd = (float)(1.0 / sqrt(var + (double)eps));
         if (tid == 0) {
-            out4[cc] = g * invstd;
-            out4[CT + cc] = bt - (float)mean * g * invstd;
+            const float sc = g * invstd;
+            out4[cc] = sc;
+            out4[CT + cc] = (float)((double)bt - mean * (double)sc);
             out4[2 * CT + cc] = (float)mean;
             out4[3 * CT + cc] = invstd;
             out4[4 * CT + cc] = g;                          // the affine weight per (group, channel): what the backward's apply kernel reads

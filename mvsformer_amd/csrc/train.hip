@@ -7,6 +7,7 @@
 // combined in a fixed order by a second tiny kernel (no float atomics: BatchNorm statistics repeat bit-exactly run to run,
 // which matters because the training head is an arg-max - a one-ulp change in a logit can move a whole hypothesis window).
 #include "common.h"
+#include "reduce_f64.h"
 
 namespace {
 
@@ -46,24 +47,39 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
-// part[p][c] = sum x, part[p][C + c] = sum x^2 over this block's share of channel c; p = b * gridDim.x + blockIdx.x
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int C, size_t N, float* __restrict__ part) {
-    __shared__ float red[8];
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
+    return t;
+}
+
+// part[p][c] = sum x, part[p][C + c] = sum x^2 over this block's share of channel c; p = b * gridDim.x + blockIdx.x.
+// Both sums are DOUBLE from the lane accumulators on (an fp32 product is exact in double): the finalize kernels form
+// var = sum x^2 / n - mean^2, which cancels |mean/std|^2 of the leading digits - fp32 sums leave nothing of the variance of a channel
+// whose mean is 100 standard deviations from zero.  The kernel stays bound by its one read of x (2 fp64 ops per 4 bytes).
+__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int C, size_t N, double* __restrict__ part) {
+    __shared__ double red[8];
     const int c = blockIdx.y, b = blockIdx.z;
     const float* row = x + ((size_t)b * C + c) * N;
-    float s = 0.0f, q = 0.0f;
+    double s = 0.0, q = 0.0;
     for (size_t i0 = (size_t)blockIdx.x * CHUNK; i0 < N; i0 += (size_t)gridDim.x * CHUNK) {
         const size_t i1 = min(i0 + CHUNK, N);
         for (size_t i = i0 + threadIdx.x; i < i1; i += 256) {
-            const float v = row[i];
+            const double v = (double)row[i];
             s += v;
-            q = fmaf(v, v, q);
+            q = fma(v, v, q);
         }
     }
     s = block_sum(s, red);
     q = block_sum(q, red);
     if (threadIdx.x == 0) {
-        float* o = part + ((size_t)b * gridDim.x + blockIdx.x) * 2 * C;
+        double* o = part + ((size_t)b * gridDim.x + blockIdx.x) * 2 * C;
         o[c] = s;
         o[C + c] = q;
     }
@@ -77,20 +93,21 @@ __device__ __forceinline__ double resolve_count(double count_host, const float* 
 }
 
 // mean/var from the (possibly all-reduced) sums; eval-style scale/shift for the apply kernel; running-stat update
-__global__ void bn_finalize_kernel(const float* __restrict__ sums, const float* __restrict__ gamma, const float* __restrict__ beta,
+__global__ void bn_finalize_kernel(const double* __restrict__ sums, const float* __restrict__ gamma, const float* __restrict__ beta,
                                    float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps,
                                    double count_host, const float* __restrict__ count_dev, int C, float* __restrict__ scale,
                                    float* __restrict__ shift, float* __restrict__ mean_out, float* __restrict__ invstd_out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double count = resolve_count(count_host, count_dev);
-    const double mean = (double)sums[c] / count;
-    double var = (double)sums[C + c] / count - mean * mean;
+    const double mean = sums[c] / count;
+    double var = sums[C + c] / count - mean * mean;
     if (var < 0.0) var = 0.0;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
     const float g = gamma ? gamma[c] : 1.0f, bt = beta ? beta[c] : 0.0f;
-    scale[c] = g * invstd;
-    shift[c] = bt - (float)mean * g * invstd;
+    const float sc = g * invstd;
+    scale[c] = sc;
+    shift[c] = (float)((double)bt - mean * (double)sc);     // against the ROUNDED scale: x*scale + shift = (x - mean)*scale + beta, one rounding of |mean/std|
     mean_out[c] = (float)mean;
     invstd_out[c] = invstd;
     if (running_mean) {
@@ -103,7 +120,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums, const float* 
 // Grouped form: the tensor holds `groups` independent BatchNorm calls of the SAME module side by side as channels
 // g*C + c (the visibility CNN is applied once per source view in the reference, mvsformer_model.py:91: statistics per view,
 // one set of affine parameters, running statistics updated once per call IN ORDER).  One thread per base channel walks the groups.
-__global__ void bn_finalize_grouped_kernel(const float* __restrict__ sums, const float* __restrict__ gamma, const float* __restrict__ beta,
+__global__ void bn_finalize_grouped_kernel(const double* __restrict__ sums, const float* __restrict__ gamma, const float* __restrict__ beta,
                                            float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps,
                                            double count_host, const float* __restrict__ count_dev, int C, int groups,
                                            float* __restrict__ scale, float* __restrict__ shift,
@@ -116,12 +133,13 @@ __global__ void bn_finalize_grouped_kernel(const float* __restrict__ sums, const
     float rm = running_mean ? running_mean[c] : 0.0f, rv = running_var ? running_var[c] : 0.0f;
     for (int q = 0; q < groups; ++q) {
         const int cc = q * C + c;
-        const double mean = (double)sums[cc] / count;
-        double var = (double)sums[CT + cc] / count - mean * mean;
+        const double mean = sums[cc] / count;
+        double var = sums[CT + cc] / count - mean * mean;
         if (var < 0.0) var = 0.0;
         const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        scale[cc] = g * invstd;
-        shift[cc] = bt - (float)mean * g * invstd;
+        const float sc = g * invstd;
+        scale[cc] = sc;
+        shift[cc] = (float)((double)bt - mean * (double)sc);
         mean_out[cc] = (float)mean;
         invstd_out[cc] = invstd;
         const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
@@ -269,8 +287,8 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
 }
 
 dim3 row_grid(int B, int C, size_t N) { return dim3((unsigned)((N + CHUNK - 1) / CHUNK), C, B); }
-// reductions end in one fp32 atomic per block on 2C addresses, and same-address atomics serialize in L2: cap the blocks per
-// (b, c) row (grid-stride over chunks) so that a channel has at most ~RED_ADDERS partial sums instead of N/4096
+// cap the blocks per (b, c) row (grid-stride over chunks) so that a channel has at most ~RED_ADDERS partial rows for the fixed-order
+// second launch to add, instead of N/4096
 constexpr int RED_ADDERS = 48;
 dim3 reduce_grid(int B, int C, size_t N) {
     size_t nb = (N + CHUNK - 1) / CHUNK;
@@ -284,19 +302,19 @@ dim3 reduce_grid(int B, int C, size_t N) {
 extern "C" int64_t mvs_bn_reduce_workspace_bytes(int B, int C, int64_t N) {
     if (B < 1 || C < 1 || N < 1) return -1;
     const dim3 g = reduce_grid(B, C, (size_t)N);
-    return (int64_t)g.x * B * 2 * C * (int64_t)sizeof(float);
+    return (int64_t)g.x * B * 2 * C * (int64_t)sizeof(double);      // mvs_bn_stats' rows are double; mvs_bn_bwd_reduce's float rows fit
 }
 
-extern "C" int mvs_bn_stats(const float* x, int B, int C, int64_t N, float* sums, void* workspace, mvs_stream_t stream) {
+extern "C" int mvs_bn_stats(const float* x, int B, int C, int64_t N, double* sums, void* workspace, mvs_stream_t stream) {
     MVS_REQUIRE(x && sums && workspace && B >= 1 && C >= 1 && C <= 65535 && B <= 65535 && N >= 1, "mvs_bn_stats: bad arguments");
     const dim3 g = reduce_grid(B, C, (size_t)N);
-    float* part = reinterpret_cast<float*>(workspace);
+    double* part = reinterpret_cast<double*>(workspace);
     hipLaunchKernelGGL(bn_stats_kernel, g, dim3(256), 0, MVS_STREAM(stream), x, C, (size_t)N, part);
     mvs::launch_partials_reduce(part, (int)(g.x * B), 2 * C, sums, MVS_STREAM(stream));
     return mvs::finish_launch("mvs_bn_stats");
 }
 
-extern "C" int mvs_bn_finalize(const float* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
+extern "C" int mvs_bn_finalize(const double* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
                                float momentum, float eps, double count, const float* count_dev, int C, float* scale, float* shift,
                                float* mean, float* invstd, mvs_stream_t stream) {
     MVS_REQUIRE(sums && scale && shift && mean && invstd && C >= 1 && (count_dev || count >= 1.0), "mvs_bn_finalize: bad arguments");
@@ -305,7 +323,7 @@ extern "C" int mvs_bn_finalize(const float* sums, const float* gamma, const floa
     return mvs::finish_launch("mvs_bn_finalize");
 }
 
-extern "C" int mvs_bn_finalize_grouped(const float* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
+extern "C" int mvs_bn_finalize_grouped(const double* sums, const float* gamma, const float* beta, float* running_mean, float* running_var,
                                        float momentum, float eps, double count, const float* count_dev, int C, int groups, float* scale,
                                        float* shift, float* mean, float* invstd, mvs_stream_t stream) {
     MVS_REQUIRE(sums && scale && shift && mean && invstd && C >= 1 && groups >= 1 && (count_dev || count >= 1.0),

@@ -66,7 +66,7 @@ class BiasFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         C = dy.shape[1]
-        return dy, (ops.bn_stats(dy.contiguous())[:C] if ctx.needs_input_grad[1] else None)
+        return dy, (ops.bn_stats(dy.contiguous())[:C].float() if ctx.needs_input_grad[1] else None)
 
 
 class UpsampleAddFn(torch.autograd.Function):

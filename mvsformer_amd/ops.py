@@ -793,18 +793,18 @@ def _reduce_ws(fn: str, device, *shape) -> torch.Tensor:
 
 
 def bn_stats(x: torch.Tensor) -> torch.Tensor:
-    """``x [B,C,...]`` -> ``sums [2C]`` (sum, sum of squares per channel)."""
+    """``x [B,C,...]`` -> ``sums [2C]`` (sum, sum of squares per channel), fp64: ``bn_finalize`` subtracts them."""
     _chk(x, "x")
     B, C = x.shape[0], x.shape[1]
     N = x.numel() // (B * C)
-    sums = torch.empty(2 * C, device=x.device, dtype=torch.float32)
+    sums = torch.empty(2 * C, device=x.device, dtype=torch.float64)
     ws = _reduce_ws("mvs_bn_reduce_workspace_bytes", x.device, B, C, N)
     _call("mvs_bn_stats", None, _ptr(x), B, C, N, _ptr(sums), _ptr(ws), _stream())
     return sums
 
 
 def _bn_args(sums, gamma, beta, running_mean, running_var, count_dev):
-    _chk(sums, "sums"), _opt(gamma, "bn.weight"), _opt(beta, "bn.bias"), _opt(running_mean, "bn.running_mean")
+    _chk(sums, "sums", dtype=torch.float64), _opt(gamma, "bn.weight"), _opt(beta, "bn.bias"), _opt(running_mean, "bn.running_mean")
     _opt(running_var, "bn.running_var"), _opt(count_dev, "count_dev")
 
 
@@ -1308,7 +1308,7 @@ def bf16_conv3d_stats(x, wpacked, cin, cout, gather: int, stride, groups: int = 
     if B % groups:
         raise _lib.MvsHipError("grouped statistics: batch %d is not a multiple of %d groups" % (B, groups))
     y = torch.empty(B, Do, Ho, Wo, cout, device=x.device, dtype=torch.bfloat16)
-    sums = torch.empty(2 * groups * cout, device=x.device, dtype=torch.float32)
+    sums = torch.empty(2 * groups * cout, device=x.device, dtype=torch.float64)
     ws = _reduce_ws("mvs_bf16_conv3d_stats_workspace_bytes", x.device, B, cout, Do, Ho, Wo)
     flops = 2.0 * 27 * cin * cout * B * (Do * Ho * Wo if gather == 0 else Di * Hi * Wi)
     tag = ("bf16_conv_kernel<%d,%d,g%d,s%d%d>" % (cin, cout, gather, sd, shw), "flops", flops)
@@ -1405,10 +1405,10 @@ def _bf16_bn_shape(x: torch.Tensor, groups: int):
 
 
 def bf16_bn_stats(x: torch.Tensor, groups: int = 1) -> torch.Tensor:
-    """-> ``sums [2*groups*C]``: [sum | sum of squares] per (group, channel)."""
+    """-> ``sums [2*groups*C]`` (fp64): [sum | sum of squares] per (group, channel)."""
     _chk16(x, "x")
     C, R, rps = _bf16_bn_shape(x, groups)
-    sums = torch.empty(2 * groups * C, device=x.device, dtype=torch.float32)
+    sums = torch.empty(2 * groups * C, device=x.device, dtype=torch.float64)
     ws = _reduce_ws("mvs_bf16_bn_reduce_workspace_bytes", x.device, C, R, groups, rps)
     _call("mvs_bf16_bn_stats", "bf16_bn_stats", _ptr(x), C, R, groups, rps, _ptr(sums), _ptr(ws), _stream())
     return sums

@@ -525,3 +525,190 @@ def test_skiplink_and_grouped_wgrad_do_not_change_gradients(dev, C, ndepth, H, W
         assert rel < 2e-2, (n, rel)
     a, b = torch.cat(va), torch.cat(vb)
     assert (a @ b / (a.norm() * b.norm() + 1e-30)).item() > 0.995
+
+
+def _var_tol(mean, var, rows=1):
+    """Bound on the relative error of a batch variance formed as sum x^2 / n - mean^2: a relative error e in either sum shows as
+    e * (1 + (mean/std)^2) in the difference.  The bf16 kernels' partial rows are fp32 values of one block's share (the statistics
+    kernel rounds a double sum once; the convolution epilogue adds up to 256 voxels in fp32: 4 x 2^-24 allowed per row), everything
+    after them is double, so the independent errors of ``rows`` partial rows average to 1 / sqrt(rows) of that; the result is rounded to
+    fp32 once (2^-24, not amplified).  (The statistics kernel first kept fp32 chains inside a block and missed this bound at mean/std 4
+    with 2.9e-7 against 2.4e-7: chains over like-sized terms round with a common bias that does not average out.  It now accumulates in
+    double up to the row.)  Measured on the MI355X at mean/std 16:
+    with the rows added in fp32 (before) 1.9e-5 .. 2.8e-5 at 2^18 rows and 2.0e-5 .. 2.5e-5 in the convolution epilogue, which this bound
+    refuses; with double 2.3e-7 .. 8.3e-7 and 8e-9 .. 5e-8."""
+    r2 = float(mean) ** 2 / max(float(var), 1e-300)
+    return 4.0 * 2.0 ** -24 * (1.0 + r2) / rows ** 0.5 + 2.0 ** -24
+
+
+def _mean_tol(mean, var):
+    """The same for the mean, relative to itself: the sum's error is 4 x 2^-24 of |mean| + std (the size of its terms)."""
+    return 4.0 * 2.0 ** -24 * (1.0 + float(var) ** 0.5 / max(abs(float(mean)), 1e-300))
+
+
+BF16_LADDER = [(r, s) for r in (0.0, 4.0, 16.0) for s in (1e-2, 1.0, 1e2)]      # |mean|/std up to 16: bf16 data (8 bits) cannot hold more
+
+
+@pytest.mark.parametrize("shape", [(2, 16, 5, 6, 7), (1, 16, 8, 128, 256)], ids=["short-210", "long-2^18"])
+def test_bn_act_bf16_offset_ladder(dev, shape):
+    """Channels whose mean is 0 / 4 / 16 standard deviations from zero at std 1e-2 / 1 / 1e2 through the bf16 BatchNorm kernels
+    (mvs_bf16_bn_train_fwd, mvs_bf16_bn_stats + mvs_bn_finalize, mvs_bf16_bn_bwd_reduce / _apply).  Reference: fp64 BatchNorm of the
+    bf16-ROUNDED input on the CPU.  momentum = 1: running_var is the batch variance.  Each channel on its own (their scales differ by
+    1e4); tolerances are test_bn_act_bf16_fn's on the bf16 tensors (1e-2 / 1.5e-2); the fp32 statistics are held to ``_var_tol`` / ``_mean_tol``,
+    which the fp32 sums of the earlier kernels miss at mean/std = 16 (figures in DESIGN.md section 5)."""
+    import torch.nn as nn
+    from mvsformer_amd import autograd as ag, ops
+    C = shape[1]
+    chans = BF16_LADDER + [(0.0, 1.0)] * (C - len(BF16_LADDER))
+    gen = torch.Generator().manual_seed(23)
+    x = torch.randn(*shape, generator=gen)
+    for c, (r, s) in enumerate(chans):
+        x[:, c] = (x[:, c] + r) * s
+    x = bf(x)
+    R = bf(torch.randn(x.shape, generator=gen))
+    gamma, beta = torch.rand(C, generator=gen) + 0.5, torch.randn(C, generator=gen)
+    xr = x.double().requires_grad_(True)
+    g64, b64 = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    rm, rv = torch.zeros(C, dtype=torch.float64), torch.ones(C, dtype=torch.float64)
+    y = F.batch_norm(xr, rm, rv, g64, b64, True, 1.0, 1e-5)
+    (y * R.double()).sum().backward()
+    bn = nn.BatchNorm3d(C, momentum=1.0)
+    with torch.no_grad():
+        bn.weight.copy_(gamma)
+        bn.bias.copy_(beta)
+    bn = bn.to(dev)
+    xm = to_cl(x, dev).requires_grad_(True)
+    ym = ag.BnActBf16Fn.apply(xm, bn.weight, bn.bias, None, bn, False)
+    (ym.float() * R.permute(0, 2, 3, 4, 1).to(dev)).sum().backward()
+    ymc, dxc = from_cl(ym.detach()), from_cl(xm.grad)
+    # the unfused chain (what SyncBatchNorm and the convolution-epilogue statistics feed): same statistics from mvs_bf16_bn_stats + mvs_bn_finalize
+    sums = ops.bf16_bn_stats(xm.detach())
+    rm2, rv2 = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+    ops.bn_finalize(sums, bn.weight.detach(), bn.bias.detach(), rm2, rv2, 1.0, 1e-5, float(x.numel() // C))
+    bad = []
+    for c, (r, s) in enumerate(chans[:len(BF16_LADDER)]):
+        # partial rows: 512 blocks of 512 rows at 2^18 rows (bn_shape in csrc/bf16_train.hip); the short tensor is counted as one
+        vtol, mtol = _var_tol(rm[c], rv[c], 512 if x.numel() // C >= 2 ** 18 else 1), _mean_tol(rm[c], rv[c])
+        for what, got, want, tol in (("running_var", bn.running_var[c], rv[c], vtol), ("running_mean", bn.running_mean[c], rm[c], mtol),
+                                     ("running_var (stats + finalize)", rv2[c], rv[c], vtol), ("running_mean (stats + finalize)", rm2[c], rm[c], mtol),
+                                     ("y", ymc[:, c], y.detach()[:, c], 1e-2), ("dx", dxc[:, c], xr.grad[:, c], 1.5e-2)):
+            got64, want64 = torch.as_tensor(got).detach().double().cpu(), torch.as_tensor(want).detach().double().cpu()
+            err = (got64 - want64).abs().max().item() / max(want64.abs().max().item(), 1e-12)
+            print("bf16 ladder %s mean/std=%g std=%g %s: err %.3e (tol %.1e)" % (shape, r, s, what, err, tol))
+            if not err < tol:
+                bad.append((r, s, what, err, tol))
+    assert not bad, bad
+    relclose(bn.weight.grad, g64.grad, 1e-2, "dgamma")
+    relclose(bn.bias.grad, b64.grad, 1e-2, "dbeta")
+
+
+@pytest.mark.parametrize("groups", [1, 2])
+def test_conv_bf16_epilogue_statistics_offset_ladder(dev, groups):
+    """The statistics taken in the convolution's epilogue at an offset: a convolution whose output channels have mean/std of about 0.6, 5
+    and 16 at scales 1e-2 / 1 / 1e2 (input 1 + randn/8, centre-tap weights of 4, 5 or 7 positive and the rest negative input channels plus
+    small random taps), through ``ops.bf16_conv3d_stats`` + ``bn_finalize(_grouped)`` (the fp32 block rows added in double by
+    ``launch_partials_reduce_grouped``) and through ``ops.bf16_conv3d_bn_fwd`` (``bf16_bn_rows_finalize_kernel``; what ``LayerBf16Fn`` runs).
+    Reference: fp64 BatchNorm of the bf16-ROUNDED convolution output (the plain ``bf16_conv3d``'s, bit-identical to the fused forms'), per
+    group (sample b belongs to group b % groups).  momentum = 1: the running variance is the last group's batch variance; the per-group
+    mean / invstd come from the finalize outputs.  Statistics to ``_var_tol`` / ``_mean_tol``, the normalized bf16 output to 1e-2."""
+    from mvsformer_amd import ops
+    cin, cout, N, D, H, W = 8, 16, 4, 4, 12, 40
+    gen = torch.Generator().manual_seed(5)
+    x = (1.0 + 0.125 * torch.randn(N, D, H, W, cin, generator=gen)).to(torch.bfloat16)
+    npos = [4, 5, 7] * 3 + [4] * 7
+    scale = [1e-2] * 3 + [1.0] * 3 + [1e2] * 3 + [1.0] * 7
+    w = torch.randn(cout, cin, 3, 3, 3, generator=gen) * 0.01
+    for c in range(cout):
+        sign = torch.tensor([1.0] * npos[c] + [-1.0] * (cin - npos[c]))
+        w[c, :, 1, 1, 1] += sign * (0.75 + 0.5 * torch.rand(cin, generator=gen))
+        w[c] *= scale[c]
+    gamma, beta = torch.rand(cout, generator=gen) + 0.5, torch.randn(cout, generator=gen)
+    xm, gm, bm = x.to(dev), gamma.to(dev), beta.to(dev)
+    wp = ops.bf16_pack(w.to(dev), 0, cin, cout)
+    y0 = ops.bf16_conv3d(xm, wp, cin, cout, 0, (1, 1))
+    yf = y0.float().cpu().double()                            # [N, D, H, W, C]
+    count = float(yf.numel() // (cout * groups))
+    mean = torch.stack([yf[g::groups].reshape(-1, cout).mean(0) for g in range(groups)])                       # [groups, C]
+    var = torch.stack([yf[g::groups].reshape(-1, cout).var(0, unbiased=False) for g in range(groups)])
+    ratio = (mean.abs() / var.sqrt())[:, :9]
+    print("mean/std of the ladder channels:", [round(v, 2) for v in ratio[0].tolist()])
+    assert ratio[:, 2::3].min() > 12.0 and ratio[:, 1::3].min() > 3.0      # the ladder is there (a property of the inputs, checked on the reference)
+    want_z = torch.empty_like(yf)
+    for g in range(groups):
+        want_z[g::groups] = (yf[g::groups] - mean[g]) / torch.sqrt(var[g] + 1e-5) * gamma.double() + beta.double()
+
+    def compare(tag, mean_got, invstd_got, rm, rv):
+        bad = []
+        for g in range(groups):
+            for c in range(9):
+                # block rows: N*D*H*ceil(W/64) = 192 work items, four to a block -> 48 rows (one per item in the stats form), split over the groups
+                vtol, mtol = _var_tol(mean[g, c], var[g, c], 48 // groups), _mean_tol(mean[g, c], var[g, c])
+                checks = [("mean", mean_got[g, c], mean[g, c], mtol), ("invstd", invstd_got[g, c], 1.0 / torch.sqrt(var[g, c] + 1e-5), vtol)]
+                if g == groups - 1:                          # momentum 1: the running statistics hold the LAST group's update
+                    checks += [("running_mean", rm[c], mean[g, c], mtol), ("running_var", rv[c], var[g, c] * count / (count - 1.0), vtol)]
+                for what, got, want, tol in checks:
+                    err = abs(float(got) - float(want)) / abs(float(want))
+                    print("%s group %d mean/std=%.2f scale=%g %s: err %.3e (tol %.1e)" % (tag, g, ratio[g, c], scale[c], what, err, tol))
+                    if not err < tol:
+                        bad.append((tag, g, c, what, err, tol))
+        return bad
+
+    # (a) epilogue statistics + the shared finalize
+    y1, sums = ops.bf16_conv3d_stats(xm, wp, cin, cout, 0, (1, 1), groups)
+    assert torch.equal(y0, y1)
+    rm, rv = torch.zeros(cout, device=dev), torch.ones(cout, device=dev)
+    if groups > 1:
+        _, _, mu, istd = ops.bn_finalize_grouped(sums, gm, bm, rm, rv, 1.0, 1e-5, count, groups)
+    else:
+        _, _, mu, istd = ops.bn_finalize(sums, gm, bm, rm, rv, 1.0, 1e-5, count)
+    bad = compare("conv3d_stats + finalize", mu.double().cpu().view(groups, cout), istd.double().cpu().view(groups, cout), rm.cpu(), rv.cpu())
+    # (b) the fused layer forward
+    rm2, rv2 = torch.zeros(cout, device=dev), torch.ones(cout, device=dev)
+    y2, z, st = ops.bf16_conv3d_bn_fwd(xm, wp, cin, cout, 0, (1, 1), None, False, gm, bm, rm2, rv2, 1.0, 1e-5, groups)
+    assert torch.equal(y0, y2)
+    bad += compare("conv3d_bn_fwd", st[2].double().cpu().view(groups, cout), st[3].double().cpu().view(groups, cout), rm2.cpu(), rv2.cpu())
+    assert not bad, bad
+    zf = z.float().cpu().double()
+    for c in range(9):
+        relclose(zf[..., c], want_z[..., c], 1e-2, "z channel %d" % c)
+
+
+# rows per block of the bf16 reduce kernels (bn_shape in csrc/bf16_train.hip): a multiple of 256 / (C/8) rows, at least two sweeps, at most 2048,
+# sized for ~512 blocks.  C = 8: blocks of 512 rows; C = 64: blocks of 64 rows; 2048 * 513 + 5 rows: the 2048-row cap binds and the last block is
+# ragged.  Two rows is the smallest batch torch's BatchNorm reference accepts (N = 1 of the fp32 list has no bf16 twin for that reason).
+BF16_ROWS = [(8, 2), (8, 511), (8, 512), (8, 513), (64, 63), (64, 64), (64, 65), (8, 2048 * 513 + 5)]
+
+
+@pytest.mark.parametrize("C,R", BF16_ROWS)
+def test_bn_act_bf16_row_lengths(dev, C, R):
+    """``BnActBf16Fn`` (mvs_bf16_bn_train_fwd, mvs_bf16_bn_bwd_reduce, mvs_bf16_bn_bwd_apply) at row counts around one block of the reduce
+    kernels and above the point where the rows-per-block cap binds, against fp64 BatchNorm of the bf16-rounded input.  No ReLU: a margin
+    around its kink wide enough for bf16 outputs (1e-2 of max|y|) would exclude 3 % of the elements; the gate itself is
+    test_bn_act_bf16_fn's.  Tolerances are that test's; the statistics are held to ``_var_tol`` / ``_mean_tol``."""
+    import torch.nn as nn
+    from mvsformer_amd import autograd as ag
+    gen = torch.Generator().manual_seed(C + R % 1000)
+    x = bf(torch.randn(1, C, 1, 1, R, generator=gen) * 2 + 0.5)
+    Rw = bf(torch.randn(x.shape, generator=gen))
+    gamma, beta = torch.rand(C, generator=gen) + 0.5, torch.randn(C, generator=gen)
+    xr = x.double().requires_grad_(True)
+    g64, b64 = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    rm, rv = torch.zeros(C, dtype=torch.float64), torch.ones(C, dtype=torch.float64)
+    y = F.batch_norm(xr, rm, rv, g64, b64, True, 1.0, 1e-5)
+    (y * Rw.double()).sum().backward()
+    bn = nn.BatchNorm3d(C, momentum=1.0)
+    with torch.no_grad():
+        bn.weight.copy_(gamma)
+        bn.bias.copy_(beta)
+    bn = bn.to(dev)
+    xm = to_cl(x, dev).requires_grad_(True)
+    ym = ag.BnActBf16Fn.apply(xm, bn.weight, bn.bias, None, bn, False)
+    (ym.float() * Rw.permute(0, 2, 3, 4, 1).to(dev)).sum().backward()
+    relclose(from_cl(ym.detach()), y.detach(), 1e-2, "y")
+    relclose(from_cl(xm.grad), xr.grad, 1.5e-2, "dx")
+    relclose(bn.weight.grad, g64.grad, 1e-2, "dgamma")
+    relclose(bn.bias.grad, b64.grad, 1e-2, "dbeta")
+    for c in range(C):
+        mean_c, var_c = x[0, c].double().mean(), x[0, c].double().var(unbiased=False)
+        relclose(bn.running_mean[c], rm[c], _mean_tol(mean_c, var_c), "running_mean[%d]" % c)
+        relclose(bn.running_var[c], rv[c], _var_tol(mean_c, var_c), "running_var[%d]" % c)
