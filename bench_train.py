@@ -8,6 +8,7 @@ under ``torch.autocast(bfloat16)`` as the reference trainer does (trainer/mvsfor
 bf16 matrix cores, fp32 cost volume / statistics / head / loss / master weights; ``--dtype f32`` keeps everything fp32.
 
     python bench_train.py --steps 10 [--gpus N]          (N > 1 without a launcher: spawns one rank per GPU itself)
+    python bench_train.py --recipe reference [--optimizer torch]   (parameter groups + LambdaLR + GradScaler + norm clipping in the same capture)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 bench_train.py --gpus 8 --steps 10
 """
 import argparse
@@ -40,7 +41,31 @@ def parse(argv=None):
                          "step 13-22 ms (box dependent) -> 0.4 ms, so the step runs at the GPU's pace whatever the host does; auto = on, with an "
                          "eager fallback if the capture fails.  Under DistributedDataParallel + SyncBatchNorm the RCCL all-reduces are "
                          "captured with the kernels (DDP constructed, warmed up for 12 iterations and captured on one side stream)")
+    ap.add_argument("--recipe", choices=["plain", "reference"], default="plain",
+                    help="plain: one parameter group, one constant learning rate (the record this file has always printed); reference: the "
+                         "reference trainer's recipe (train.py:78-100, trainer/mvsformer_trainer.py:39-45, 150-167) inside the same ONE capture - "
+                         "layer-wise style parameter groups, a warm-up-cosine LambdaLR stepped after every step, torch.amp.GradScaler and "
+                         "global-norm clipping: FusedAdamW(groups, device_hyper=True, max_grad_norm=...), whose changing inputs live on the "
+                         "device (--optimizer torch: torch.optim.AdamW(fused, capturable) with tensor learning rates + "
+                         "torch.nn.utils.clip_grad_norm_, the A/B line)")
+    ap.add_argument("--groups", type=int, default=28, help="--recipe reference: parameter groups (28 = the reference's 27 layer-wise ViT groups + the rest)")
+    ap.add_argument("--max-grad-norm", type=float, default=5.0, help="--recipe reference: global gradient-norm clip (trainer.grad_norm)")
     return ap.parse_args(argv)
+
+
+def recipe_groups(model, ngroups, lr=1e-4, weight_decay=0.01, layer_decay=0.75):
+    """Parameter groups shaped like the reference's layer-wise decay (models/lr_decay.py): the tensors in order are cut into ngroups / 2
+    consecutive "layers", each split into decayed (ndim > 1) and not decayed tensors; the rate falls by ``layer_decay`` per layer."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    layers = max(1, ngroups // 2)
+    groups = {}
+    for k, p in enumerate(params):
+        layer = k * layers // len(params)
+        key = (layer, p.ndim > 1)
+        if key not in groups:
+            groups[key] = dict(params=[], lr=lr * layer_decay ** (layers - 1 - layer), weight_decay=weight_decay if p.ndim > 1 else 0.0)
+        groups[key]["params"].append(p)
+    return list(groups.values())
 
 
 def measure(args, top=12):
@@ -76,7 +101,46 @@ def measure(args, top=12):
     # AdamW as the reference trainer builds it (train.py:98), as mvsformer_amd.optim.FusedAdamW: the same update in three launches of 2048-value
     # blocks (--optimizer torch: torch.optim.AdamW(fused=True, capturable=True), five launches of 40 us - one block per tensor chunk; its
     # default capturable form spends 304 elementwise launches and 1.1 ms of the step on bias corrections)
-    if args.optimizer == "hip":
+    reference = getattr(args, "recipe", "plain") == "reference"
+    sched = scaler = None
+    if reference:
+        import math
+        groups = recipe_groups(model, args.groups)
+        if args.optimizer == "hip":
+            from mvsformer_amd.optim import FusedAdamW
+            opt = FusedAdamW(groups, lr=1e-4, device_hyper=True, max_grad_norm=args.max_grad_norm)
+        else:                                                # a captured torch step sees a moving rate only through tensor learning rates
+            base_lrs = [g["lr"] for g in groups]
+            for g in groups:
+                g["lr"] = torch.tensor(g["lr"], device=dev, dtype=torch.float32)
+            opt = torch.optim.AdamW(groups, lr=torch.tensor(1e-4, device=dev), capturable=True, fused=True)
+        total, warm = args.warmup + args.steps + 16, 8       # the warm-up ends inside the run: both branches of the schedule are timed
+
+        def lr_lambda(it, min_lr=0.01):                      # warm-up, then half a cosine down to min_lr (the shape of train.py:99's schedule)
+            if it < warm:
+                return (it + 1) / warm
+            return min_lr + (1.0 - min_lr) * 0.5 * (1.0 + math.cos(math.pi * (it - warm) / max(1, total - warm)))
+
+        if args.optimizer == "hip":
+            sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda)
+        else:
+            # LambdaLR on tensor rates multiplies on the device and reads the product back (one .item() per group and step); the same
+            # schedule from host floats, one fill per group, is the best the torch side can do and what the A/B line measures
+            class HostLambda:
+                it = 0
+
+                def step(self):
+                    self.it += 1
+                    self.write()
+
+                def write(self):
+                    for g, base in zip(opt.param_groups, base_lrs):
+                        g["lr"].fill_(base * lr_lambda(self.it))
+
+            sched = HostLambda()
+            sched.write()
+        scaler = torch.amp.GradScaler("cuda")
+    elif args.optimizer == "hip":
         from mvsformer_amd.optim import FusedAdamW
         opt = FusedAdamW(model.parameters(), lr=1e-4)
     else:
@@ -98,6 +162,14 @@ def measure(args, top=12):
             out = model(feats, proj, dv, tmp=[5.0, 5.0, 5.0, 1.0])
         # the reference's loss for depth_type='ce' (trainer/mvsformer_trainer.py:119-120), fused HIP kernel per stage
         loss = sum(ce_loss_stage4(out, gts, masks, dlossw=[1, 1, 1, 1], inverse_depth=True).values())
+        if reference:                                        # trainer/mvsformer_trainer.py:150-165
+            scaler.scale(loss).backward()
+            if args.optimizer == "torch":
+                scaler.unscale_(opt)
+                torch.nn.utils.clip_grad_norm_(model.parameters(), args.max_grad_norm, error_if_nonfinite=False)
+            scaler.step(opt)                                 # FusedAdamW: norm, clip coefficient, 1 / scale and the overflow flag stay on the device
+            scaler.update()
+            return loss
         loss.backward()
         opt.step()
         return loss
@@ -108,11 +180,28 @@ def measure(args, top=12):
             from mvsformer_amd.graphs import CapturedStep
             # under DDP: the reducer's logger times its first 10 iterations with events (not capturable) and rebuilds its buckets after the
             # first one - torch's whole-network-capture recipe is >= 11 eager iterations first
-            step = CapturedStep(eager_step, warmup=12 if ddp else 3, keep_graph=True, stream=ddp_stream)
+            step = CapturedStep(eager_step, warmup=12 if ddp else 3, keep_graph=True, stream=ddp_stream,
+                                before_replay=[opt.sync_hyper] if reference and args.optimizer == "hip" else None)
         except Exception as e:                               # report, fall back to eager launches
             if args.graph == "on":
                 raise
             step, use_graph, graph_note = eager_step, False, "capture failed: %r" % (e,)
+    if reference:                                            # the scheduler moves the rate after EVERY step, eager or replayed (trainer :167)
+        inner_step = step
+
+        def scheduled_step():
+            loss = inner_step()
+            sched.step()
+            return loss
+
+        scheduled_step.node_counts = getattr(inner_step, "node_counts", None)
+        step = scheduled_step
+
+        def lr_now():                                        # the last group's rate as the DEVICE holds it (a device-side copy: no synchronisation)
+            if args.optimizer == "hip":
+                opt.sync_hyper()
+                return opt.hyper_table[-1, 0].clone()
+            return opt.param_groups[-1]["lr"].detach().clone()
     for _ in range(args.warmup):
         loss = step()
     torch.cuda.synchronize()
@@ -126,6 +215,7 @@ def measure(args, top=12):
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
+    lr_first = lr_now() if reference else None               # what the first timed step reads
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
@@ -133,6 +223,7 @@ def measure(args, top=12):
     if world > 1:
         dist.barrier()
     own_dt = time.perf_counter() - t0
+    lr_last = lr_now() if reference else None                # what the next step would read: the schedule went on through the timed region
     dt = torch.tensor([own_dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
@@ -182,6 +273,10 @@ def measure(args, top=12):
                           "unit": "samples/s", "n_gpus": world, "steps": args.steps, "ms_per_step": round(dt.item() / args.steps * 1e3, 2),
                           "host_enqueue_ms_per_step": round(t_enqueue * 1e3, 2), "hip_graph": use_graph, "graph_note": graph_note, "dtype": args.dtype, "data": "synthetic", "scaling": "weak", "final_loss": round(float(loss.detach()), 4),
                           "parallelism": "DDP + SyncBatchNorm over RCCL" if ddp else "single GPU"})
+    if rec is not None and reference:
+        skipped = int(opt.skipped_steps) if args.optimizer == "hip" else None      # torch's scaler keeps no count
+        rec.update(recipe="reference", optimizer=args.optimizer, groups=len(opt.param_groups), max_grad_norm=args.max_grad_norm,
+                   lr_first=float(lr_first), lr_last=float(lr_last), skipped_steps=skipped, loss_scale=float(scaler.get_scale()))
     if ddp and not getattr(args, "keep_process_group", False):
         dist.destroy_process_group()
     return rec

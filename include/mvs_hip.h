@@ -44,7 +44,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 42
+#define MVS_ABI_VERSION 43
 
 typedef void* mvs_stream_t;
 
@@ -807,6 +807,43 @@ typedef struct MvsAdamTensor {
 } MvsAdamTensor;
 int mvs_adamw_step(const MvsAdamTensor* tensors, int ntensors, float lr, float beta1, float beta2, float eps, float weight_decay, int maximize,
                    float* step, mvs_stream_t stream);
+
+/* ---- The reference's training recipe with every CHANGING input on the device, so that one captured hipGraph serves a whole run:
+ * layer-wise parameter groups (train.py:82-98, models/lr_decay.py:13-83), a learning rate that moves every step (LambdaLR, train.py:99,
+ * trainer/mvsformer_trainer.py:167), a GradScaler (trainer :43-45, 150-165) and global-norm clipping (trainer :39, 157-160).
+ * An entry of the tensor table (HOST array, as above) names its parameter group; the entries of ALL groups share the launches.
+ *
+ * mvs_adamw_multi   mvs_adamw_step's update (same arithmetic and order: bit-identical for one group and grad_mul = 1) with, per group gi,
+ *                   hyper[gi][MVS_ADAM_HYPER_STRIDE] = {lr, weight_decay, beta1, beta2, eps, maximize (0 / 1), 0, 0} and the count step[gi]
+ *                   read from DEVICE memory.  grad_mul (device scalar or NULL = 1): every gradient is multiplied by it on read (clip
+ *                   coefficient / loss scale).  skip (device scalar or NULL = 0): non-zero = the call changes nothing - parameters, moments
+ *                   and counts keep their bits - and skipped_steps[0] (device, or NULL) += 1.  Otherwise the counts of the groups that
+ *                   have an entry advance by one after the updates.  ngroups <= 1024.
+ * mvs_grad_norm     the global L2 norm of the entries' gradients without atomics, in a fixed order (same bits every run): one block per
+ *                   2048 values, squares summed in double into workspace (mvs_grad_norm_workspace_bytes(...) bytes, 8-byte aligned); one
+ *                   block adds the partials and writes  norm[0] = |g| / grad_scale  (the norm of the UNSCALED gradients; grad_scale = device
+ *                   scalar or NULL = 1),  grad_mul[0] = min(1, max_norm / (norm + 1e-6)) / grad_scale  (torch.nn.utils.clip_grad_norm_'s
+ *                   coefficient; max_norm <= 0 or infinite: no clipping)  and, if skip is given,
+ *                   skip[0] = (found_inf && found_inf[0] != 0) || !isfinite(norm)   (found_inf: a GradScaler's device flag, or NULL).
+ * mvs_grad_scale_   g *= grad_mul[0] for every entry (the stand-alone clip_grad_norm_, which leaves the clipped gradients in place).
+ * mvs_grad_norm and mvs_grad_scale_ read g and n of an entry only.  All tensors fp32, contiguous, on the stream's device; 16-byte
+ * accesses where an entry's pointers are 16-byte aligned, 4-byte ones otherwise. */
+#define MVS_ADAM_HYPER_STRIDE 8
+typedef struct MvsAdamEntry {
+    float* p;                 /* parameter, updated in place */
+    float* g;                 /* its gradient (written by mvs_grad_scale_ only) */
+    float* m;                 /* exp_avg */
+    float* v;                 /* exp_avg_sq */
+    int64_t n;                /* elements */
+    int32_t group;            /* row of hyper[] / step[] */
+    int32_t reserved;         /* 0 */
+} MvsAdamEntry;
+int mvs_adamw_multi(const MvsAdamEntry* tensors, int ntensors, const float* hyper, int ngroups, float* step, const float* grad_mul,
+                    const int* skip, int* skipped_steps, mvs_stream_t stream);
+int64_t mvs_grad_norm_workspace_bytes(const MvsAdamEntry* tensors, int ntensors);
+int mvs_grad_norm(const MvsAdamEntry* tensors, int ntensors, float max_norm, const float* grad_scale, const float* found_inf, void* workspace,
+                  float* norm, float* grad_mul, int* skip, mvs_stream_t stream);
+int mvs_grad_scale_(const MvsAdamEntry* tensors, int ntensors, const float* grad_mul, mvs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ import torch  # noqa: F401  (load order, see above)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = os.environ.get("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 from ctypes import c_double  # noqa: E402
 
@@ -28,6 +28,15 @@ P, I, F, L, Dbl = c_void_p, c_int, c_float, c_int64, c_double
 class AdamTensor(ctypes.Structure):
     """``MvsAdamTensor`` of include/mvs_hip.h."""
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("n", ctypes.c_int64)]
+
+
+class AdamEntry(ctypes.Structure):
+    """``MvsAdamEntry`` of include/mvs_hip.h: a tensor of the multi-group table."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("n", ctypes.c_int64),
+                ("group", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+ADAM_HYPER_STRIDE = 8                                        # MVS_ADAM_HYPER_STRIDE: lr, weight_decay, beta1, beta2, eps, maximize, 0, 0
 
 
 class WgradJob(ctypes.Structure):
@@ -111,6 +120,10 @@ SIGNATURES = {
     "mvs_bf16_pack_table_run": (I, [P, I, I, P]),
     "mvs_bf16_conv3d_taps": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
     "mvs_adamw_step": (I, [P, I, F, F, F, F, F, I, P, P]),
+    "mvs_adamw_multi": (I, [P, I, P, I, P, P, P, P, P]),
+    "mvs_grad_norm_workspace_bytes": (L, [P, I]),
+    "mvs_grad_norm": (I, [P, I, F, P, P, P, P, P, P, P]),
+    "mvs_grad_scale_": (I, [P, I, P, P]),
     "mvs_bf16_wgrad_group_workspace_bytes": (L, [P, I]),
     "mvs_bf16_wgrad_group": (I, [P, I, P, L, P]),
     "mvs_bf16_conv3d_wgrad_taps": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),

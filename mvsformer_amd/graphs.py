@@ -22,10 +22,13 @@ class CapturedStep:
     """``step_fn()`` (no arguments, returns a tensor or a tuple of tensors) captured into a hipGraph after ``warmup`` eager runs on a
     side stream (lazy initialisation - weight-pack caches, hipFuncSetAttribute, allocator growth - must not happen during capture)."""
 
-    def __init__(self, step_fn: Callable[[], object], warmup: int = 3, keep_graph: bool = False, stream=None):
+    def __init__(self, step_fn: Callable[[], object], warmup: int = 3, keep_graph: bool = False, stream=None, before_replay=None):
         """``keep_graph``: keep the captured hipGraph_t beside the executable one, so :meth:`node_counts` can walk it.  ``stream``: the
         side stream to warm up AND capture on (DistributedDataParallel wants the stream it was constructed on: its reducer's
-        AccumulateGrad hooks remember it)."""
+        AccumulateGrad hooks remember it).  ``before_replay``: callables run at the start of every :meth:`__call__`, before the replay and
+        on its stream - how host-side state reaches a captured step (``[optimizer.sync_hyper]``: a learning-rate schedule refreshes the
+        device table the captured ``FusedAdamW(device_hyper=True)`` step reads)."""
+        self.before_replay = list(before_replay) if before_replay is not None else []
         if not torch.cuda.is_available():
             raise RuntimeError("CapturedStep needs a GPU")
         side = stream if stream is not None else torch.cuda.Stream()
@@ -68,6 +71,8 @@ class CapturedStep:
 
     def __call__(self):
         """Replay; returns the (static) output tensors of the captured step - clone them if they must outlive the next replay."""
+        for fn in self.before_replay:
+            fn()
         self.graph.replay()
         from . import ops
         ops.bump_weights_epoch()                             # the replay updates parameters / running statistics without passing through Python
