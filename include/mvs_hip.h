@@ -44,7 +44,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 43
+#define MVS_ABI_VERSION 44
 
 typedef void* mvs_stream_t;
 
@@ -638,6 +638,43 @@ int mvs_vis_filter_dynamic_fwd(const float* ref_depth, const float* reproj_xyd, 
  * depth_inplace (may be NULL) [n,HW] is multiplied by the mask (test.py:414-418). */
 int mvs_prob_filter(const float* conf, int n, int C, int64_t HW, const float* thresh_host, uint8_t* mask, float* depth_inplace,
                     mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Scene-resident fusion: a whole scan -> one coloured point cloud (test.py:404-549, filter_depth /
+ * dynamic_filter_depth), csrc/pointcloud.hip.  Every view is on the device once:
+ *   depth_ref [Nv,H,W] raw depth maps; depth_src [Nv,H,W] what a view contributes as a SOURCE (prob-filtered copy for
+ *   filter_depth, the same raw stack for dynamic_filter_depth); cams [Nv,2,4,4].
+ * Job table, DEVICE memory, validated by the caller: ref_idx [R], src_idx [R,Vmax] (padded with -1), n_src [R], all
+ * int32 indices into the view stacks.  One launch covers the R reference views; per-pixel results are bit-identical to
+ * mvs_geo_filter_fwd / mvs_geo_filter_dynamic_fwd on the gathered views (same device functions).  A job whose table row
+ * is inconsistent (index outside [0,Nv), n_src outside [1|2, Vmax]) reads nothing and writes zeros.
+ * Outputs (each may be NULL): mask / geo_mask uint8 [R,H,W], ref_depth_ave [R,H,W], points [R,3,H,W].
+ * workspace: mvs_geo_filter_scene_workspace_bytes(R, Vmax).  The dynamic form takes 2 <= n_src[r] <= Vmax <= 16. */
+int64_t mvs_geo_filter_scene_workspace_bytes(int R, int Vmax);
+int mvs_geo_filter_scene_fwd(const float* depth_ref, const float* depth_src, const float* cams, int Nv, const int32_t* ref_idx,
+                             const int32_t* src_idx, const int32_t* n_src, int R, int Vmax, int H, int W, float img_dist_thresh,
+                             float depth_thresh, float vthresh, void* workspace, uint8_t* mask, float* ref_depth_ave, float* points,
+                             mvs_stream_t stream);
+int mvs_geo_filter_dynamic_scene_fwd(const float* depth_ref, const float* depth_src, const float* cams, int Nv, const int32_t* ref_idx,
+                                     const int32_t* src_idx, const int32_t* n_src, int R, int Vmax, int H, int W, float dist_base,
+                                     float rel_diff_base, void* workspace, uint8_t* geo_mask, float* ref_depth_ave, float* points,
+                                     mvs_stream_t stream);
+/* Order-preserving compaction of the kept pixels, keep = photo_mask[ref_idx[r]] & geo_mask[r] (photo_mask [Nv,H*W],
+ * geo_mask [R,H*W], uint8), in the reference's order: jobs in table order, row-major inside a job.
+ * mvs_pointcloud_count: per-block counts and their 64-bit exclusive scan into workspace
+ * (mvs_pointcloud_workspace_bytes(R,H,W), 8-byte aligned), stats [R,3] int64 = exact per-job counts of photo / geo / kept
+ * pixels, *total = number of points (all device memory).  The caller reads total, allocates, and - unless it is 0 -
+ * calls mvs_pointcloud_scatter with the same masks and workspace: records [total*15 bytes] (x y z float32
+ * little-endian, r g b uint8: the PLY vertex body, 4-byte aligned base), xyz [total,3] float32, rgb [total,3] uint8
+ * (each may be NULL, not all).  images [Nv,3,H,W] uint8, or float32 in [0,1] converted as (c*255) truncated
+ * (images_are_float), or NULL (colours 0).  mvs_pointcloud_record_offset(i) = byte offset of record i (64-bit). */
+int64_t mvs_pointcloud_workspace_bytes(int R, int H, int W);
+int64_t mvs_pointcloud_record_offset(int64_t point_index);
+int mvs_pointcloud_count(const uint8_t* photo_mask, const uint8_t* geo_mask, const int32_t* ref_idx, int Nv, int R, int H, int W,
+                         void* workspace, int64_t* stats, int64_t* total, mvs_stream_t stream);
+int mvs_pointcloud_scatter(const uint8_t* photo_mask, const uint8_t* geo_mask, const int32_t* ref_idx, int Nv, int R, int H, int W,
+                           const float* points, const void* images, int images_are_float, const void* workspace, int64_t total,
+                           uint8_t* records, float* xyz, uint8_t* rgb, mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * the classification loss fused with the head's gradient, one stage of ce_loss_stage4

@@ -13,7 +13,7 @@ from . import synth  # noqa: F401
 __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "CascadeMVS", "homo_warping_3D_with_mask",
            "homo_warping_3D", "homo_warping", "depth_regression", "conf_regression", "init_inverse_range",
            "schedule_inverse_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
-           "VITDecoderStage4Single", "DINOMVSNet"]
+           "VITDecoderStage4Single", "DINOMVSNet", "SceneFusion", "fuse_scan"]
 
 
 def __getattr__(name):
@@ -42,6 +42,9 @@ def __getattr__(name):
     if name == "fusion":
         import importlib
         return importlib.import_module(".fusion", __name__)
+    if name in ("SceneFusion", "fuse_scan"):
+        from . import fusion
+        return getattr(fusion, name)
     if name == "install":
         from .install import install
         return install

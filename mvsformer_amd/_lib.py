@@ -18,7 +18,7 @@ import torch  # noqa: F401  (load order, see above)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = os.environ.get("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 from ctypes import c_double  # noqa: E402
 
@@ -192,6 +192,13 @@ SIGNATURES = {
     "mvs_vis_x3_fwd": (I, [P, P, P, I, I, I, P, P]),
     "mvs_deconv3d_prob1_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "mvs_prob_filter": (I, [P, I, I, L, P, P, P, P]),
+    "mvs_geo_filter_scene_workspace_bytes": (L, [I, I]),
+    "mvs_geo_filter_scene_fwd": (I, [P, P, P, I, P, P, P, I, I, I, I, F, F, F, P, P, P, P, P]),
+    "mvs_geo_filter_dynamic_scene_fwd": (I, [P, P, P, I, P, P, P, I, I, I, I, F, F, P, P, P, P, P]),
+    "mvs_pointcloud_workspace_bytes": (L, [I, I, I]),
+    "mvs_pointcloud_record_offset": (L, [L]),
+    "mvs_pointcloud_count": (I, [P, P, P, I, I, I, I, P, P, P, P]),
+    "mvs_pointcloud_scatter": (I, [P, P, P, I, I, I, I, P, P, I, P, L, P, P, P, P]),
     "mvs_init_inverse_range": (I, [P, I, I, I, I, I, P, P]),
     "mvs_schedule_inverse_range": (I, [P, P, I, F, I, I, I, I, P, P]),
     "mvs_conf_accumulate": (I, [P, I, I, I, P, I, I, F, P]),

@@ -5,11 +5,16 @@ Same function names and argument meaning as reference misc/fusion.py:69-114 (``p
 averaged depth, fused world points) in ONE pass over the reference pixels with nothing materialized in between.
 
     ref_depth [n,1,h,w]   srcs_depth [n,v,1,h,w]   ref_cam [n,2,4,4]   srcs_cam [n,v,2,4,4]   (cam[:,0]=E, cam[:,1,:3,:3]=K)
+
+``SceneFusion`` / ``fuse_scan`` are the whole of test.py:404-560 (``filter_depth`` / ``dynamic_filter_depth`` /
+``pcd_filter_worker``): every view of a scan on the device once, all reference views filtered in one launch through a job
+table, the surviving points and colours compacted on the device into the PLY vertex records.
 """
 from __future__ import annotations
 
-from typing import Dict, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -98,3 +103,164 @@ def filter_scan(pair_folder: str, scan_folder: str, prob_threshold: Sequence[flo
         views[id_ref] = (pts.cpu().numpy(), dict(photo=prob.float().mean().item(), geo=geo.float().mean().item(),
                                                  final=keep.float().mean().item()))
     return views
+
+
+class SceneFusion:
+    """A scan held on the device: ``add_view`` once per view (tensors straight from ``DINOMVSNet``'s outputs, or numpy), ``set_pairs``
+    with the view graph, ``fuse()`` -> the coloured point cloud of test.py:404-472 (``method='pcd'``) / :475-549 (``'dypcd'``).
+
+    ``depth [H,W]`` (leading singleton dims allowed), ``conf [C,H,W]`` (``[H,W]`` = one channel), ``cam [2,4,4]``, ``img [3,H,W]`` uint8 or
+    float32 in [0,1] (all views or none; without images the colours are 0).  ``prob_threshold``: one threshold per confidence channel;
+    with ``combine_conf`` only ``prob_threshold[0]`` on channel 0 (test.py:415-422).  All views share H x W.
+    """
+
+    def __init__(self, method: str = "pcd", prob_threshold: Sequence[float] = (0.5,), thres_disp: float = 1.0, thres_view: float = 2,
+                 dist_base: float = 4, rel_diff_base: float = 1300, combine_conf: bool = False, device: Optional[str] = None):
+        if method not in ("pcd", "dypcd"):
+            raise ValueError("method must be 'pcd' or 'dypcd'")
+        self.method, self.combine_conf = method, bool(combine_conf)
+        self.prob_threshold = [float(p) for p in prob_threshold]
+        if not 1 <= len(self.prob_threshold) <= 4:
+            raise ValueError("prob_threshold: 1..4 values, one per confidence channel")
+        self.thres_disp, self.thres_view, self.dist_base, self.rel_diff_base = thres_disp, thres_view, dist_base, rel_diff_base
+        self.device = torch.device(device) if device is not None else None
+        if self.device is not None and self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.views: Dict[int, Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = {}
+        self.pairs: List[Tuple[int, List[int]]] = []
+        self.hw: Optional[Tuple[int, int]] = None
+
+    def _dev(self, a, name: str, dtypes) -> torch.Tensor:
+        from ._lib import MvsHipError
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise MvsHipError("%s must be a GPU tensor or a numpy array: the MI355X HIP path is the only implementation (no CPU "
+                                  "fallback)" % name)
+            if self.device is None:
+                self.device = a.device
+        else:
+            if self.device is None:
+                self.device = torch.device("cuda:0")
+            a = torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        if a.device != self.device:
+            raise MvsHipError("%s lives on %s, the scene on %s" % (name, a.device, self.device))
+        if a.dtype not in dtypes:
+            raise MvsHipError("%s must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), a.dtype))
+        return a
+
+    def add_view(self, view_id: int, depth, conf, cam, img=None) -> None:
+        from ._lib import MvsHipError
+        depth = self._dev(depth, "depth", (torch.float32,))
+        conf = self._dev(conf, "conf", (torch.float32,))
+        cam = self._dev(cam, "cam", (torch.float32,))
+        if depth.dim() < 2 or depth.numel() != depth.shape[-1] * depth.shape[-2]:
+            raise MvsHipError("depth must be [H,W] (leading singleton dimensions allowed), got %s" % (tuple(depth.shape),))
+        h, w = depth.shape[-2:]
+        depth = depth.reshape(h, w)
+        if conf.dim() == 4 and conf.shape[0] == 1:
+            conf = conf[0]
+        if conf.dim() == 2:
+            conf = conf[None]
+        cam = cam.reshape(2, 4, 4) if cam.numel() == 32 else cam
+        if conf.dim() != 3 or tuple(conf.shape[1:]) != (h, w) or tuple(cam.shape) != (2, 4, 4):
+            raise MvsHipError("view %d: depth %s, conf %s, cam %s do not fit together" % (view_id, (h, w), tuple(conf.shape), tuple(cam.shape)))
+        if img is not None:
+            img = self._dev(img, "img", (torch.uint8, torch.float32))
+            if img.dim() == 4 and img.shape[0] == 1:
+                img = img[0]
+            if tuple(img.shape) != (3, h, w):
+                raise MvsHipError("view %d: img must be [3,%d,%d], got %s" % (view_id, h, w, tuple(img.shape)))
+        if self.hw is None:
+            self.hw = (h, w)
+        if (h, w) != self.hw:
+            raise MvsHipError("view %d is %dx%d, the scene %dx%d: all views of a scene share H x W" % (view_id, h, w, *self.hw))
+        self.views[int(view_id)] = (depth, conf, cam, img)
+
+    def set_pairs(self, pairs) -> None:
+        """``[(ref_id, [src_id, ...])]`` in output order (``data_io.read_pair_file`` / ``load_scene()['pairs']``)."""
+        self.pairs = [(int(r), [int(v) for v in srcs]) for r, srcs in pairs]
+
+    @classmethod
+    def from_folder(cls, pair_folder: str, scan_folder: str, n_src_views: int = 10, **kwargs) -> "SceneFusion":
+        from . import data_io
+        scene = data_io.load_scene(pair_folder, scan_folder, n_src_views)
+        self = cls(**kwargs)
+        for i, vid in enumerate(scene["view_ids"]):
+            self.add_view(vid, scene["depths"][i], scene["confs"][i], scene["cams"][i], None if scene["imgs"] is None else scene["imgs"][i])
+        self.set_pairs(scene["pairs"])
+        return self
+
+    def fuse(self, want: Sequence[str] = ("records", "xyz", "rgb"), with_intermediates: bool = False) -> Dict[str, object]:
+        """-> ``xyz [M,3]`` float32, ``rgb [M,3]`` uint8, ``records`` uint8 ``[M*15]`` (the PLY vertex body) as numpy arrays (those named
+        in ``want``), ``counts_per_view {ref_id: points}``, ``stats {ref_id: {photo, geo, final}}`` (fractions of the view's pixels), and
+        ``n_points``.  Points come in ``pairs`` order, row-major inside a view, as the reference concatenates them.  With
+        ``with_intermediates`` also the device tensors the compaction read: ``photo_mask [Nv,H,W]`` (views in ``view_ids`` order),
+        ``geo_mask [R,H,W]`` and ``points_dense [R,3,H,W]`` (one per pair)."""
+        from ._lib import MvsHipError
+        if not self.pairs or not self.views:
+            raise ValueError("SceneFusion.fuse: add_view() and set_pairs() first")
+        ids = list(self.views)
+        index = {v: i for i, v in enumerate(ids)}
+        for r, srcs in self.pairs:
+            for v in [r] + srcs:
+                if v not in index:
+                    raise ValueError("view %d is named in the pairs but was never added" % v)
+            if not srcs:
+                raise ValueError("reference view %d has no source views" % r)
+            if self.method == "dypcd" and not 2 <= len(srcs) <= 16:
+                raise MvsHipError("reference view %d has %d source views: the dynamic check takes 2..16" % (r, len(srcs)))
+        imgs = [v[3] for v in self.views.values()]
+        if any(i is None for i in imgs) and not all(i is None for i in imgs):
+            raise ValueError("either every view has an image or none")
+        if imgs[0] is not None and len({i.dtype for i in imgs}) != 1:
+            raise ValueError("images must be all uint8 or all float32")
+        nch = 1 if self.combine_conf else len(self.prob_threshold)
+        if any(v[1].shape[0] < nch for v in self.views.values()):
+            raise MvsHipError("%d thresholds but a view has fewer confidence channels" % nch)
+        with torch.cuda.device(self.device):
+            depths = torch.stack([v[0] for v in self.views.values()]).contiguous()
+            confs = torch.stack([v[1][:nch] for v in self.views.values()]).contiguous()
+            cams = torch.stack([v[2] for v in self.views.values()]).contiguous()
+            images = None if imgs[0] is None else torch.stack(imgs).contiguous()
+            table = ops.JobTable([(index[r], [index[v] for v in srcs]) for r, srcs in self.pairs], len(ids), self.device)
+            # ONE prob-filter launch for the scene: every view's photometric mask, and (pcd) the zeroed copy it contributes as a source
+            depth_src = depths.clone() if self.method == "pcd" else depths
+            photo = ops.prob_filter(confs, self.prob_threshold[:nch], depth_inplace=depth_src if self.method == "pcd" else None)
+            if self.method == "pcd":
+                out = ops.geo_filter_scene(table, depths, depth_src, cams, self.thres_disp, 0.01, self.thres_view, want=("mask", "points"))
+                geo = out["mask"]
+            else:
+                out = ops.geo_filter_dynamic_scene(table, depths, depth_src, cams, self.dist_base, self.rel_diff_base,
+                                                   want=("geo_mask", "points"))
+                geo = out["geo_mask"]
+            comp = ops.pointcloud_compact(table, photo.view(len(ids), *self.hw), geo, out["points"], images, want=tuple(want))
+            res: Dict[str, object] = {k: comp[k].cpu().numpy() for k in want}
+        if with_intermediates:
+            res.update(photo_mask=photo.view(len(ids), *self.hw), geo_mask=geo, points_dense=out["points"], view_ids=ids)
+        hw = float(self.hw[0] * self.hw[1])
+        st = comp["stats"]
+        res["n_points"] = comp["total"]
+        res["counts_per_view"] = {r: int(st[i, 2]) for i, (r, _) in enumerate(self.pairs)}
+        res["stats"] = {r: dict(photo=st[i, 0] / hw, geo=st[i, 1] / hw, final=st[i, 2] / hw) for i, (r, _) in enumerate(self.pairs)}
+        return res
+
+
+def fuse_scan(pair_folder: str, scan_folder: str, plyfilename: str, prob_threshold: Sequence[float], method: str = "pcd",
+              thres_disp: float = 1.0, thres_view: float = 2, dist_base: float = 4, rel_diff_base: float = 1300,
+              combine_conf: bool = False, n_src_views: int = 10, device: str = "cuda:0") -> Dict[str, object]:
+    """``pcd_filter_worker`` (test.py:552-560): the scan folder ``save_depth_outputs`` (+ ``images/``) left -> ``plyfilename``.
+    Returns ``n_points``, ``stats``, ``counts_per_view`` and ``seconds`` = {load, device, write}."""
+    import time
+    from . import data_io
+    t0 = time.perf_counter()
+    scene = SceneFusion.from_folder(pair_folder, scan_folder, n_src_views, method=method, prob_threshold=prob_threshold,
+                                    thres_disp=thres_disp, thres_view=thres_view, dist_base=dist_base, rel_diff_base=rel_diff_base,
+                                    combine_conf=combine_conf, device=device)
+    torch.cuda.synchronize(scene.device)
+    t1 = time.perf_counter()
+    out = scene.fuse(want=("records",))
+    t2 = time.perf_counter()
+    data_io.write_ply_records(plyfilename, out["records"], out["n_points"])
+    t3 = time.perf_counter()
+    return dict(n_points=out["n_points"], stats=out["stats"], counts_per_view=out["counts_per_view"],
+                seconds=dict(load=t1 - t0, device=t2 - t1, write=t3 - t2))

@@ -1041,6 +1041,122 @@ def vis_filter_dynamic(ref_depth, reproj_xyd, dist_base, rel_diff_base, want=("m
     return {k: (t if k == "ref_depth_ave" else t.view(torch.bool)) for k, t in out.items()}
 
 
+# ------------------------------------------------------------------- scene-resident fusion -> point cloud (§8 f2)
+class JobTable:
+    """The job table of the scene kernels: job r filters view ``ref[r]`` against views ``srcs[r]`` (indices into the scene's view stacks).
+    Validated on the host, uploaded once: ``ref_idx [R]``, ``src_idx [R,Vmax]`` (padded with -1), ``n_src [R]``, int32."""
+
+    def __init__(self, jobs, n_views: int, device):
+        jobs = [(int(r), [int(v) for v in srcs]) for r, srcs in jobs]
+        if not jobs:
+            raise ValueError("job table: no jobs")
+        for r, srcs in jobs:
+            if not srcs:
+                raise ValueError("job table: reference view %d has no source views" % r)
+            for v in [r] + srcs:
+                if not 0 <= v < n_views:
+                    raise ValueError("job table: view index %d outside [0, %d)" % (v, n_views))
+        self.jobs, self.n_views = jobs, int(n_views)
+        self.R, self.Vmax = len(jobs), max(len(srcs) for _, srcs in jobs)
+        self.n_src_host = [len(srcs) for _, srcs in jobs]
+        host = torch.full((self.R, self.Vmax + 2), -1, dtype=torch.int32)
+        for i, (r, srcs) in enumerate(jobs):
+            host[i, 0], host[i, 1] = r, len(srcs)
+            host[i, 2:2 + len(srcs)] = torch.tensor(srcs, dtype=torch.int32)
+        self.ref_idx = host[:, 0].contiguous().to(device)
+        self.n_src = host[:, 1].contiguous().to(device)
+        self.src_idx = host[:, 2:].contiguous().to(device)
+
+
+def _chk_scene(table: JobTable, depth_ref, depth_src, cams):
+    _chk(depth_ref, "depth_ref"), _chk(depth_src, "depth_src"), _chk(cams, "cams")
+    _chk(table.ref_idx, "ref_idx", torch.int32), _chk(table.src_idx, "src_idx", torch.int32), _chk(table.n_src, "n_src", torch.int32)
+    if depth_ref.dim() != 3 or depth_src.shape != depth_ref.shape or cams.shape != (depth_ref.shape[0], 2, 4, 4) \
+            or depth_ref.shape[0] != table.n_views:
+        raise _lib.MvsHipError("scene filter: inconsistent shapes %s %s %s for %d views" % (
+            tuple(depth_ref.shape), tuple(depth_src.shape), tuple(cams.shape), table.n_views))
+    return depth_ref.shape
+
+
+def geo_filter_scene(table: JobTable, depth_ref, depth_src, cams, img_dist_thresh: float = 1.0, depth_thresh: float = 0.01,
+                     vthresh: float = 2.0, want=("mask", "points")) -> Dict[str, torch.Tensor]:
+    """``mvs_geo_filter_fwd`` for every job of ``table`` in one launch: ``depth_ref`` / ``depth_src [Nv,H,W]``, ``cams [Nv,2,4,4]`` ->
+    ``mask [R,H,W]`` bool, ``ref_depth_ave [R,H,W]``, ``points [R,3,H,W]``."""
+    nv, h, w = _chk_scene(table, depth_ref, depth_src, cams)
+    dev, R, V = depth_ref.device, table.R, table.Vmax
+    shapes = dict(mask=(R, h, w), ref_depth_ave=(R, h, w), points=(R, 3, h, w))
+    out = {k: torch.empty(shapes[k], device=dev, dtype=torch.uint8 if k == "mask" else torch.float32) for k in want}
+    ws = torch.empty(_lib.load().mvs_geo_filter_scene_workspace_bytes(R, V), device=dev, dtype=torch.uint8)
+    algo = 4.0 * h * w * sum(1 + n for n in table.n_src_host) + h * w * R * sum({"mask": 1, "ref_depth_ave": 4, "points": 12}[k] for k in want)
+    _call("mvs_geo_filter_scene_fwd", ("geo_filter_scene", "bytes", algo), _ptr(depth_ref), _ptr(depth_src), _ptr(cams), nv,
+          _ptr(table.ref_idx), _ptr(table.src_idx), _ptr(table.n_src), R, V, h, w, float(img_dist_thresh), float(depth_thresh),
+          float(vthresh), _ptr(ws), *[_ptr(out.get(k)) for k in ("mask", "ref_depth_ave", "points")], _stream())
+    if "mask" in out:
+        out["mask"] = out["mask"].view(torch.bool)
+    return out
+
+
+def geo_filter_dynamic_scene(table: JobTable, depth_ref, depth_src, cams, dist_base: float = 4, rel_diff_base: float = 1300,
+                             want=("geo_mask", "points")) -> Dict[str, torch.Tensor]:
+    """``mvs_geo_filter_dynamic_fwd`` for every job of ``table`` in one launch; each job takes 2..16 source views."""
+    nv, h, w = _chk_scene(table, depth_ref, depth_src, cams)
+    bad = [n for n in table.n_src_host if not 2 <= n <= 16]
+    if bad:
+        raise _lib.MvsHipError("geo_filter_dynamic_scene: a job has %d source views, the dynamic check takes 2..16" % bad[0])
+    dev, R, V = depth_ref.device, table.R, table.Vmax
+    shapes = dict(geo_mask=(R, h, w), ref_depth_ave=(R, h, w), points=(R, 3, h, w))
+    out = {k: torch.empty(shapes[k], device=dev, dtype=torch.uint8 if k == "geo_mask" else torch.float32) for k in want}
+    ws = torch.empty(_lib.load().mvs_geo_filter_scene_workspace_bytes(R, V), device=dev, dtype=torch.uint8)
+    algo = 4.0 * h * w * sum(1 + n for n in table.n_src_host) + h * w * R * sum({"geo_mask": 1, "ref_depth_ave": 4, "points": 12}[k]
+                                                                                 for k in want)
+    _call("mvs_geo_filter_dynamic_scene_fwd", ("geo_filter_dynamic_scene", "bytes", algo), _ptr(depth_ref), _ptr(depth_src), _ptr(cams),
+          nv, _ptr(table.ref_idx), _ptr(table.src_idx), _ptr(table.n_src), R, V, h, w, float(dist_base), float(rel_diff_base), _ptr(ws),
+          *[_ptr(out.get(k)) for k in ("geo_mask", "ref_depth_ave", "points")], _stream())
+    if "geo_mask" in out:
+        out["geo_mask"] = out["geo_mask"].view(torch.bool)
+    return out
+
+
+def pointcloud_compact(table: JobTable, photo_mask, geo_mask, points, images=None, want=("records", "xyz", "rgb")):
+    """keep = ``photo_mask[ref[r]] & geo_mask[r]`` (bool / uint8 ``[Nv,H,W]`` / ``[R,H,W]``) -> the kept ``points [R,3,H,W]`` and the colours
+    of ``images [Nv,3,H,W]`` (uint8, or float32 in [0,1]; None: zeros), jobs in table order, row-major inside a job:
+    ``records`` uint8 ``[M*15]`` (PLY vertex body), ``xyz [M,3]`` float32, ``rgb [M,3]`` uint8, plus ``stats`` int64 ``[R,3]`` on the host
+    (photo, geo, kept pixels per job) and ``total`` = M.  One host synchronisation (reading M and the stats); M == 0 launches no scatter."""
+    photo_mask, geo_mask = [m.view(torch.uint8) if isinstance(m, torch.Tensor) and m.dtype == torch.bool else m for m in (photo_mask, geo_mask)]
+    _chk(photo_mask, "photo_mask", torch.uint8), _chk(geo_mask, "geo_mask", torch.uint8), _chk(points, "points")
+    _chk(table.ref_idx, "ref_idx", torch.int32)
+    R, nv = table.R, table.n_views
+    if geo_mask.dim() != 3 or geo_mask.shape[0] != R or photo_mask.shape != (nv,) + tuple(geo_mask.shape[1:]) \
+            or points.shape != (R, 3) + tuple(geo_mask.shape[1:]):
+        raise _lib.MvsHipError("pointcloud_compact: inconsistent shapes %s %s %s for %d jobs over %d views" % (
+            tuple(photo_mask.shape), tuple(geo_mask.shape), tuple(points.shape), R, nv))
+    h, w = geo_mask.shape[1:]
+    is_float = 0
+    if images is not None:
+        if isinstance(images, torch.Tensor) and images.dtype == torch.float32:
+            is_float = 1
+        _chk(images, "images", torch.float32 if is_float else torch.uint8)
+        if images.shape != (nv, 3, h, w):
+            raise _lib.MvsHipError("pointcloud_compact: images must be [%d,3,%d,%d], got %s" % (nv, h, w, tuple(images.shape)))
+    dev, lib = points.device, _lib.load()
+    ws = torch.empty(lib.mvs_pointcloud_workspace_bytes(R, h, w) // 8 + 1, device=dev, dtype=torch.int64)
+    meta = torch.empty(1 + 3 * R, device=dev, dtype=torch.int64)            # total, then stats [R,3]: one copy to the host
+    _call("mvs_pointcloud_count", ("pointcloud_count", "bytes", 2.0 * R * h * w), _ptr(photo_mask), _ptr(geo_mask), _ptr(table.ref_idx), nv,
+          R, h, w, _ptr(ws), meta.data_ptr() + 8, meta.data_ptr(), _stream())
+    meta_h = meta.cpu()
+    total = int(meta_h[0])
+    out = {"total": total, "stats": meta_h[1:].view(R, 3).numpy()}
+    shapes = dict(records=((lib.mvs_pointcloud_record_offset(total),), torch.uint8), xyz=((total, 3), torch.float32),
+                  rgb=((total, 3), torch.uint8))
+    for k in want:
+        out[k] = torch.empty(shapes[k][0], device=dev, dtype=shapes[k][1])
+    if total > 0 and want:
+        _call("mvs_pointcloud_scatter", ("pointcloud_scatter", "bytes", 2.0 * R * h * w + total * (15.0 + 15.0 * len(want))),
+              _ptr(photo_mask), _ptr(geo_mask), _ptr(table.ref_idx), nv, R, h, w, _ptr(points), _ptr(images), is_float, _ptr(ws), total,
+              *[_ptr(out.get(k)) for k in ("records", "xyz", "rgb")], _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------- fused CE loss (§8 f3)
 def ce_loss(logits, depth_values, depth_gt, mask, inverse_depth: bool, weight: float = 1.0, want_grad: bool = True,
             want_index: bool = False):
