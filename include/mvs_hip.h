@@ -44,7 +44,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 44
+#define MVS_ABI_VERSION 45
 
 typedef void* mvs_stream_t;
 
@@ -772,6 +772,27 @@ int mvs_attention_softmax_bwd(const float* P, const float* dP, const float* dA, 
                               mvs_stream_t stream);
 int mvs_bicubic_resize_bwd(const float* dout, float* din, float* tmp, int planes, int H, int W, int Ho, int Wo, float rscale_h, float rscale_w,
                            mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Flash attention for the training mode above (csrc/vit_flash_train.hip): softmax(scale * Q K^T) V and its backward per (image, head) without
+ * any N x N tensor.  Split-form arithmetic like mvs_attention_x3 (fp32-equivalent); head_dim = 64; qkv = [B][N][3C] packed rows
+ * (q | k | v, head h at columns h*64, C = heads*64); qkv, out, dout, dqkv 16-byte aligned.  Every output element is summed by one lane in a
+ * fixed order - no atomics, two runs are bitwise equal.
+ *   mvs_attention_train_fwd_flash: out [B][N][C] = P V and lse [B][heads][N] = log sum_k exp(scale * q . k_k) (natural logarithm; online
+ *       softmax, keys >= N masked).  cls_row (may be NULL): [B][heads][N] = P_0 = exp(scale * q_0 . k - lse_0), the CLS query's attention row
+ *       (mvsformer_model.py:223,253 read vit_att[:, :, 0, 1:]).
+ *   mvs_attention_train_bwd_flash: dqkv [B][N][3C] from dout [B][N][C] and the forward's out / lse, in two passes that recompute
+ *       P = exp(scale * S - lse) and dP = dO V^T tile by tile: a pass over key tiles accumulates dV += P^T dO and dK += dS^T Q, a pass over
+ *       query tiles dQ += dS K, with dS = scale * P * (dP - D), D[b][h][i] = sum_c dO * O (= sum_k P_k dP_k): the dS of
+ *       mvs_attention_softmax_bwd.  dA_cls (may be NULL): [B][heads][N], the gradient of cls_row: row 0 uses g = dP + dA, that is
+ *       dP_0k + dA_0k in place of dP_0k and D_0 + sum_k P_0k dA_0k in place of D_0 (da_rows = 1 of mvs_attention_softmax_bwd).
+ *       workspace: mvs_attention_train_flash_workspace_bytes(B, N, heads) bytes (D).
+ * ------------------------------------------------------------------------------------------------------- */
+int mvs_attention_train_fwd_flash(const float* qkv, float* out, float* lse, float* cls_row, int B, int N, int heads, int head_dim, float scale,
+                                  mvs_stream_t stream);
+int64_t mvs_attention_train_flash_workspace_bytes(int B, int N, int heads);
+int mvs_attention_train_bwd_flash(const float* qkv, const float* out, const float* lse, const float* dout, const float* dA_cls, float* dqkv,
+                                  void* workspace, int B, int N, int heads, int head_dim, float scale, mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The transformer blocks on PRE-SPLIT ("packed") operands (csrc/vit_packed.hip; models/vision_transformer.py:123-154,194-214): every matrix

@@ -18,7 +18,7 @@ import torch  # noqa: F401  (load order, see above)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = os.environ.get("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 from ctypes import c_double  # noqa: E402
 
@@ -173,6 +173,9 @@ SIGNATURES = {
     "mvs_gelu_bwd": (I, [P, P, P, L, P]),
     "mvs_attention_softmax_bwd": (I, [P, P, P, I, P, L, I, F, P]),
     "mvs_bicubic_resize_bwd": (I, [P, P, P, I, I, I, I, I, F, F, P]),
+    "mvs_attention_train_fwd_flash": (I, [P, P, P, P, I, I, I, I, F, P]),
+    "mvs_attention_train_flash_workspace_bytes": (L, [I, I, I]),
+    "mvs_attention_train_bwd_flash": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P]),
     "mvs_x3p_bytes": (L, [L, I]),
     "mvs_x3p_pack": (I, [P, P, L, I, I, L, P]),
     "mvs_x3p_unpack": (I, [P, P, L, I, I, L, P]),

@@ -33,6 +33,7 @@ _RULES = [
     (r"^(fpn8_x3|fpn_level_x3|mvs_fpn_level_x3)", ["fpn_x3.hip", "conv_common.h", "common.h", "split3.h"]),
     (r"^(layernorm_stats|layernorm_bwd|colsum|gelu_|attention_softmax_bwd|bicubic_bwd|mvs_layernorm_stats|mvs_layernorm_bwd|mvs_colsum|mvs_gelu|"
      r"mvs_attention_softmax_bwd|mvs_bicubic_resize_bwd|vit_train)", ["vit_train.hip", "common.h"]),
+    (r"^(flash_train|mvs_attention_train)", ["vit_flash_train.hip", "common.h", "split3.h"]),
     (r"^(x3p_|gemm_x3p|attention_x3p|layernorm_x3p|cls_attention)", ["vit_packed.hip", "common.h", "split3.h"]),
     (r"^(x3_gemm|x3_attention|gemm_x3|attention_x3|layernorm|softmax_rows|bicubic)", ["vit.hip", "common.h", "geometry.h", "split3.h"]),
 ]

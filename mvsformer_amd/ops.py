@@ -1987,6 +1987,43 @@ def attention_softmax_bwd(p: torch.Tensor, dp: torch.Tensor, scale: float, da: O
     return ds
 
 
+def attention_train_fwd_flash(qkv: torch.Tensor, heads: int, scale: float, want_cls: bool = False):
+    """Flash attention forward for training (csrc/vit_flash_train.hip) on packed ``qkv [B,N,3C]`` -> ``(out [B,N,C], lse [B,heads,N])`` and,
+    with ``want_cls``, the CLS query's attention row ``[B,heads,N]``.  Head dimension 64."""
+    _chk(qkv, "qkv")
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    if C * 3 != C3 or heads < 1 or C % heads:
+        raise _lib.MvsHipError("attention_train_fwd_flash: qkv %s for %d heads" % (tuple(qkv.shape), heads))
+    out = torch.empty(B, N, C, device=qkv.device, dtype=torch.float32)
+    lse = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32)
+    cls_row = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32) if want_cls else None
+    _call("mvs_attention_train_fwd_flash", "flash_train_fwd", _ptr(qkv), _ptr(out), _ptr(lse), _ptr(cls_row), B, N, heads, C // heads, float(scale),
+          _stream())
+    return (out, lse, cls_row) if want_cls else (out, lse)
+
+
+def attention_train_bwd_flash(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, heads: int, scale: float,
+                              da_cls: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of :func:`attention_train_fwd_flash` -> dqkv ``[B,N,3C]``; ``da_cls [B,heads,N]`` = the gradient of the CLS row.  Two
+    passes that recompute P from ``lse``; fixed summation order (bitwise reproducible)."""
+    _chk(qkv, "qkv"), _chk(out, "out"), _chk(lse, "lse"), _chk(dout, "dout"), _opt(da_cls, "da_cls")
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    if C * 3 != C3 or heads < 1 or C % heads or tuple(out.shape) != (B, N, C) or tuple(dout.shape) != (B, N, C) or lse.numel() != B * heads * N or \
+            (da_cls is not None and da_cls.numel() != B * heads * N):
+        raise _lib.MvsHipError("attention_train_bwd_flash: qkv %s, out %s, lse %s, dout %s for %d heads"
+                               % (tuple(qkv.shape), tuple(out.shape), tuple(lse.shape), tuple(dout.shape), heads))
+    n = getattr(_lib.load(), "mvs_attention_train_flash_workspace_bytes")(B, N, heads)
+    if n < 0:
+        raise _lib.MvsHipError("attention_train_bwd_flash: bad shape %s" % (tuple(qkv.shape),))
+    ws = torch.empty(int(n) // 4, device=qkv.device, dtype=torch.float32)
+    dqkv = torch.empty(B, N, C3, device=qkv.device, dtype=torch.float32)
+    _call("mvs_attention_train_bwd_flash", "flash_train_bwd", _ptr(qkv), _ptr(out), _ptr(lse), _ptr(dout), _ptr(da_cls), _ptr(dqkv), _ptr(ws), B, N,
+          heads, C // heads, float(scale), _stream())
+    return dqkv
+
+
 def bicubic_resize_bwd(dout: torch.Tensor, H: int, W: int, rscale_h: float, rscale_w: float) -> torch.Tensor:
     """The adjoint of :func:`bicubic_resize` (same ``rscale`` arguments): ``dout [..., Ho, Wo]`` -> ``[..., H, W]``."""
     _chk(dout, "dout")

@@ -301,17 +301,38 @@ def attention_train_bwd(qkv: torch.Tensor, p: torch.Tensor, dout: torch.Tensor, 
     return dqkv
 
 
+def attention_flash_train_fwd(qkv: torch.Tensor, heads: int, want_cls: bool = False):
+    """Attention of packed ``qkv [B,N,3C]`` in flash form (``mvs_attention_train_fwd_flash``, head dimension 64) -> (P V ``[B,N,C]``,
+    ``lse [B,heads,N]`` = log sum_k exp(q . k_k / sqrt(hd))) and, with ``want_cls``, the CLS query's row of P ``[B,heads,N]``.  No N x N tensor."""
+    return ops.attention_train_fwd_flash(qkv, heads, (qkv.shape[-1] // 3 // heads) ** -0.5, want_cls)
+
+
+def attention_flash_train_bwd(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, heads: int,
+                              da_cls: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of :func:`attention_flash_train_fwd` -> dqkv ``[B,N,3C]`` (``mvs_attention_train_bwd_flash``): P and dP are recomputed
+    tile by tile from ``lse``, dS as in ``mvs_attention_softmax_bwd``; ``da_cls [B,heads,N]`` = the gradient of the returned CLS row.
+    Deterministic: two runs are bitwise equal."""
+    return ops.attention_train_bwd_flash(qkv, out, lse, dout, heads, (qkv.shape[-1] // 3 // heads) ** -0.5, da_cls)
+
+
+def _train_flash_on() -> bool:
+    return os.environ.get("MVS_VIT_TRAIN_FLASH", "1") != "0"
+
+
 class _ViTTrainFn(torch.autograd.Function):
     """``VisionTransformer.forward_with_last_att`` / ``forward_with_cls_att`` in training mode and its backward
     (models/vision_transformer.py:104-154,194-214,394-451).
 
-    Forward: the eval path's materialized form (csrc/vit.hip ``mvs_gemm_x3`` for every product, ``mvs_softmax_rows``), with LayerNorm writing
-    its row statistics (``mvs_layernorm_stats``) and fc1's pre-activation kept for GELU's backward.  Saved per block: the block input, both
-    LayerNorm outputs and statistics, qkv, the attention matrix P, the attention output, the mid-block tokens, fc1 before and after GELU.
+    Forward: ``mvs_gemm_x3`` for every linear layer, LayerNorm writing its row statistics (``mvs_layernorm_stats``), fc1's pre-activation kept
+    for GELU's backward.  Attention with heads of 64 is the flash pair of csrc/vit_flash_train.hip (:func:`attention_flash_train_fwd` /
+    ``_bwd``): a block keeps the row log-sum-exp ``[B,heads,N]`` and no N x N tensor; with ``cls_only`` the returned CLS row comes from the last
+    block's forward.  The materialized form (:func:`attention_train_fwd`, P saved) remains for the last block when the WHOLE matrix is
+    returned, for other head sizes, and for every block under ``MVS_VIT_TRAIN_FLASH=0``.  Saved per block: the block input, both
+    LayerNorm outputs and statistics, qkv, lse (or P), the attention output, the mid-block tokens, fc1 before and after GELU.
     Backward, per block in reverse: linear data gradients = ``mvs_gemm_x3`` with ``b_kn = 1``, weight gradients dW = dY^T X with ``a_mode = 3``,
     bias / LayerNorm parameter gradients = ``mvs_colsum`` (fixed-order column sums), the attention backward dP = dO V^T, dS =
     ``mvs_attention_softmax_bwd`` (which folds in the gradient of the returned attention: all rows, or the CLS row only), dQ = dS K,
-    dK = dS^T Q, dV = P^T dO written into one dqkv.  The position table's gradient goes through ``mvs_bicubic_resize_bwd``.  No atomics: two
+    dK = dS^T Q, dV = P^T dO written into one dqkv (flash blocks: the same quantities recomputed tile by tile).  The position table's gradient goes through ``mvs_bicubic_resize_bwd``.  No atomics: two
     runs give bitwise-equal gradients.
 
     ``cls_only``: return the last block's CLS query row ``[B, heads, N]`` instead of its whole attention matrix."""
@@ -344,13 +365,24 @@ class _ViTTrainFn(torch.autograd.Function):
             grid = ops.bicubic_resize(grid, hp, wp, rh, rw)
             pos = torch.cat([pe[:, :1], grid.permute(1, 2, 0).reshape(1, n, C)], dim=1)
         t = (tok + pos).contiguous()
-        saved = []
+        saved, is_flash, att_out = [], [], None
+        flash = hd == 64 and _train_flash_on()                # (hd != 64: the materialized form, as in eval)
         for (n1w, n1b, qw, qb, prw, prb, n2w, n2b, f1w, f1b, f2w, f2b) in blocks:
             hid = f1w.shape[0]
             y1, m1, r1 = ops.layernorm_stats(t, n1w, n1b, eps)
             qkv = torch.empty(B, N, 3 * C, device=dev, dtype=torch.float32)
             ops.gemm_x3(y1, qw, qkv, M, 3 * C, C, C, C, 3 * C, shift=qb)
-            p_att, att = attention_train_fwd(qkv, NH)
+            last = len(saved) == len(blocks) - 1
+            if flash and not (last and not cls_only):
+                # flash form: the block keeps lse [B,heads,N] instead of P [B,heads,N,N]; the last block also gives the CLS row
+                if last:
+                    att, p_att, att_out = attention_flash_train_fwd(qkv, NH, want_cls=True)
+                else:
+                    att, p_att = attention_flash_train_fwd(qkv, NH)
+                is_flash.append(True)
+            else:
+                p_att, att = attention_train_fwd(qkv, NH)
+                is_flash.append(False)
             t2 = torch.empty_like(t)
             ops.gemm_x3(att, prw, t2, M, C, C, C, C, C, shift=prb, res=t)
             y2, m2, r2 = ops.layernorm_stats(t2, n2w, n2b, eps)
@@ -362,9 +394,11 @@ class _ViTTrainFn(torch.autograd.Function):
             saved.append((t, y1, m1, r1, qkv, p_att, att, t2, y2, m2, r2, hpre, hact))
             t = tn
         out, mf, rf = ops.layernorm_stats(t, nw, nb, eps)
-        last = saved[-1][5]
-        att_out = last[:, :, 0].contiguous() if cls_only else last.clone()
+        if att_out is None:
+            last = saved[-1][5]
+            att_out = last[:, :, 0].contiguous() if cls_only else last.clone()
         ctx.cfg = ( B, N, C, NH, hd, n, hp, wp, K0, scale, rs, [tuple(p.shape) for p in params])
+        ctx.is_flash = is_flash
         ctx.state = (f, patches, saved, t, mf, rf)
         return out, att_out
 
@@ -406,7 +440,11 @@ class _ViTTrainFn(torch.autograd.Function):
             dwp = torch.empty(C, C, device=dev, dtype=torch.float32)
             ops.gemm_x3(dt2, att, dwp, C, C, M, C, C, C, b_kn=True, a_mode=3)
             dbp = ops.colsum(dt2)
-            dqkv = attention_train_bwd(qkv, p_att, datt_o, NH, da if i == len(saved) - 1 else None)
+            da_i = da if i == len(saved) - 1 else None
+            if ctx.is_flash[i]:                              # p_att holds lse
+                dqkv = attention_flash_train_bwd(qkv, att, p_att, datt_o, NH, da_i)
+            else:
+                dqkv = attention_train_bwd(qkv, p_att, datt_o, NH, da_i)
             # attn.qkv
             dy1 = torch.empty(B, N, C, device=dev, dtype=torch.float32)
             ops.gemm_x3(dqkv, qw, dy1, M, C, 3 * C, 3 * C, C, C, b_kn=True)

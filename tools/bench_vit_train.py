@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Cost of fine-tuning the DINO ViT ("fix": false) at 640 x 512, 5 views (the ViT sees 320 x 256: 321 tokens per view): the ViT's training
 forward and forward + backward (mvsformer_amd/vit.py ``_ViTTrainFn``), and one DINOMVSNet training step (forward, ce_loss_stage4, backward)
-with fix=False against fix=True.  Median of --steps timed repetitions after --warmup; prints one JSON line."""
+with fix=False against fix=True, and ``vit_train_peak_mb``: the peak device memory of one ViT forward + backward.  ``MVS_VIT_TRAIN_FLASH=0``
+selects the materialized attention, so one run per setting is the A/B.  Median of --steps timed repetitions after --warmup; prints one JSON line."""
 import argparse
 import json
 import os
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--views", type=int, default=5)
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--vit-only", action="store_true", help="skip the two DINOMVSNet steps")
     args = ap.parse_args()
     import mvsformer_amd as m
     from mvsformer_amd import losses, synth
@@ -52,10 +54,23 @@ def main():
         tok, att = vit.forward_with_cls_att(x)
         torch.autograd.grad(tok.sum() + att.sum(), params)
 
-    res = {"views": V, "height": H, "width": W, "tokens_per_view": (H // 32) * (W // 32) + 1}
+    # MVS_VIT_TRAIN_FLASH=0: the materialized attention (P saved); unset / 1: the flash pair (mvsformer_amd/vit.py reads it per call)
+    res = {"views": V, "height": H, "width": W, "tokens_per_view": (H // 32) * (W // 32) + 1,
+           "vit_train_flash": os.environ.get("MVS_VIT_TRAIN_FLASH", "1") != "0"}
     res["vit_train_fwd_ms"] = _time(vit_fwd, args.steps, args.warmup)
     res["vit_train_fwd_bwd_ms"] = _time(vit_fwd_bwd, args.steps, args.warmup)
+    # peak of one forward + backward over the level before it (the saved activations + the backward's transients)
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    vit_fwd_bwd()
+    torch.cuda.synchronize()
+    res["vit_train_peak_mb"] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
     res["vit_bwd_over_fwd"] = (res["vit_train_fwd_bwd_ms"] - res["vit_train_fwd_ms"]) / res["vit_train_fwd_ms"]
+    if args.vit_only:
+        print(json.dumps(res))
+        return
     _, proj, dv, scene = synth.make_inputs(V, H, W, seed=1)
     proj = {k: v.to(dev) for k, v in proj.items()}
     dv = dv.to(dev)
