@@ -44,7 +44,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 45
+#define MVS_ABI_VERSION 46
 
 typedef void* mvs_stream_t;
 
@@ -163,6 +163,20 @@ int mvs_cv_corr_rows_fwd(const float* feat, const float* rt, const float* depth,
                          int rows, float* entropy, void* store, int flags, mvs_stream_t stream);
 int mvs_cv_merge_rows_fwd(const void* store, const float* depth, const float* weight, int B, int V, int C, int G, int D, int H, int W,
                           int y0, int rows, int r_lo, int nrows, float* volume, float* sim_depth, mvs_stream_t stream);
+
+/* View-indexed forms of the gathering sweeps, for a scene whose feature maps are kept once per IMAGE: bank [N,H,W,C] channel-last holds N
+ * views, and view v of sample b is bank block view_idx[b*V + v] (column 0 = the reference view; a view may be named more than once).
+ * view_idx is a HOST array of B*V ints.  Every entry is checked against [0, N) before anything is launched - a bad table returns
+ * MVS_EINVAL and never becomes an out-of-range read - and the table then travels by value in the kernel arguments (B*V <= 64, an error
+ * otherwise), so the calls are capture-safe.  Everything else - arguments, outputs, arithmetic - is that of mvs_cv_entropy_fwd /
+ * mvs_cv_aggregate_fwd / mvs_cv_corr_rows_fwd: the results equal the dense calls on the gathered views bit for bit.  mvs_cv_merge*_fwd never
+ * read features and serve both forms; y0 = 0, rows = H is the whole-image stored-correlation sweep.  The LDS-tiled sweeps have no such form. */
+int mvs_cv_entropy_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, int B, int V, int C, int G,
+                             int D, int H, int W, float* entropy, int flags, mvs_stream_t stream);
+int mvs_cv_aggregate_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, const float* weight, int B,
+                               int V, int C, int G, int D, int H, int W, float* volume, float* sim_depth, int flags, mvs_stream_t stream);
+int mvs_cv_corr_rows_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, int B, int V, int C, int G,
+                               int D, int H, int W, int y0, int rows, float* entropy, void* store, int flags, mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * LDS-tiled form of the same two sweeps (cost_volume_tiled.hip) - the default eval path of StageNet.  Same math as
@@ -472,6 +486,10 @@ int mvs_schedule_inverse_range(const float* prev_depth, const float* prev_hyp, i
 /* Nearest-neighbour upsample + accumulate of the per-stage confidences (mvsformer_model.py:297-301):
  *   acc [B,Hf,Wf] += nearest(conf [B,H,W]) * weight */
 int mvs_conf_accumulate(const float* conf, int B, int H, int W, float* acc, int Hf, int Wf, float weight, mvs_stream_t stream);
+/* A view's confidence record (test.py:289-292) in one launch: out [4,H,W], plane k = the stage-(k+1) confidence c_{k+1} [H >> (3-k), W >> (3-k)]
+ * nearest-upsampled by the integer factor 8, 4, 2, 1 (source pixel = dst / factor).  H, W multiples of 8; out may be a slice of a
+ * scene-wide [Nv,4,H,W] tensor. */
+int mvs_conf_stack(const float* c1, const float* c2, const float* c3, const float* c4, int H, int W, float* out, mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Row before the path: FPNDecoder.forward, models/module.py:242-270, eval-mode BatchNorm.  Inputs and the

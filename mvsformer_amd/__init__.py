@@ -13,7 +13,7 @@ from . import synth  # noqa: F401
 __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "CascadeMVS", "homo_warping_3D_with_mask",
            "homo_warping_3D", "homo_warping", "depth_regression", "conf_regression", "init_inverse_range",
            "schedule_inverse_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
-           "VITDecoderStage4Single", "DINOMVSNet", "SceneFusion", "fuse_scan"]
+           "VITDecoderStage4Single", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference"]
 
 
 def __getattr__(name):
@@ -45,6 +45,12 @@ def __getattr__(name):
     if name in ("SceneFusion", "fuse_scan"):
         from . import fusion
         return getattr(fusion, name)
+    if name == "scene":
+        import importlib
+        return importlib.import_module(".scene", __name__)
+    if name == "SceneInference":
+        from . import scene
+        return scene.SceneInference
     if name == "install":
         from .install import install
         return install

@@ -18,7 +18,7 @@ import torch  # noqa: F401  (load order, see above)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = os.environ.get("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 from ctypes import c_double  # noqa: E402
 
@@ -62,6 +62,9 @@ SIGNATURES = {
     "mvs_cv_merge_fwd": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P]),
     "mvs_cv_corr_rows_fwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P, P, I, P]),
     "mvs_cv_merge_rows_fwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
+    "mvs_cv_entropy_fwd_views": (I, [P, P, I, P, P, I, I, I, I, I, I, I, P, I, P]),
+    "mvs_cv_aggregate_fwd_views": (I, [P, P, I, P, P, P, I, I, I, I, I, I, I, P, P, I, P]),
+    "mvs_cv_corr_rows_fwd_views": (I, [P, P, I, P, P, I, I, I, I, I, I, I, I, I, P, P, I, P]),
     "mvs_cv_tiled_workspace_bytes": (L, [I, I, I, I, I, I]),
     "mvs_conv3d_x3_supported": (I, [I, I, I, I]),
     "mvs_conv3d_x3_packed_bytes": (L, [I, I, I, I]),
@@ -205,6 +208,7 @@ SIGNATURES = {
     "mvs_init_inverse_range": (I, [P, I, I, I, I, I, P, P]),
     "mvs_schedule_inverse_range": (I, [P, P, I, F, I, I, I, I, P, P]),
     "mvs_conf_accumulate": (I, [P, I, I, I, P, I, I, F, P]),
+    "mvs_conf_stack": (I, [P, P, P, P, I, I, P, P]),
     "mvs_conv2d_packed_floats": (L, [I, I, I]),
     "mvs_conv2d_pack_weights": (I, [P, I, I, I, P, P]),
     "mvs_conv2d_bn_lrelu": (I, [P, P, P, P, I, I, I, I, I, I, I, F, P, P]),

@@ -86,6 +86,36 @@ class CascadeMVS(nn.Module):
         outputs["photometric_confidence"] = prob_maps
         return outputs
 
+    def forward_bank(self, banks, view_idx, proj_matrices, depth_values, tmp=2.0):
+        """Eval cascade over per-stage feature BANKS: ``banks['stageK'] [N,H/s,W/s,C_s]`` channel-last hold a scene's views once each and
+        ``view_idx [B,V]`` (host integers, column 0 = the reference view) names the views of each sample; ``proj_matrices`` /
+        ``depth_values`` / ``tmp`` and the output dict are those of :meth:`CascadeMVS.forward`.  Inference only."""
+        from ._lib import MvsHipError
+        if self.training:
+            raise MvsHipError("CascadeMVS.forward_bank is an inference path: call .eval() first (training goes through forward)")
+        n = len(self.ndepths)
+        with torch.no_grad():
+            last = banks["stage%d" % n]
+            rows = view_idx.tolist() if hasattr(view_idx, "tolist") else [list(r) for r in view_idx]
+            B, Hf, Wf = len(rows), last.shape[1], last.shape[2]
+            prob_maps = torch.zeros(B, Hf, Wf, dtype=torch.float32, device=last.device)
+            outputs: Dict[str, object] = {}
+            stage_out = None
+            for i in range(n):
+                bank = banks["stage%d" % (i + 1)]
+                H, W = bank.shape[1:3]
+                if i == 0:
+                    hyp = init_inverse_range(depth_values, self.ndepths[0], bank.device, torch.float32, H, W)
+                else:
+                    hyp = schedule_inverse_range(stage_out["depth"], stage_out["depth_values"], self.ndepths[i], self.depth_interals_ratio[i], H, W)
+                stage_out = self.fusions[i].forward_bank(bank, rows, proj_matrices["stage%d" % (i + 1)], hyp, tmp=tmp)
+                ops.conf_accumulate(stage_out["photometric_confidence"].contiguous(), prob_maps, 1.0 / n)
+                outputs["stage%d" % (i + 1)] = stage_out
+                outputs.update(stage_out)
+            outputs["refined_depth"] = stage_out["depth"]
+            outputs["photometric_confidence"] = prob_maps
+            return outputs
+
 
 def randomize_bn_(module: nn.Module, seed: int = 1) -> None:
     """Give every BatchNorm non-trivial running statistics / affine parameters (default init makes eval-mode BN the

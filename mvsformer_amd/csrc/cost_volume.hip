@@ -87,6 +87,16 @@ __device__ __forceinline__ BlockId xcd_block(int gx, int gy, int total) {
     return b;
 }
 
+// Where a sweep finds view v of sample b.  Dense: feat is [B,V,H,W,C] and the view is block b*V + v.  Bank: feat is a bank [N,H,W,C] shared by
+// many samples and a table view_idx[B][V] (column 0 = the reference view) names the block; the table travels BY VALUE in the kernel
+// arguments (wavefront-uniform scalar loads, nothing to keep alive under graph capture) after the host entry has checked every value
+// against [0, N).  The sweep kernels take the table as a trailing parameter PACK: the dense instantiations (empty pack) have the argument
+// list and the body they always had and compile to the same code; kernel<..., ViewTable> is the bank form.
+constexpr int MAX_VIEW_SLOTS = 64;                       // B*V entries a by-value table holds
+struct ViewTable { int idx[MAX_VIEW_SLOTS]; };
+__device__ __forceinline__ int view_block(int slot) { return slot; }
+__device__ __forceinline__ int view_block(int slot, const ViewTable& t) { return t.idx[slot]; }
+
 // ---------------------------------------------------------------------------------------------------------
 // geometry pass: lane l = (p = l % PPW, dd = l / PPW) evaluates sample (pixel x0+p, depth c0+dd) and leaves
 // {tap pixel indices, tap weights} in the wavefront's LDS slab at slot l = dd*PPW + p.
@@ -159,10 +169,11 @@ constexpr bool pipelined(int LPP) { return LPP <= 4; }
 // ---------------------------------------------------------------------------------------------------------
 // sweep A
 // ---------------------------------------------------------------------------------------------------------
-template <int LPP, bool FAST>
-__global__ __launch_bounds__(64 * NW) void cv_entropy_kernel(const float* __restrict__ feat /*[B,V,H,W,C]*/,
+template <int LPP, bool FAST, class... VT>
+__global__ __launch_bounds__(64 * NW) void cv_entropy_kernel(const float* __restrict__ feat /*[B,V,H,W,C] | bank [N,H,W,C]*/,
                                                              const float* __restrict__ rt_all, const float* __restrict__ depth,
-                                                             int V, int D, int H, int W, float* __restrict__ entropy, int gx, int total) {
+                                                             int V, int D, int H, int W, float* __restrict__ entropy, int gx, int total,
+                                                             const VT... views) {
     constexpr int C = 4 * LPP, CPG = C / G, PPW = 64 / LPP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -181,8 +192,8 @@ __global__ __launch_bounds__(64 * NW) void cv_entropy_kernel(const float* __rest
     const unsigned pix_bytes = C * 4u;
     const int pg = lane / LPP, cq = lane % LPP;
     const int xg = min(x0 + pg, W - 1);
-    const f32x4 r = *reinterpret_cast<const f32x4*>(feat + ((size_t)(b * V) * HW + (size_t)y * W + xg) * C + cq * 4);
-    const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)(b * V + sv + 1) * HW * C, (unsigned)(HW * pix_bytes));
+    const f32x4 r = *reinterpret_cast<const f32x4*>(feat + ((size_t)view_block(b * V, views...) * HW + (size_t)y * W + xg) * C + cq * 4);
+    const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)view_block(b * V + sv + 1, views...) * HW * C, (unsigned)(HW * pix_bytes));
     const float* rt = rt_all + (size_t)(b * (V - 1) + sv) * 12;
     const float* depth_row = depth + (size_t)b * D * HW + (size_t)y * W;
     const float half_w = (float)((W - 1) / 2.0), half_h = (float)((H - 1) / 2.0);
@@ -267,11 +278,14 @@ __global__ __launch_bounds__(64 * NW) void cv_entropy_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------
 // sweep B
 // ---------------------------------------------------------------------------------------------------------
-template <int LPP, bool SIM, bool FAST>
+template <int LPP, bool SIM, bool FAST, class... VT>
 __global__ __launch_bounds__(64 * NW) void cv_aggregate_kernel(const float* __restrict__ feat, const float* __restrict__ rt_all,
                                                                const float* __restrict__ depth, const float* __restrict__ weight,
                                                                int V, int D, int H, int W, float* __restrict__ volume,
-                                                               float* __restrict__ sim_depth, int gx, int total, __bf16* __restrict__ vol16) {
+                                                               float* __restrict__ sim_depth, int gx, int total, const VT... views,
+                                                               __bf16* __restrict__ vol16) {
+    // (the pack sits BEFORE vol16: profilers demangle kernel names with the C++ runtime's demangler, which gives up on a __bf16 parameter
+    // followed by a pack expansion - and the per-kernel tables key on the demangled names)
     // vol16 (optional): the same volume ALSO as bf16 channel-last [B,D,H,W,G] - what the bf16 regularizer of the training path reads (the
     // separate fp32 NCDHW -> bf16 NDHWC pass then never runs)
     constexpr int C = 4 * LPP, CPG = C / G, PPW = 64 / LPP;
@@ -292,7 +306,7 @@ __global__ __launch_bounds__(64 * NW) void cv_aggregate_kernel(const float* __re
     const bool active = x0 + pg < W;
     const int xg = min(x0 + pg, W - 1);
     const size_t pix = (size_t)y * W + xg;
-    const f32x4 r = *reinterpret_cast<const f32x4*>(feat + ((size_t)(b * V) * HW + pix) * C + cq * 4);
+    const f32x4 r = *reinterpret_cast<const f32x4*>(feat + ((size_t)view_block(b * V, views...) * HW + pix) * C + cq * 4);
     const float* depth_row = depth + (size_t)b * D * HW + (size_t)y * W;
     const float half_w = (float)((W - 1) / 2.0), half_h = (float)((H - 1) / 2.0);
 
@@ -338,7 +352,7 @@ __global__ __launch_bounds__(64 * NW) void cv_aggregate_kernel(const float* __re
                     for (int k = 0; k < NG; ++k) acc[dd][k] = 0.0f;
                 }
             }
-            const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)(b * V + sv + 1) * HW * C, (unsigned)(HW * pix_bytes));
+            const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)view_block(b * V + sv + 1, views...) * HW * C, (unsigned)(HW * pix_bytes));
             const float wv = wp[(size_t)sv * HW];
             __builtin_amdgcn_wave_barrier();
             f32x4 w[LPP], t[LPP][4];
@@ -413,7 +427,7 @@ __global__ __launch_bounds__(64 * NW) void cv_aggregate_kernel(const float* __re
         }
         for (int sv = 0; sv < V - 1; ++sv) {
             const float* rt = rt_all + (size_t)(b * (V - 1) + sv) * 12;
-            const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)(b * V + sv + 1) * HW * C, (unsigned)(HW * pix_bytes));
+            const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)view_block(b * V + sv + 1, views...) * HW * C, (unsigned)(HW * pix_bytes));
             const float wv = wp[(size_t)sv * HW];
             __builtin_amdgcn_wave_barrier();
             geometry_pass<PPW, FAST>(rt, depth_row, HW, c0, D, x0, y, H, W, half_w, half_h, lane, taps_o, taps_w);
@@ -514,10 +528,11 @@ struct CorrCfg {
     static constexpr size_t lds_bytes(int D) { return (size_t)NW * (64 * 32 + (PPW * D + RED_FLOATS + STAGE_FLOATS + SSTAGE_FLOATS) * sizeof(float)); }
 };
 
-template <int LPP, bool FAST>
-__global__ __launch_bounds__(64 * NW) void cv_corr_kernel(const float* __restrict__ feat /*[B,V,H,W,C]*/, const float* __restrict__ rt_all,
+template <int LPP, bool FAST, class... VT>
+__global__ __launch_bounds__(64 * NW) void cv_corr_kernel(const float* __restrict__ feat /*[B,V,H,W,C] | bank [N,H,W,C]*/, const float* __restrict__ rt_all,
                                                           const float* __restrict__ depth, int V, int D, int H, int W, float* __restrict__ entropy,
-                                                          float* __restrict__ corr, float* __restrict__ simv, int gx, int total, int y0, int Hs) {
+                                                          float* __restrict__ corr, float* __restrict__ simv, int gx, int total, int y0, int Hs,
+                                                          const VT... views) {
     // (y0, Hs): the band of reference rows this launch covers - image rows y0 .. y0 + Hs - 1; entropy and store are band-local ([..][Hs][..]),
     // features / hypotheses are the whole image.  y0 = 0, Hs = H is the whole image.
     using Cfg = CorrCfg<LPP>;
@@ -545,8 +560,8 @@ __global__ __launch_bounds__(64 * NW) void cv_corr_kernel(const float* __restric
     const unsigned pix_bytes = C * 4u;
     const int pg = lane / LPP, cq = lane % LPP;
     const int xg = min(x0 + pg, W - 1);
-    const f32x4 r = *reinterpret_cast<const f32x4*>(feat + ((size_t)(b * V) * HW + (size_t)y * W + xg) * C + cq * 4);
-    const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)(b * V + sv + 1) * HW * C, (unsigned)(HW * pix_bytes));
+    const f32x4 r = *reinterpret_cast<const f32x4*>(feat + ((size_t)view_block(b * V, views...) * HW + (size_t)y * W + xg) * C + cq * 4);
+    const mvs::rsrc_t src = mvs::make_rsrc(feat + (size_t)view_block(b * V + sv + 1, views...) * HW * C, (unsigned)(HW * pix_bytes));
     const float* rt = rt_all + (size_t)(b * (V - 1) + sv) * 12;
     const float* depth_row = depth + (size_t)b * D * HW + (size_t)y * W;
     const float half_w = (float)((W - 1) / 2.0), half_h = (float)((H - 1) / 2.0);
@@ -800,6 +815,20 @@ int check_shapes(const char* who, int B, int V, int C, int Gin, int D, int H, in
     return MVS_OK;
 }
 
+// Bank sweeps: the host copy of view_idx [B][V] -> the by-value table, every entry checked against the bank BEFORE anything is launched
+// (a bad table is an error code, never an out-of-range read).
+int fill_view_table(const char* who, const int* view_idx, int B, int V, int N, ViewTable* t) {
+    MVS_REQUIRE(view_idx, "%s: null view table", who);
+    MVS_REQUIRE(N >= 1, "%s: empty bank (N=%d)", who, N);
+    MVS_REQUIRE((int64_t)B * V <= MAX_VIEW_SLOTS, "%s: B*V = %lld view slots, the by-value table holds %d", who, (long long)B * V, MAX_VIEW_SLOTS);
+    *t = ViewTable{};
+    for (int i = 0; i < B * V; ++i) {
+        MVS_REQUIRE(view_idx[i] >= 0 && view_idx[i] < N, "%s: view_idx[%d][%d] = %d is outside the bank [0, %d)", who, i / V, i % V, view_idx[i], N);
+        t->idx[i] = view_idx[i];
+    }
+    return MVS_OK;
+}
+
 }  // namespace
 
 extern "C" int mvs_nchw_to_nhwc(const float* in, float* out, int N, int C, int64_t HW, mvs_stream_t stream) {
@@ -868,6 +897,36 @@ extern "C" int mvs_cv_entropy_fwd(const float* feat, const float* rt, const floa
     return mvs::finish_launch("mvs_cv_entropy_fwd");
 }
 
+// the same over a bank [N,H,W,C]: view v of sample b is bank block view_idx[b*V + v] (HOST array, column 0 = the reference view)
+extern "C" int mvs_cv_entropy_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, int B, int V, int C,
+                                        int Gin, int D, int H, int W, float* entropy, int flags, mvs_stream_t stream) {
+    MVS_REQUIRE(bank && rt && depth && entropy, "mvs_cv_entropy_fwd_views: null pointer");
+    if (int rc = check_shapes("mvs_cv_entropy_fwd_views", B, V, C, Gin, D, H, W)) return rc;
+    ViewTable views;
+    if (int rc = fill_view_table("mvs_cv_entropy_fwd_views", view_idx, B, V, N, &views)) return rc;
+    const int LPP = C / 4, PPW = 64 / LPP;
+    const size_t lds = (size_t)NW * 128 * 32 + (size_t)NW * PPW * D * sizeof(float);
+    MVS_REQUIRE(lds <= 64 * 1024, "mvs_cv_entropy_fwd_views: D=%d with C=%d needs %zu bytes of LDS (> 64 KiB)", D, C, lds);
+    const int gx = mvs::ceil_div(W, NW * PPW);
+    const int64_t total64 = (int64_t)gx * H * B * (V - 1);
+    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "mvs_cv_entropy_fwd_views: too many blocks");
+    const int total = (int)total64;
+    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
+    hipStream_t s = MVS_STREAM(stream);
+    const bool fast = !(flags & 1);
+#define MVS_LAUNCH_ENT(L)                                                                                                                          \
+    if (fast) hipLaunchKernelGGL((cv_entropy_kernel<L, true, ViewTable>), grid, block, lds, s, bank, rt, depth, V, D, H, W, entropy, gx, total, views); \
+    else hipLaunchKernelGGL((cv_entropy_kernel<L, false, ViewTable>), grid, block, lds, s, bank, rt, depth, V, D, H, W, entropy, gx, total, views)
+    switch (LPP) {
+        case 2: MVS_LAUNCH_ENT(2); break;
+        case 4: MVS_LAUNCH_ENT(4); break;
+        case 8: MVS_LAUNCH_ENT(8); break;
+        default: MVS_LAUNCH_ENT(16); break;
+    }
+#undef MVS_LAUNCH_ENT
+    return mvs::finish_launch("mvs_cv_entropy_fwd_views");
+}
+
 static int cv_aggregate_impl(const float* feat, const float* rt, const float* depth, const float* weight, int B, int V, int C, int Gin, int D, int H,
                              int W, float* volume, void* volume16, float* sim_depth, int flags, mvs_stream_t stream);
 
@@ -918,6 +977,42 @@ static int cv_aggregate_impl(const float* feat, const float* rt, const float* de
     return mvs::finish_launch("mvs_cv_aggregate_fwd");
 }
 
+extern "C" int mvs_cv_aggregate_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, const float* weight,
+                                          int B, int V, int C, int Gin, int D, int H, int W, float* volume, float* sim_depth, int flags,
+                                          mvs_stream_t stream) {
+    MVS_REQUIRE(bank && rt && depth && weight && volume, "mvs_cv_aggregate_fwd_views: null pointer");
+    if (int rc = check_shapes("mvs_cv_aggregate_fwd_views", B, V, C, Gin, D, H, W)) return rc;
+    ViewTable views;
+    if (int rc = fill_view_table("mvs_cv_aggregate_fwd_views", view_idx, B, V, N, &views)) return rc;
+    const int LPP = C / 4, PPW = 64 / LPP;
+    const int gx = mvs::ceil_div(W, NW * PPW);
+    const int64_t total64 = (int64_t)gx * H * B;
+    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "mvs_cv_aggregate_fwd_views: too many blocks");
+    const int total = (int)total64;
+    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
+    hipStream_t s = MVS_STREAM(stream);
+    const size_t lds = (size_t)NW * 128 * 32;
+    const bool fast = !(flags & 1);
+#define MVS_LAUNCH_AGG2(L, SIMV, FASTV)                                                                                                   \
+    hipLaunchKernelGGL((cv_aggregate_kernel<L, SIMV, FASTV, ViewTable>), grid, block, lds, s, bank, rt, depth, weight, V, D, H, W, volume, \
+                       sim_depth, gx, total, views, (__bf16*)nullptr)
+#define MVS_LAUNCH_AGG(L)                                                              \
+    if (sim_depth) {                                                                   \
+        if (fast) MVS_LAUNCH_AGG2(L, true, true); else MVS_LAUNCH_AGG2(L, true, false);   \
+    } else {                                                                           \
+        if (fast) MVS_LAUNCH_AGG2(L, false, true); else MVS_LAUNCH_AGG2(L, false, false); \
+    }
+    switch (LPP) {
+        case 2: MVS_LAUNCH_AGG(2); break;
+        case 4: MVS_LAUNCH_AGG(4); break;
+        case 8: MVS_LAUNCH_AGG(8); break;
+        default: MVS_LAUNCH_AGG(16); break;
+    }
+#undef MVS_LAUNCH_AGG
+#undef MVS_LAUNCH_AGG2
+    return mvs::finish_launch("mvs_cv_aggregate_fwd_views");
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // stored-correlation sweeps (coarse stages)
 // ---------------------------------------------------------------------------------------------------------
@@ -943,7 +1038,7 @@ extern "C" int64_t mvs_cv_corr_store_bytes(int B, int V, int C, int Gin, int D, 
 
 namespace {
 int corr_launch(const char* who, const float* feat, const float* rt, const float* depth, int B, int V, int C, int Gin, int D, int H, int W, int y0, int Hs,
-                float* entropy, void* store, int flags, mvs_stream_t stream) {
+                float* entropy, void* store, int flags, mvs_stream_t stream, const ViewTable* views = nullptr) {
     MVS_REQUIRE(feat && rt && depth && entropy && store, "%s: null pointer", who);
     if (int rc = check_shapes(who, B, V, C, Gin, D, H, W)) return rc;
     MVS_REQUIRE(C == 32 || C == 64, "%s: the stored-correlation sweeps are built for C = 32 and C = 64 (got %d)", who, C);
@@ -965,7 +1060,14 @@ int corr_launch(const char* who, const float* feat, const float* rt, const float
 #define MVS_LAUNCH_CORR(L)                                                                                                                          \
     if (fast) hipLaunchKernelGGL((cv_corr_kernel<L, true>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, y0, Hs); \
     else hipLaunchKernelGGL((cv_corr_kernel<L, false>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, y0, Hs)
-    if (LPP == 16) { MVS_LAUNCH_CORR(16); } else { MVS_LAUNCH_CORR(8); }
+#define MVS_LAUNCH_CORR_VIEWS(L)                                                                                                                     \
+    if (fast) hipLaunchKernelGGL((cv_corr_kernel<L, true, ViewTable>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, \
+                                 y0, Hs, *views);                                                                                                      \
+    else hipLaunchKernelGGL((cv_corr_kernel<L, false, ViewTable>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, y0, Hs, *views)
+    if (views) {                                            // feat is a bank [N,H,W,C]
+        if (LPP == 16) { MVS_LAUNCH_CORR_VIEWS(16); } else { MVS_LAUNCH_CORR_VIEWS(8); }
+    } else if (LPP == 16) { MVS_LAUNCH_CORR(16); } else { MVS_LAUNCH_CORR(8); }
+#undef MVS_LAUNCH_CORR_VIEWS
 #undef MVS_LAUNCH_CORR
     return mvs::finish_launch(who);
 }
@@ -1000,6 +1102,14 @@ extern "C" int mvs_cv_corr_fwd(const float* feat, const float* rt, const float* 
 extern "C" int mvs_cv_corr_rows_fwd(const float* feat, const float* rt, const float* depth, int B, int V, int C, int Gin, int D, int H, int W, int y0,
                                     int rows, float* entropy, void* store, int flags, mvs_stream_t stream) {
     return corr_launch("mvs_cv_corr_rows_fwd", feat, rt, depth, B, V, C, Gin, D, H, W, y0, rows, entropy, store, flags, stream);
+}
+
+extern "C" int mvs_cv_corr_rows_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, int B, int V, int C, int Gin,
+                                          int D, int H, int W, int y0, int rows, float* entropy, void* store, int flags, mvs_stream_t stream) {
+    MVS_REQUIRE(B >= 1 && V >= 2, "mvs_cv_corr_rows_fwd_views: bad shape B=%d V=%d", B, V);
+    ViewTable views;
+    if (int rc = fill_view_table("mvs_cv_corr_rows_fwd_views", view_idx, B, V, N, &views)) return rc;
+    return corr_launch("mvs_cv_corr_rows_fwd_views", bank, rt, depth, B, V, C, Gin, D, H, W, y0, rows, entropy, store, flags, stream, &views);
 }
 
 extern "C" int mvs_cv_merge_rows_fwd(const void* store, const float* depth, const float* weight, int B, int V, int C, int Gin, int D, int H, int W, int y0,

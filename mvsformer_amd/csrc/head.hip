@@ -173,6 +173,31 @@ __global__ void conf_accumulate_kernel(const float* __restrict__ conf, int H, in
     acc[o] = acc[o] + conf[((size_t)b * H + sy) * W + sx] * weight;
 }
 
+// A view's confidence record (test.py:289-292): the four stage confidences nearest-upsampled to the finest stage's H x W and stacked,
+// out [4][H][W] (plane k = stage k+1, from c_k [H >> (3-k)][W >> (3-k)]).  Integer factors 8, 4, 2, 1: the source pixel is dst >> shift, which
+// is what F.interpolate(mode='nearest') and cv2.INTER_NEAREST pick for these factors.  4 pixels of a row per thread, one 16-byte store per plane.
+struct ConfStackArgs { const float* c[4]; };
+__global__ __launch_bounds__(256) void conf_stack_kernel(const ConfStackArgs a, int H, int W, float* __restrict__ out) {
+    const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
+    if (x4 >= W || y >= H) return;
+    const size_t HW = (size_t)H * W, o = (size_t)y * W + x4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int sh = 3 - k, Wk = W >> sh;
+        const float* row = a.c[k] + (size_t)(y >> sh) * Wk;
+        float4 v;
+        if (sh >= 2) {                                       // the 4 pixels share one source pixel
+            v.x = v.y = v.z = v.w = row[x4 >> sh];
+        } else if (sh == 1) {
+            const float2 s2 = *reinterpret_cast<const float2*>(row + (x4 >> 1));
+            v = make_float4(s2.x, s2.x, s2.y, s2.y);
+        } else {
+            v = *reinterpret_cast<const float4*>(row + x4);
+        }
+        *reinterpret_cast<float4*>(out + k * HW + o) = v;
+    }
+}
+
 // stand-alone depth_regression (module.py:597-603): sum_d p*depth_values, depth_values [B,D,H,W] or [B,D]
 __global__ void depth_regression_kernel(const float* __restrict__ p, const float* __restrict__ dv, int per_pixel, int D, int H, int W,
                                         float* __restrict__ out) {
@@ -329,4 +354,16 @@ extern "C" int mvs_conf_accumulate(const float* conf, int B, int H, int W, float
     dim3 grid(mvs::ceil_div(Wf, 64), mvs::ceil_div(Hf, 4), B), block(64, 4);
     hipLaunchKernelGGL(conf_accumulate_kernel, grid, block, 0, MVS_STREAM(stream), conf, H, W, acc, Hf, Wf, weight);
     return mvs::finish_launch("mvs_conf_accumulate");
+}
+
+extern "C" int mvs_conf_stack(const float* c1, const float* c2, const float* c3, const float* c4, int H, int W, float* out, mvs_stream_t stream) {
+    MVS_REQUIRE(c1 && c2 && c3 && c4 && out, "mvs_conf_stack: null pointer");
+    MVS_REQUIRE(H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && H <= 4 * 65535, "mvs_conf_stack: H, W must be multiples of 8 (got %d x %d)", H, W);
+    // 16-byte stores into out, 16- / 8-byte loads from the stage-4 / stage-3 maps (W % 8 == 0 keeps every row aligned once the base is)
+    MVS_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(c4) & 15) == 0 && (reinterpret_cast<uintptr_t>(c3) & 7) == 0,
+                "mvs_conf_stack: out / stage-4 map must be 16-byte aligned, the stage-3 map 8-byte aligned");
+    ConfStackArgs a{{c1, c2, c3, c4}};
+    dim3 grid(mvs::ceil_div(W, 256), mvs::ceil_div(H, 4)), block(64, 4);
+    hipLaunchKernelGGL(conf_stack_kernel, grid, block, 0, MVS_STREAM(stream), a, H, W, out);
+    return mvs::finish_launch("mvs_conf_stack");
 }

@@ -404,6 +404,99 @@ def cv_merge_rows(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor
           _ptr(volume), _ptr(sim_depth), _stream())
 
 
+# ----------------------------------------------------------------------------------------------- sweeps over a feature bank
+def _view_table(view_idx, who: str):
+    """``view_idx [B,V]`` (nested sequence, numpy array or CPU integer tensor; column 0 = the reference view) -> (ctypes int array, B, V).
+    A HOST table on purpose: the C entry checks every value against the bank before it launches and passes the table by value."""
+    if isinstance(view_idx, torch.Tensor):
+        if view_idx.is_cuda or view_idx.is_floating_point():
+            raise _lib.MvsHipError("%s: view_idx is a host table of integers (list, numpy array or CPU integer tensor)" % who)
+        view_idx = view_idx.tolist()
+    elif hasattr(view_idx, "tolist"):
+        view_idx = view_idx.tolist()
+    rows = [list(r) for r in view_idx]
+    if not rows or any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) < 2:
+        raise _lib.MvsHipError("%s: view_idx must be [B,V>=2]" % who)
+    raw = [v for r in rows for v in r]
+    flat = [int(v) for v in raw]
+    if flat != raw:
+        raise _lib.MvsHipError("%s: view_idx must hold integers" % who)
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in flat):
+        raise _lib.MvsHipError("%s: view_idx value outside the int range" % who)
+    return (ctypes.c_int * len(flat))(*flat), len(rows), len(rows[0])
+
+
+def _chk_bank(bank: torch.Tensor, view_idx, depth: torch.Tensor, who: str):
+    _chk(bank, "feature bank")
+    if bank.dim() != 4:
+        raise _lib.MvsHipError("%s: the bank must be channel-last [N,H,W,C], got %s" % (who, tuple(bank.shape)))
+    table, B, V = _view_table(view_idx, who)
+    N, H, W, C = bank.shape
+    D = depth.shape[1] if depth.dim() == 4 else -1
+    if depth.shape != (B, D, H, W):
+        raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, "D", H, W), tuple(depth.shape)))
+    return table, B, V, N, H, W, C, D
+
+
+def cv_entropy_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None) -> torch.Tensor:
+    """:func:`cv_entropy` over a bank ``[N,H,W,C]``: view ``v`` of sample ``b`` is ``bank[view_idx[b][v]]``.  Bit-identical to the dense op on
+    the gathered views."""
+    _chk(rt, "rt"), _chk(depth, "depth_values")
+    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_entropy_views")
+    if rt.shape != (B, V - 1, 12):
+        raise _lib.MvsHipError("rt must be [B,V-1,12]=%s, got %s" % ((B, V - 1, 12), tuple(rt.shape)))
+    ent = torch.empty(B, V - 1, H, W, device=bank.device, dtype=torch.float32)
+    tag = ("cv_entropy_views_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
+    _call("mvs_cv_entropy_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _cv_flags(exact), _stream())
+    return ent
+
+
+def cv_aggregate_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, G: int, want_sim_depth: bool,
+                       exact: Optional[bool] = None):
+    """:func:`cv_aggregate` over a bank (see :func:`cv_entropy_views`) -> ``(volume [B,G,D,H,W], sim_depth [B,H,W] | None)``."""
+    _chk(rt, "rt"), _chk(depth, "depth_values"), _chk(weight, "vis_weight")
+    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_aggregate_views")
+    if rt.shape != (B, V - 1, 12) or weight.shape != (B, V - 1, H, W):
+        raise _lib.MvsHipError("cv_aggregate_views: rt %s / weight %s do not match B=%d V=%d H=%d W=%d" % (tuple(rt.shape), tuple(weight.shape), B, V, H, W))
+    vol = torch.empty(B, G, D, H, W, device=bank.device, dtype=torch.float32)
+    sim = torch.empty(B, H, W, device=bank.device, dtype=torch.float32) if want_sim_depth else None
+    tag = ("cv_aggregate_views_kernel<%d,%s>" % (C // 4, "true" if want_sim_depth else "false"), "bytes", 4.0 * B * H * W * (V * C + D + G * D))
+    _call("mvs_cv_aggregate_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W, _ptr(vol), _ptr(sim),
+          _cv_flags(exact), _stream())
+    return vol, sim
+
+
+def cv_corr_rows_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, G: int, y0: int, rows: int,
+                       store: Optional[torch.Tensor] = None, exact: Optional[bool] = None):
+    """:func:`cv_corr_rows` over a bank (see :func:`cv_entropy_views`); ``y0 = 0, rows = H`` is :func:`cv_corr`.  The store is read by
+    :func:`cv_merge` / :func:`cv_merge_rows`, which never see features."""
+    _chk(rt, "rt"), _chk(depth, "depth_values")
+    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_corr_rows_views")
+    if rt.shape != (B, V - 1, 12):
+        raise _lib.MvsHipError("rt must be [B,V-1,12]=%s, got %s" % ((B, V - 1, 12), tuple(rt.shape)))
+    y0, rows = int(y0), int(rows)
+    if y0 < 0 or rows < 1 or y0 + rows > H:
+        raise _lib.MvsHipError("cv_corr_rows_views: rows [%d, %d) outside the image (H = %d)" % (y0, y0 + rows, H))
+    nbytes = int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, rows, W))
+    if nbytes <= 0:
+        raise _lib.MvsHipError("stored-correlation sweeps are not built for C=%d, G=%d, D=%d" % (C, G, D))
+    if store is None or store.numel() * 4 < nbytes:
+        store = torch.empty(nbytes // 4, device=bank.device, dtype=torch.float32)
+    else:
+        _chk(store, "correlation store")
+    ent = torch.empty(B, V - 1, rows, W, device=bank.device, dtype=torch.float32)
+    tag = ("cv_corr_views_kernel<%d>" % (C // 4), "bytes", 4.0 * B * rows * W * (V * C + D))
+    _call("mvs_cv_corr_rows_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, y0, rows, _ptr(ent), _ptr(store),
+          _cv_flags(exact), _stream())
+    return ent, store
+
+
+def cv_bank_store_bytes(bank: torch.Tensor, B: int, V: int, D: int, G: int) -> int:
+    """:func:`cv_store_bytes` for ``B`` samples of ``V`` views taken from a bank ``[N,H,W,C]``."""
+    _, H, W, C = bank.shape
+    return int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, H, W))
+
+
 def cv_tiled_supported(feat: torch.Tensor) -> bool:
     """The LDS-tiled sweeps take the FPN decoder's NCHW ``[B,V,C,H,W]`` maps directly (C in 8/16/32/64, contiguous fp32)."""
     return (isinstance(feat, torch.Tensor) and feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 5 and feat.is_contiguous()
@@ -781,6 +874,31 @@ def conf_accumulate(conf: torch.Tensor, acc: torch.Tensor, weight: float = 1.0) 
     B, H, W = conf.shape
     _, Hf, Wf = acc.shape
     _call("mvs_conf_accumulate", None, _ptr(conf), B, H, W, _ptr(acc), Hf, Wf, float(weight), _stream())
+
+
+def conf_stack(confs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The four stage confidences ``[H/8,W/8] .. [H,W]`` (a leading batch dimension of 1 allowed) nearest-upsampled and stacked into
+    ``out [4,H,W]`` in one launch (test.py:289-292); ``out`` may be a slice of a scene-wide ``[Nv,4,H,W]`` tensor."""
+    if len(confs) != 4:
+        raise _lib.MvsHipError("conf_stack takes the four stage confidences")
+    cs = []
+    for k, c in enumerate(confs):
+        _chk(c, "stage %d confidence" % (k + 1))
+        if c.dim() == 3 and c.shape[0] == 1:
+            c = c[0]
+        if c.dim() != 2:
+            raise _lib.MvsHipError("conf_stack: stage %d confidence must be [H,W] (or [1,H,W]), got %s" % (k + 1, tuple(c.shape)))
+        cs.append(c)
+    H, W = cs[3].shape
+    if H % 8 or W % 8 or any(tuple(cs[k].shape) != (H >> (3 - k), W >> (3 - k)) for k in range(4)):
+        raise _lib.MvsHipError("conf_stack: stage maps %s are not H/8, H/4, H/2, H of a multiple-of-8 size" % ([tuple(c.shape) for c in cs],))
+    if out is None:
+        out = torch.empty(4, H, W, device=cs[3].device, dtype=torch.float32)
+    _chk(out, "confidence record")
+    if tuple(out.shape) != (4, H, W):
+        raise _lib.MvsHipError("conf_stack: out must be [4,%d,%d], got %s" % (H, W, tuple(out.shape)))
+    _call("mvs_conf_stack", None, _ptr(cs[0]), _ptr(cs[1]), _ptr(cs[2]), _ptr(cs[3]), H, W, _ptr(out), _stream())
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- training kernels

@@ -38,14 +38,17 @@ def _store_plan(feat_cl, D, G) -> int:
     stay inside the 256 MB Infinity Cache next to the feature maps (MVS_CV_STORE_MAX_MB, default 160; 0 disables the path; MVS_CV_STORE_BANDS caps
     k, default 1 - banding is opt-in until it is measured faster at config-2 stage 2).  Measured at config 2 (profiles/r03_bench_sweeps.txt): stage 1 (127 MB) 0.30 -> 0.20 ms for
     the pair; stage 2 in one piece (254 MB: the round trip goes to HBM) 0.29 -> 0.32 ms."""
+    return _store_plan_bytes(ops.cv_store_bytes(feat_cl, D, G), feat_cl.shape[2])
+
+
+def _store_plan_bytes(nbytes: int, H: int) -> int:
+    """:func:`_store_plan` from the store's size (``ops.cv_store_bytes``; <= 0: not built for the shape) and the image height."""
     limit = float(os.environ.get("MVS_CV_STORE_MAX_MB", "160")) * 2 ** 20
     max_bands = int(os.environ.get("MVS_CV_STORE_BANDS", "1"))
-    nbytes = ops.cv_store_bytes(feat_cl, D, G)
     if nbytes <= 0 or limit <= 0:
         return 0
     if nbytes <= limit:
         return 1
-    H = feat_cl.shape[2]
     for k in range(2, max_bands + 1):
         rows = -(-H // k) + 2 * VIS_HALO + 1                  # (+1: a band's first row is rounded down to even)
         if rows < H and nbytes * rows / H <= limit:
@@ -152,7 +155,57 @@ class StageNet(nn.Module):
                 weight = self._vis_weight(entropy, vis_params, vis_prepared)
                 volume, sim_depth = ops.cv_aggregate(feat, rt, hyp, weight, G, want_sim_depth=True)
 
-        # step 3: regularization + head
+        return self._regularize_head(volume, sim_depth, hyp, depth_values, tmp)
+
+    def forward_bank(self, bank, view_idx, proj_matrices, depth_values, tmp=2.0):
+        """Eval forward over a feature BANK: ``bank [N,H,W,C]`` channel-last holds a scene's views once each, ``view_idx [B,V]`` (host
+        integers, column 0 = the reference view) says which of them sample ``b`` is made of; ``proj_matrices [B,V,2,4,4]`` and
+        ``depth_values [B,D,H,W]`` as for :meth:`forward`.  Same plan, same kernels' arithmetic and same output dict as ``forward`` on
+        ``bank[view_idx]`` - the sweeps read the views in place (``ops.cv_*_views``).  ``MVS_CV_TILED`` is ignored: the LDS-tiled sweeps
+        have no indexed form."""
+        if self.training:
+            raise MvsHipError("StageNet.forward_bank is an inference path: call .eval() first (training reads [B,V,C,H,W] through forward)")
+        G = self.args["base_ch"]
+        if not isinstance(bank, torch.Tensor) or not bank.is_cuda or bank.dim() != 4:
+            raise MvsHipError("bank must be a channel-last GPU tensor [N,H,W,C]: the MI355X HIP path is the only implementation (no CPU fallback)")
+        bank = bank.detach()
+        proj = proj_matrices.detach().to(torch.float32).contiguous()
+        hyp = depth_values.detach().to(torch.float32).contiguous()
+        if hyp.dim() != 4:
+            raise MvsHipError("depth_values must be [B,D,H,W]")
+        rows = view_idx.tolist() if hasattr(view_idx, "tolist") else [list(r) for r in view_idx]
+        B, V = len(rows), len(rows[0])
+        if proj.shape[:2] != (B, V):
+            raise AssertionError("Different number of images and projection matrices")
+        rt = ops.proj_prepare(proj)
+        vis_params, vis_prepared = self._vis_params()
+        H_, W_, C_ = bank.shape[1:]
+        D_ = hyp.shape[1]
+        bands = _store_plan_bytes(ops.cv_bank_store_bytes(bank, B, V, D_, G), H_)
+        if bands == 1:
+            entropy, store = ops.cv_corr_rows_views(bank, rows, rt, hyp, G, 0, H_)
+            weight = self._vis_weight(entropy, vis_params, vis_prepared)
+            volume, sim_depth = ops.cv_merge(store, hyp, weight, V, C_, G, want_sim_depth=True)
+        elif bands > 1:                                         # row bands, as in forward()
+            volume = torch.empty(B, G, D_, H_, W_, device=bank.device, dtype=torch.float32)
+            sim_depth = torch.empty(B, H_, W_, device=bank.device, dtype=torch.float32)
+            hb = -(-H_ // bands)
+            store = None
+            for r0 in range(0, H_, hb):
+                r1 = min(H_, r0 + hb)
+                y0, y1 = max(0, (r0 - VIS_HALO) & ~1), min(H_, r1 + VIS_HALO)
+                entropy, store = ops.cv_corr_rows_views(bank, rows, rt, hyp, G, y0, y1 - y0, store)
+                weight = self._vis_weight(entropy, vis_params, vis_prepared)
+                ops.cv_merge_rows(store, hyp, weight, V, C_, G, y0, r0 - y0, r1 - r0, volume, sim_depth)
+        else:
+            entropy = ops.cv_entropy_views(bank, rows, rt, hyp, G)
+            weight = self._vis_weight(entropy, vis_params, vis_prepared)
+            volume, sim_depth = ops.cv_aggregate_views(bank, rows, rt, hyp, weight, G, want_sim_depth=True)
+        return self._regularize_head(volume, sim_depth, hyp, depth_values, tmp)
+
+    def _regularize_head(self, volume, sim_depth, hyp, depth_values, tmp):
+        """Step 3 of the eval forward: regularization + head."""
+        depth_type = self.args["depth_type"]
         if type(tmp) == list:
             tmp = tmp[self.stage_idx]
         if isinstance(self.cost_reg, CostRegNet3D):

@@ -1,0 +1,112 @@
+#!/usr/bin/env python
+"""Depth inference over a whole scan with every image through the FPN and the ViT once (``mvsformer_amd.scene.SceneInference``):
+
+    python tools/infer_scan.py --scan SCAN_FOLDER --checkpoint model_best.pth [--config config.json] [--num_view 5] [--numdepth 192]
+        [--interval_scale 1.06] [--tmp 5,5,5,1] [--out OUT_FOLDER] [--ply cloud.ply] [--prob_threshold 0.5,0.5,0.5,0.5] [--method pcd]
+
+``SCAN_FOLDER`` holds ``images/%08d.jpg|png``, ``cams/%08d_cam.txt`` and ``pair.txt`` (the layout ``general_eval.py`` reads).  ``--out`` gets
+the files the reference's ``save_depth`` writes (``depth_est/``, ``confidence/``, ``cams/``, ``images/``: ``tools/fuse_scan.py`` and the
+reference's own filter step consume them); ``--ply`` fuses the scan on the device with no file in between.  Images are used as they are:
+their size must be a multiple of 64 (resize / crop beforehand - datasets are out of scope here), and the intrinsics in the camera files
+must belong to that size.  Needs the GPU.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mvsformer_amd as m  # noqa: E402
+from mvsformer_amd import data_io  # noqa: E402
+from mvsformer_amd.scene import IMAGENET_MEAN, IMAGENET_STD  # noqa: E402
+
+DEFAULT_ARGS = dict(fix=True, depth_type="ce", fusion_type="cnn", inverse_depth=True, attn_temp=2.0, base_ch=8, ndepths=[32, 16, 8, 4], feat_chs=[8, 16, 32, 64],
+                    depth_interals_ratio=[4.0, 2.67, 1.5, 1.0], multi_scale=False,
+                    vit_args=dict(twin=False, rescale=0.5, do_vit=True, patch_size=16, qk_scale="default", vit_arch="vit_small", vit_ch=384, out_ch=64,
+                                  att_fusion=True, nhead=6))
+
+
+def depth_values(cam_file, numdepth, interval_scale):
+    """general_eval.py:91-104,220: ``depth_min`` / ``depth_interval`` from line 11 of the camera file -> the hypothesis range."""
+    with open(cam_file) as f:
+        lines = [ln.rstrip() for ln in f.readlines()]
+    tok = lines[11].split()
+    depth_min, interval = float(tok[0]), float(tok[1])
+    if len(tok) >= 3:
+        depth_max = depth_min + int(float(tok[2])) * interval
+        interval = (depth_max - depth_min) / numdepth
+    interval *= interval_scale
+    return np.arange(depth_min, interval * (numdepth - 0.5) + depth_min, interval, dtype=np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scan", required=True)
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--config", default=None, help="the reference's config json (arch.args); default: MVSFormer-P")
+    ap.add_argument("--num_view", type=int, default=5)
+    ap.add_argument("--numdepth", type=int, default=192)
+    ap.add_argument("--interval_scale", type=float, default=1.06)
+    ap.add_argument("--tmp", default="5,5,5,1")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--ply", default=None)
+    ap.add_argument("--prob_threshold", default="0.5,0.5,0.5,0.5")
+    ap.add_argument("--method", default="pcd", choices=["pcd", "dypcd"])
+    ap.add_argument("--combine_conf", action="store_true")
+    ap.add_argument("--capacity_views", type=int, default=None)
+    ap.add_argument("--max_bank_mb", type=float, default=16384.0)
+    ap.add_argument("--extract_batch", type=int, default=4)
+    a = ap.parse_args()
+    if not a.out and not a.ply:
+        raise SystemExit("nothing to do: give --out and / or --ply")
+    if not torch.cuda.is_available():
+        raise SystemExit("infer_scan.py runs the MI355X path: no GPU")
+    dev = torch.device("cuda:0")
+    args = json.load(open(a.config))["arch"]["args"] if a.config else DEFAULT_ARGS
+    net = m.DINOMVSNet(args)
+    sd = torch.load(a.checkpoint, map_location="cpu")
+    sd = sd.get("state_dict", sd)
+    net.load_state_dict({k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}, strict=True)
+    net = net.to(dev).eval()
+    pairs = data_io.read_pair_file(os.path.join(a.scan, "pair.txt"))
+    ids = []
+    for r, srcs in pairs:
+        for v in [r] + srcs:
+            if v not in ids:
+                ids.append(v)
+    si = m.SceneInference(net, capacity_views=a.capacity_views, max_bank_mb=a.max_bank_mb, extract_batch=a.extract_batch, combine_conf=a.combine_conf)
+    mean, std = np.array(IMAGENET_MEAN, np.float32), np.array(IMAGENET_STD, np.float32)
+    t0 = time.perf_counter()
+    for v in ids:
+        path = data_io._image_path(a.scan, v)
+        if path is None:
+            raise SystemExit("no images/{:0>8}.jpg (or .png) in {}".format(v, a.scan))
+        img = data_io.read_img(path)
+        if img.shape[0] % 64 or img.shape[1] % 64:
+            raise SystemExit("%s is %dx%d: H and W must be multiples of 64 (resize / crop the scan first)" % (path, img.shape[0], img.shape[1]))
+        cam_file = os.path.join(a.scan, "cams/{:0>8}_cam.txt".format(v))
+        x = ((img.astype(np.float32) / 255.0 - mean) / std).transpose(2, 0, 1)
+        si.add_image(v, torch.from_numpy(np.ascontiguousarray(x)).to(dev), torch.from_numpy(data_io._cam_2x4x4(cam_file)).to(dev),
+                     torch.from_numpy(depth_values(cam_file, a.numdepth, a.interval_scale)).to(dev))
+    si.set_pairs(pairs, num_views=a.num_view)
+    th = [float(x) for x in a.prob_threshold.split(",")]
+    fusion = m.SceneFusion(a.method, th, combine_conf=a.combine_conf, device="cuda:0") if a.ply else None
+    t1 = time.perf_counter()
+    si.run(tmp=[float(x) for x in a.tmp.split(",")], fusion=fusion, save_to=a.out)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    res = dict(views=len(ids), samples=len(pairs), seconds=dict(load=t1 - t0, infer=t2 - t1), bank=si.stats)
+    if fusion is not None:
+        out = fusion.fuse(want=("records",))
+        data_io.write_ply_records(a.ply, out["records"], out["n_points"])
+        res.update(n_points=out["n_points"], ply=a.ply)
+        res["seconds"]["fuse"] = time.perf_counter() - t2
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
