@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
         idx = min(idx, D - 1);
         const bool in_range = !(g < lo) && !(g > hi);
         const bool valid = in_range && (mask[(size_t)b * HW + pix] > 0.5f);
-        const float lse = m + logf(s);
+        const float ls = logf(s), lse = m + ls;
         if (valid) {
             lsum = lse - at(lg, idx);
             cnt = 1.0f;
@@ -59,8 +59,10 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
         if (grad) {
             float* gr = grad + (size_t)b * D * HW + pix;
             const int hot = INVERSE ? D - 1 - idx : idx;
+            // softmax as exp((l - max) - log s): m + log s rounds at the size of the logits (2^-17 at |l| ~ 80), which would show
+            // in every p of a peaked column; l - max is exact for the entries that carry the mass
             for (int d = 0; d < D; ++d) {
-                const float p = expf(lg[(size_t)d * HW] - lse);
+                const float p = expf((lg[(size_t)d * HW] - m) - ls);
                 gr[(size_t)d * HW] = valid ? (p - (d == hot ? 1.0f : 0.0f)) : 0.0f;
             }
         }
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(256) void mixup_ce_loss_kernel(const float* __restr
         const float wl = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x), wr = 1.0f - wl;      // torch.clamp: a NaN stays a NaN
         const float outl = g < lo ? 1.0f : 0.0f, outr = g > hi ? 1.0f : 0.0f;
         const float fm = (1.0f - fminf(outl + outr, 1.0f)) * (mask[(size_t)b * HW + pix] > 0.5f ? 1.0f : 0.0f);
-        const float lsel = ml + logf(sl), lser = mr + logf(sr);
+        const float lsl = logf(sl), lsr = logf(sr), lsel = ml + lsl, lser = mr + lsr;
         lsum = (lsel - at(lg, idx)) * wl * fm + (lser - at(lg, idx + 1)) * wr * fm;
         cnt = fm;
         if (grad) {
@@ -130,8 +132,9 @@ __global__ __launch_bounds__(256) void mixup_ce_loss_kernel(const float* __restr
                 const int j = INVERSE ? D - 1 - d : d;       // position in the flipped column
                 const float l = lg[(size_t)d * HW];
                 float v = 0.0f;
-                if (j < D - 1) v += wl * fm * (expf(l - lsel) - (j == idx ? 1.0f : 0.0f));
-                if (j >= 1) v += wr * fm * (expf(l - lser) - (j == idx + 1 ? 1.0f : 0.0f));
+                // exp((l - max) - log s), as in ce_loss_kernel: no rounding at the size of the logits
+                if (j < D - 1) v += wl * fm * (expf((l - ml) - lsl) - (j == idx ? 1.0f : 0.0f));
+                if (j >= 1) v += wr * fm * (expf((l - mr) - lsr) - (j == idx + 1 ? 1.0f : 0.0f));
                 gr[(size_t)d * HW] = v;
             }
         }

@@ -1,13 +1,26 @@
 """TEST INFRASTRUCTURE — CPU oracle for the training losses: restates reference
 models/losses.py:304-350 (ce_loss_stage4, focal=False), :353-408 (mixup_ce_loss_stage4) and :51-85 (reg_loss_stage4) for one stage,
 in the order of operations the reference uses.  Pinned by tests/golden/ce_loss.npz and other_losses.npz (values and gradients produced
-by the real functions).  Never imported by the product path."""
+by the real functions).  Never imported by the product path.
+
+Precision: every loss takes its DISCRETE decisions (the CE bin index and validity, the reg-loss range mask, the Wasserstein nearest-hypothesis
+index, the mixup interval index and range mask) from float32 comparisons of the float32 values of ``depth_values`` / ``depth_gt`` / ``mask``,
+whatever dtype the arguments have: those comparisons define the reference (ground truths that sit exactly on a float32 bin edge move to the
+neighbouring bin when the edges are re-evaluated in float64).  The CONTINUOUS part (log-sum-exp, mix weights, smooth-L1, the Sinkhorn
+iterations) runs in the dtype of the differentiable argument, so passing float64 tensors gives a float64 value and, through autograd, a
+float64 gradient for exactly the pixels and bins the float32 reference selects.  With float32 arguments nothing changes."""
 import torch
 import torch.nn.functional as F
 
 
+def _f32(x):
+    """The float32 value the discrete decisions are taken on (exact for inputs that were float32 before a ``.double()``)."""
+    return x.detach().to(torch.float32)
+
+
 def gt_bins(depth_values, depth_gt, mask, inverse_depth=True):
     """losses.py:309-335 -> (gt_index [B,H,W] long, final_mask [B,H,W] bool), index in flipped order when inverse."""
+    depth_values, depth_gt, mask = _f32(depth_values), _f32(depth_gt), _f32(mask)
     gt = depth_gt.unsqueeze(1)
     dv = torch.flip(depth_values, dims=[1]) if inverse_depth else depth_values
     half = (dv[:, 1:] - dv[:, :-1]).abs() / 2
@@ -30,16 +43,24 @@ def ce_loss_stage4(inputs, depth_gt_ms, mask_ms, dlossw, inverse_depth=True):
                              1.0 if dlossw is None else dlossw[int(k[-1]) - 1]) for k in ("stage1", "stage2", "stage3", "stage4")}
 
 
+def mixup_bins(depth_values, depth_gt, mask, inverse_depth=True):
+    """losses.py:358-376 -> (index of the interval's left hypothesis [B,H,W] long in flipped order, float mask [B,H,W]: in range and mask > 0.5)."""
+    gt32 = _f32(depth_gt).unsqueeze(1)
+    dv32 = torch.flip(_f32(depth_values), dims=[1]) if inverse_depth else _f32(depth_values)
+    outside = torch.clamp((gt32 < dv32[:, 0:1]).float() + (gt32 > dv32[:, -1:]).float(), 0, 1)
+    final = (1 - outside).squeeze(1) * (_f32(mask) > 0.5).float()
+    index = (dv32[:, 1:] <= gt32.expand_as(dv32[:, :-1])).float().sum(dim=1, keepdim=True).long()
+    return torch.clamp_max(index, dv32.shape[1] - 2).squeeze(1), final
+
+
 def mixup_ce_loss_stage(prob_volume_pre, depth_values, depth_gt, mask, inverse_depth=True, weight=1.0):
     """losses.py:358-399 for one stage."""
-    gt = depth_gt.unsqueeze(1)
-    maskf = (mask > 0.5).float()
-    dv = torch.flip(depth_values, dims=[1]) if inverse_depth else depth_values
+    dt = prob_volume_pre.dtype
+    index, final = mixup_bins(depth_values, depth_gt, mask, inverse_depth)
+    final = final.to(dt)
+    gt = depth_gt.to(dt).unsqueeze(1)
+    dv = torch.flip(depth_values.to(dt), dims=[1]) if inverse_depth else depth_values.to(dt)
     logits = torch.flip(prob_volume_pre, dims=[1]) if inverse_depth else prob_volume_pre
-    outside = torch.clamp((gt < dv[:, 0:1]).float() + (gt > dv[:, -1:]).float(), 0, 1)
-    final = (1 - outside).squeeze(1) * maskf
-    index = (dv[:, 1:] <= gt.expand_as(dv[:, :-1])).float().sum(dim=1, keepdim=True).long()
-    index = torch.clamp_max(index, dv.shape[1] - 2).squeeze(1)
     left = torch.gather(dv[:, :-1], 1, index.unsqueeze(1))
     itv = torch.gather((dv[:, 1:] - dv[:, :-1]).abs(), 1, index.unsqueeze(1))
     wl = torch.clamp((gt - left).abs() / itv, 0, 1).squeeze(1)
@@ -55,18 +76,24 @@ def mixup_ce_loss_stage4(inputs, depth_gt_ms, mask_ms, dlossw, inverse_depth=Tru
                                    1.0 if dlossw is None else dlossw[int(k[-1]) - 1]) for k in ("stage1", "stage2", "stage3", "stage4")}
 
 
-def reg_loss_stage(depth, depth_values, depth_gt, mask, interval, mask_out_range=False, inverse_depth=True, weight=1.0):
-    """losses.py:56-84 for one stage; ``interval [B]``."""
-    itv = interval.reshape(-1, 1, 1)
-    sel = mask > 0.5
+def reg_select(depth_values, depth_gt, mask, mask_out_range=False, inverse_depth=True):
+    """losses.py:58-74 -> the pixels the mean runs over [B,H,W] bool."""
+    sel = _f32(mask) > 0.5
     if mask_out_range:
-        dv = torch.flip(depth_values, dims=[1]) if inverse_depth else depth_values
+        dv = torch.flip(_f32(depth_values), dims=[1]) if inverse_depth else _f32(depth_values)
         half = (dv[:, 1:] - dv[:, :-1]).abs() / 2
         half = torch.cat([half, half[:, -1:]], dim=1)
         lo, hi = dv[:, 0] - half[:, 0], dv[:, -1] + half[:, -1]
-        outside = torch.clamp((depth_gt < lo).float() + (depth_gt > hi).float(), 0, 1)
+        outside = torch.clamp((_f32(depth_gt) < lo).float() + (_f32(depth_gt) > hi).float(), 0, 1)
         sel = sel & (1 - outside).bool()
-    return weight * F.smooth_l1_loss((depth / itv)[sel], (depth_gt / itv)[sel], reduction="mean")
+    return sel
+
+
+def reg_loss_stage(depth, depth_values, depth_gt, mask, interval, mask_out_range=False, inverse_depth=True, weight=1.0):
+    """losses.py:56-84 for one stage; ``interval [B]``."""
+    itv = interval.to(depth.dtype).reshape(-1, 1, 1)
+    sel = reg_select(depth_values, depth_gt, mask, mask_out_range, inverse_depth)
+    return weight * F.smooth_l1_loss((depth / itv)[sel], (depth_gt.to(depth.dtype) / itv)[sel], reduction="mean")
 
 
 def reg_loss_stage4(inputs, depth_gt_ms, mask_ms, dlossw, depth_interval, mask_out_range=False, inverse_depth=True):
@@ -102,15 +129,20 @@ def make_loss_case(seed=0, B=2, sizes=((32, 8, 12), (16, 16, 24), (8, 24, 32), (
     return inputs, gts, masks
 
 
+def nearest_hypothesis(depth_values, depth_gt):
+    """losses.py:136-138: index of the hypothesis nearest to the ground truth [B,H,W] long, the first one on a tie (torch.min)."""
+    return (_f32(depth_values) - _f32(depth_gt)[:, None]).abs().min(1)[1]
+
+
 def sinkhorn_stage(prob, depth_values, depth_gt, mask, iters=10, eps=1.0, weight=1.0):
     """models/losses.py:88-128 with ``continuous=False``: the log-domain Sinkhorn plan between each pixel's probability column and the one-hot of
     the hypothesis nearest to the ground truth, cost |i - j| / eps (the reference's signs: + cost in the exponent), loss = mean over
     ``mask > 0.5`` of sum_ij T_ij |i - j|.  Plain torch (autograd gives the gradient through all iterations)."""
     B, D, H, W = prob.shape
-    ar = torch.arange(D, dtype=torch.float32)
+    ar = torch.arange(D, dtype=prob.dtype)
     Dm = (ar[:, None] - ar[None, :]).abs()                                   # [D (i: prediction), D (j: ground truth)]
-    gi = (depth_values - depth_gt[:, None]).abs().min(1)[1].reshape(B * H * W)
-    mu = torch.zeros(B * H * W, D)
+    gi = nearest_hypothesis(depth_values, depth_gt).reshape(B * H * W)
+    mu = torch.zeros(B * H * W, D, dtype=prob.dtype)
     mu[torch.arange(B * H * W), gi] = 1.0
     nu = prob.permute(0, 2, 3, 1).reshape(B * H * W, D)
     log_mu, log_nu = (mu + 1e-12).log(), (nu + 1e-12).log()
@@ -119,7 +151,7 @@ def sinkhorn_stage(prob, depth_values, depth_gt, mask, iters=10, eps=1.0, weight
         v = log_mu - torch.logsumexp(Dm[None] / eps + u[:, :, None], dim=1)
         u = log_nu - torch.logsumexp(Dm[None] / eps + v[:, None, :], dim=2)
     T = (Dm[None] / eps + u[:, :, None] + v[:, None, :]).exp()
-    sel = (mask > 0.5).reshape(-1)
+    sel = (_f32(mask) > 0.5).reshape(-1)
     return weight * (T * Dm[None]).reshape(B * H * W, -1)[sel].sum(-1).mean()
 
 

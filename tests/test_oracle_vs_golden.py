@@ -249,6 +249,81 @@ def test_mixup_ce_and_reg_loss_oracle_vs_reference(tag, inverse):
             assert max_abs(reg_in[k]["depth"].grad, g["%s_%s_reg%d_grad" % (tag, k, rng)]) < 1e-8
 
 
+def _f64_leaf(a):
+    return a.double().requires_grad_(True)
+
+
+@pytest.mark.parametrize("tag,inverse", [("inv", True), ("fwd", False)])
+def test_loss_oracles_fp64_path_vs_reference(tag, inverse):
+    """The float64 path of oracle/ref_losses.py (continuous part in float64, discrete decisions from float32 comparisons) on the golden
+    inputs against the values and gradients the real models/losses.py functions recorded in float32 (ce_loss.npz, other_losses.npz):
+    the same pixels and bins are selected, so the two differ by the float32 rounding of the recorded run only.  A reference that also
+    took the decisions in float64 would move a few bins per stage (ground truths exactly on a float32 bin edge) and miss these bounds."""
+    from oracle import ref_losses
+    gc, go = load_golden("ce_loss.npz"), load_golden("other_losses.npz")
+    inputs, gts, masks = _loss_inputs(tag)
+    itv = t(go[tag + "_interval"])
+    for s, k in enumerate(inputs):
+        dv, gt, mask = inputs[k]["depth_values"], gts[k], masks[k]
+        wc, wo = float(gc[tag + "_dlossw"][s]), float(go["dlossw"][s])
+        lg = _f64_leaf(inputs[k]["prob_volume_pre"])
+        loss = ref_losses.ce_loss_stage(lg, dv.double(), gt.double(), mask.double(), inverse, wc)
+        assert loss.dtype == torch.float64
+        loss.backward()
+        want, wg = float(gc["%s_%s_loss" % (tag, k)]), gc["%s_%s_grad" % (tag, k)]
+        assert abs(loss.item() - want) < 1e-6 * max(1.0, abs(want)), k
+        assert max_abs(lg.grad, wg) < 1e-6 * np.abs(wg).max(), k
+        i64, f64 = ref_losses.gt_bins(dv.double(), gt.double(), mask.double(), inverse)
+        i32, f32 = ref_losses.gt_bins(dv, gt, mask, inverse)
+        assert torch.equal(i64, i32) and torch.equal(f64, f32)
+
+        lg = _f64_leaf(inputs[k]["prob_volume_pre"])
+        loss = ref_losses.mixup_ce_loss_stage(lg, dv.double(), gt.double(), mask.double(), inverse, wo)
+        assert loss.dtype == torch.float64
+        loss.backward()
+        want, wg = float(go["%s_%s_mixup_loss" % (tag, k)]), go["%s_%s_mixup_grad" % (tag, k)]
+        assert abs(loss.item() - want) < 2e-6 * max(1.0, abs(want)), k
+        assert max_abs(lg.grad, wg) < 1e-6 * np.abs(wg).max(), k
+
+        for rng in (0, 1):
+            depth = _f64_leaf(t(go["%s_%s_reg_depth" % (tag, k)]))
+            loss = ref_losses.reg_loss_stage(depth, dv.double(), gt.double(), mask.double(), itv.double(), bool(rng), inverse, wo)
+            assert loss.dtype == torch.float64
+            loss.backward()
+            want, wg = float(go["%s_%s_reg%d_loss" % (tag, k, rng)]), go["%s_%s_reg%d_grad" % (tag, k, rng)]
+            assert abs(loss.item() - want) < 2e-6 * max(1.0, abs(want)), (k, rng)
+            # the recorded float32 run rounds depth / itv and gt / itv (each up to 2^-24 of ~600 / 2.5) BEFORE it subtracts them: inside
+            # the quadratic zone the gradient x / (itv N) carries that absolute error of x, i.e. 2^-23 max|depth / itv| of max|grad|
+            cancel = 2.0 ** -23 * (depth.detach() / itv.double().reshape(-1, 1, 1)).abs().max().item()
+            assert max_abs(depth.grad, wg) < (1e-6 + cancel) * np.abs(wg).max(), (k, rng)
+
+
+def test_wasserstein_oracle_fp64_path_vs_reference():
+    """ref_losses.sinkhorn_stage in float64 (nearest hypothesis from the float32 distances) against tests/golden/was_loss.npz, at the bound the
+    float32 oracle is held to."""
+    from oracle import ref_losses
+    gi, g = load_golden("ce_loss.npz"), load_golden("was_loss.npz")
+    for s, k in enumerate(("stage1", "stage2", "stage3", "stage4")):
+        prob = torch.softmax(torch.from_numpy(gi["inv_%s_logits" % k]), 1)             # the float32 values the golden run saw
+        p64 = _f64_leaf(prob)
+        dv, gt, mask = (torch.from_numpy(gi["inv_%s_%s" % (k, n)]) for n in ("depth_values", "gt", "mask"))
+        loss = ref_losses.sinkhorn_stage(p64, dv.double(), gt.double(), mask.double(), 10, 1.0, float(g["dlossw"][s]))
+        assert loss.dtype == torch.float64
+        loss.backward()
+        want, wg = float(g[k + "_loss"]), torch.from_numpy(g[k + "_grad"])
+        assert abs(loss.item() - want) < 2e-6 * max(1.0, abs(want)), k
+        assert (p64.grad - wg).abs().max() < 2e-5 * wg.abs().max(), k
+
+
+def test_loss_edge_cases_have_a_recorded_float32_deviation():
+    """tests/test_hip_loss_edges.py bounds each GPU case by max(golden-test tolerance, 4 x the recorded deviation of the float32 oracle from the
+    float64 oracle).  Every case has an entry, and the float32 oracle as it runs here stays within the bound the device is given."""
+    import test_hip_loss_edges as e
+    assert set(e.DEV32) == {e.case_id(c) for c in e.ALL_CASES} and len(e.DEV32) == len(e.ALL_CASES)
+    for cid, (dl, dg) in e.measure_dev32().items():
+        assert dl <= max(4 * e.DEV32[cid][0], 1e-9) and dg <= max(4 * e.DEV32[cid][1], 1e-9), (cid, dl, dg, e.DEV32[cid])
+
+
 def fpn_golden():
     g = load_golden("fpn_decoder.npz")
     sd = {k[3:]: t(v) for k, v in g.items() if k.startswith("sd.")}
