@@ -755,7 +755,8 @@ extern "C" int mvs_attention_x3(const float* qkv, const float* vt, float* out, i
 }
 
 extern "C" int mvs_layernorm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C, float eps, mvs_stream_t stream) {
-    MVS_REQUIRE(x && gamma && beta && y && rows >= 1 && C >= 1 && C <= 1024, "mvs_layernorm: rows >= 1, 1 <= C <= 1024 (got %d)", C);
+    MVS_REQUIRE(x && gamma && beta && y && rows >= 1 && rows < ((int64_t)1 << 31) && C >= 1 && C <= 1024,
+                "mvs_layernorm: rows >= 1, 1 <= C <= 1024 (got %d)", C);
     hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, MVS_STREAM(stream), x, gamma, beta, y, (int)rows, C, eps);
     return mvs::finish_launch("mvs_layernorm");
 }

@@ -1,6 +1,6 @@
 """The DINO ViT-small branch (csrc/vit.hip, mvsformer_amd/vit.py) on the GPU against the reference's own outputs
 (tests/golden/vit_small.npz, made by oracle/gen_golden.py::gen_vit from the real ``vits.vit_small`` + ``VITDecoderStage4Single``) and the
-primitive kernels against plain torch (CPU, fp64 where it matters)."""
+primitive kernels against plain torch (CPU, fp64 where it matters).  The primitives at tile and row edges, per slice: tests/test_hip_vit_edges.py."""
 import numpy as np
 import pytest
 import torch

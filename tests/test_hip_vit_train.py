@@ -1,7 +1,7 @@
 """Training mode of the DINO ViT-small branch ("fix": false; mvsformer_amd/vit.py ``_ViTTrainFn``, csrc/vit_train.hip, the A-transposed mode of
 ``mvs_gemm_x3``) on the GPU: each backward piece against fp64 torch autograd on the CPU and run twice for bitwise equality, the whole ViT's
 forward and parameter gradients against ``oracle/ref_vit.py`` in fp64, and ``DINOMVSNet`` with ``fix=False`` against the same model with
-``fix=True``."""
+``fix=True``.  The backward pieces at row, chunk and tile edges, per slice: tests/test_hip_vit_edges.py."""
 import copy
 
 import numpy as np
