@@ -14,7 +14,8 @@ from typing import Dict, List
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "mvs_hip.h")
 
-# kernel-name / launch-tag prefix -> the .hip file with the __global__ function (+ the headers it includes); first match wins
+# kernel-name / launch-tag prefix -> the .hip file with the __global__ function (+ the csrc/ headers it includes, directly or through another header:
+# tests/test_abi.py checks the lists against the #include lines); first match wins
 _RULES = [
     (r"^(cv_|nchw_to_nhwc|mvs_nchw_to_nhwc)", ["cost_volume.hip", "common.h", "geometry.h"]),
     (r"^(vis_x3|mvs_vis)", ["vis_net_x3.hip", "conv_common.h", "common.h", "split3.h"]),
@@ -22,20 +23,20 @@ _RULES = [
     (r"^x3_small", ["conv3d_x3_small.hip", "conv_common.h", "common.h", "split3.h"]),
     (r"^(x3_conv|x3_deconv|x3_pack|x3_deconv_pack)", ["conv3d_x3.hip", "conv_common.h", "common.h", "split3.h"]),
     (r"^conv3d_kernel", ["conv3d_fwd.hip", "conv_common.h", "common.h"]),
-    (r"^(deconv3d_kernel|prob3|prob1)", ["conv3d.hip", "conv_common.h", "common.h"]),
+    (r"^(deconv3d_kernel|prob3)", ["conv3d.hip", "conv_common.h", "common.h"]),
     (r"^pack_deconv_s1", ["deconv3d_s1.hip", "conv_common.h", "common.h"]),
-    (r"^(head_|init_inverse|schedule_inverse|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|mvs_conf)", ["head.hip", "common.h"]),
+    (r"^(head_|prob1_kernel|mvs_prob1_fwd|init_inverse|schedule_inverse|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|mvs_conf)", ["head.hip", "common.h"]),
     (r"^(proj_|mvs_proj)", ["proj.hip", "common.h"]),
-    (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^(fpn8_cp|mvs_fpn_level_cp)", ["fpn_cp.hip", "conv_common.h", "common.h", "split3.h"]),
+    (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h"]),
+    (r"^(fpn8_cp|mvs_fpn_level_cp)", ["fpn_cp.hip", "conv_common.h", "common.h", "split3.h", "prims.h"]),
     (r"^(conv2d_x3s|mvs_conv2d_x3s)", ["conv2d_x3s.hip", "conv_common.h", "common.h", "split3.h"]),
     (r"^(enc_x3|mvs_conv2d_x3)", ["conv2d_x3.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^(fpn8_x3|fpn_level_x3|mvs_fpn_level_x3)", ["fpn_x3.hip", "conv_common.h", "common.h", "split3.h"]),
+    (r"^(fpn8_x3|fpn_level_x3|mvs_fpn_level_x3)", ["fpn_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h"]),
     (r"^(layernorm_stats|layernorm_bwd|colsum|gelu_|attention_softmax_bwd|bicubic_bwd|mvs_layernorm_stats|mvs_layernorm_bwd|mvs_colsum|mvs_gelu|"
-     r"mvs_attention_softmax_bwd|mvs_bicubic_resize_bwd|vit_train)", ["vit_train.hip", "common.h"]),
-    (r"^(flash_train|mvs_attention_train)", ["vit_flash_train.hip", "common.h", "split3.h"]),
-    (r"^(x3p_|gemm_x3p|attention_x3p|layernorm_x3p|cls_attention)", ["vit_packed.hip", "common.h", "split3.h"]),
-    (r"^(x3_gemm|x3_attention|gemm_x3|attention_x3|layernorm|softmax_rows|bicubic)", ["vit.hip", "common.h", "geometry.h", "split3.h"]),
+     r"mvs_attention_softmax_bwd|mvs_bicubic_resize_bwd|vit_train)", ["vit_train.hip", "common.h", "prims.h"]),
+    (r"^(flash_train|mvs_attention_train)", ["vit_flash_train.hip", "common.h", "split3.h", "prims.h"]),
+    (r"^(x3p_|gemm_x3p|attention_x3p|layernorm_x3p|cls_attention)", ["vit_packed.hip", "common.h", "split3.h", "prims.h"]),
+    (r"^(x3_gemm|x3_attention|gemm_x3|attention_x3|layernorm|softmax_rows|bicubic)", ["vit.hip", "common.h", "geometry.h", "split3.h", "prims.h"]),
 ]
 
 

@@ -6,9 +6,10 @@
 // a Conv3d(8, 1, 1) with bias), StageNet.vis[3:5] (Conv2d(8, 1, 1) + Sigmoid, models/mvsformer_model.py:37); `select` (w = e0, no bias, no
 // parameter gradient) picks channel 0 of CostRegNet's 8 -> 1 `prob` convolution, which runs zero-padded to 8 output channels.
 #include "common.h"
+#include "prims.h"
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using mvsprim::bf16x8;
 constexpr int HEAD_ROWS = 1024;                              // voxels per block of the backward (4 per thread)
 
 __global__ __launch_bounds__(256) void bf16_head_fwd_kernel(const __bf16* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,

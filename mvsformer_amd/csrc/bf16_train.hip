@@ -19,20 +19,20 @@
 #include <vector>
 
 #include "common.h"
+#include "prims.h"
 #include "reduce_f64.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-constexpr unsigned OOB = 0x80000000u;
+using mvsprim::bf16x8;
+using mvsprim::bf16x4;
+using mvsprim::f32x4;
+using mvsprim::u32x4;
+using mvsprim::rsrc_t;
+using mvsprim::OOB;
+using mvsprim::make_rsrc;
+using mvsprim::resolve_count;
 
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
 __device__ __forceinline__ bf16x8 ld8(rsrc_t r, unsigned voff) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
@@ -739,9 +739,6 @@ __global__ __launch_bounds__(256) void bf16_affine_act_kernel(const __bf16* __re
 }
 
 // dx = gamma*invstd*(g - s1/n - xhat*s2/n), g = dy*[x*scale+shift > 0 or !relu]
-__device__ __forceinline__ double resolve_count(double count_host, const float* __restrict__ count_dev) {
-    return count_dev ? (double)count_dev[0] * 4096.0 + (double)count_dev[1] : count_host;
-}
 __global__ __launch_bounds__(256) void bf16_bn_bwd_apply_kernel(const __bf16* __restrict__ dy, const __bf16* __restrict__ x,
                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,

@@ -23,12 +23,13 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "prims.h"
 
 namespace {
 using namespace mvsconv;
 
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }   // v_pk_fma_f32
+using mvsprim::f32x2;
+using mvsprim::pk_fma;
 // a - b as ONE packed instruction: b * -1 + a (exact product, one rounding = a - b); the -1 comes out of an opaque asm so that the
 // optimizer cannot fold the fma back into the <2 x float> fsub the backend would split in two
 __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {

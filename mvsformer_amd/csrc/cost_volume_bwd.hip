@@ -10,17 +10,15 @@
 // the same non-determinism class as ATen's grid_sampler_2d_backward.
 #include "common.h"
 #include "geometry.h"
+#include "prims.h"
 
 namespace {
 
 constexpr int G = 8;
 constexpr int NW = 4;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
-__device__ __forceinline__ f32x4 buf_load4(mvs::rsrc_t r, unsigned voff_bytes) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, 0, 0));
-}
+using mvsprim::f32x4;
+using mvsprim::u32x4;
+using mvsprim::buf_load4;
 template <int LPP>
 __device__ __forceinline__ float pixel_sum(float v) {
 #pragma unroll

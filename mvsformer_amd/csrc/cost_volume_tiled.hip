@@ -30,12 +30,15 @@
 
 #include "common.h"
 #include "geometry.h"
+#include "prims.h"
 
 namespace {
 
 constexpr int G = 8;
 constexpr int NT = 256;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using mvsprim::f32x4;
+using mvsprim::buf_load4;
+using mvsprim::OOB;
 
 template <int C_, int TW_, int TH_, int S_, int DCL_, int CC_, int CAP_, int OCC_>
 struct TileCfg {
@@ -89,18 +92,14 @@ struct Args {
 __device__ __forceinline__ float buf_load1(mvs::rsrc_t r, unsigned voff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
 }
-__device__ __forceinline__ f32x4 buf_load4(mvs::rsrc_t r, unsigned voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
 __device__ __forceinline__ float buf_load1s(mvs::rsrc_t r, unsigned voff, unsigned soff) {     // soff must be wave-uniform
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 __device__ __forceinline__ f32x4 buf_load4s(mvs::rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
-// voffset of a masked-off load: with any soffset the address stays beyond every block (< 2 GiB each), so the buffer unit returns
+// OOB = voffset of a masked-off load: with any soffset the address stays beyond every block (< 2 GiB each), so the buffer unit returns
 // 0 without touching memory
-constexpr unsigned OOB = 0x80000000u;      // beyond any view block (< 2 GiB each): the buffer unit returns 0, no memory access
 
 // integer min / max across the 16 lanes of a DPP row; every lane of the row gets the result
 template <bool MAX>

@@ -19,6 +19,7 @@
 //
 // Algorithmic FLOPs per output pixel of level k: 2*64*(C_k + 9*C_k); bytes: 4*(C_k in + C_k out + 64/4 upsampled source).
 #include "conv_common.h"
+#include "prims.h"
 
 namespace {
 using namespace mvsconv;
@@ -35,10 +36,9 @@ __host__ __device__ constexpr int fpn_nt(int ck) { return ck == 32 ? 2 : 1; }
 __host__ __device__ constexpr int fpn_taps(int ck) { return ck == 8 ? 12 : 9; }
 __host__ __device__ constexpr int fpn_chunk_floats(int ck) { return 4 * fpn_taps(ck) * 4 * np_of(fpn_nt(ck)); }
 
-// x * sigmoid(x) with the hardware exp2 / reciprocal (a few ulp; the epilogue shares the fp32 pipe with the MFMAs, an IEEE divide costs 10 slots)
-__device__ __forceinline__ float swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }   // v_pk_fma_f32
+using mvsprim::f32x2;
+using mvsprim::pk_fma;
+using mvsprim::swish;
 
 // packed image: [slab = cin/4 (16)][tap (9 | 12)][cin%4][NP]; a chunk of 16 input channels = 4 consecutive slabs
 __global__ void fpn_pack_kernel(const float* __restrict__ w /*[Cout,64,3,3]*/, int Cout, float* __restrict__ out) {

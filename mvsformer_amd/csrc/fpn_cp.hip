@@ -17,6 +17,7 @@
 //   phase 2 one thread per fine pixel: 9 taps x 4 corners of P, BatchNorm shift (+ the bias' border correction), Swish, 32-byte store
 // The next tile's global loads are in flight during phase 2.
 #include "conv_common.h"
+#include "prims.h"
 #include "split3.h"
 
 // experiment builds only (make exp EXPFLAGS=-DFPNCP_TIMING): per-phase cycle totals of one block's wavefronts, printed by the launcher
@@ -29,6 +30,7 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsprim::swish;
 
 constexpr int FC = 64, CK = 8, T = 16, HT = T + 2;       // fine tile, with the 3x3 halo
 constexpr int WQ = 11, NQ = 128;                          // coarse window edge; q slots (121 used)
@@ -42,7 +44,6 @@ constexpr int L_BYTES = T * T * CK * 4;                   // lateral convolution
 constexpr int LDS_BYTES = B_BYTES + LAT_BYTES + L_BYTES + 512;
 constexpr int NW = 5 * 2 * 3, NWL = 3 * 3;                // weight fragments: contraction [M tile][K step][term], lateral [step][term]
 
-__device__ __forceinline__ float swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 // the block exchanges data through LDS only: no wait for global loads / stores at a barrier (__syncthreads() is a workgroup-scope release)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 

@@ -8,11 +8,13 @@
 // the weights arrive pre-split in MFMA fragment order (BatchNorm scale folded in) straight from L1/L2, one step ahead.  The intra map itself still
 // leaves as fp32 (NCHW for the next level of this kind, channel-last for fpn_cp.hip).  fp32 in / fp32 out, fp32-equivalent.
 #include "conv_common.h"
+#include "prims.h"
 #include "split3.h"
 
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsprim::swish;
 
 constexpr int FC = 64;
 constexpr int TH = 4, TW = 32;               // output tile
@@ -23,8 +25,6 @@ constexpr int CS = 208;                      // channel stride of the fp32 LDS t
 constexpr int SH = 6, SW = 20, SS = SH * SW; // LDS window of the coarser level
 constexpr int OCTB = CS * 16, TERMB = 2 * OCTB;   // split tile: [term][octet][pixel][16 B]
 constexpr int STEPS = 5;                     // 9 taps x 2 octets = 18 K blocks (+ 2 zero)
-
-__device__ __forceinline__ float swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 __device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);

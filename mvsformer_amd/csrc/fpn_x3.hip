@@ -19,6 +19,7 @@
 // Output rows come in pairs: M = (row parity, 8 channels), K = 4 input rows x 3 columns x channels (a quarter of the A operand is
 // structural zeros instead of half, as layer 3 of vis_net_x3.hip).
 #include "conv_common.h"
+#include "prims.h"
 #include "split3.h"
 
 #ifndef FPNX3_ABLATE
@@ -28,6 +29,7 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsprim::swish;
 
 constexpr int FC = 64, CK = 8;
 constexpr int TW = 16, HC = TW + 2;                   // strip width, with the halo
@@ -49,7 +51,6 @@ constexpr int UNITS = RB * HC * 4;                    // build units of a batch:
 constexpr int PASSES = (UNITS + 63) / 64;             // 5 (the last one half full)
 static_assert(WREG % 256 == 0 && OCT % 256 == 0, "bank alignment of the fragment reads");
 
-__device__ __forceinline__ float swish(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 // LDS traffic between the phases of ONE wavefront needs no barrier (a wavefront's DS instructions execute in order); this keeps the compiler
 // from moving accesses across the phase boundary and drains the queue
 __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }

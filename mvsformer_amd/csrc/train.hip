@@ -7,11 +7,13 @@
 // combined in a fixed order by a second tiny kernel (no float atomics: BatchNorm statistics repeat bit-exactly run to run,
 // which matters because the training head is an arg-max - a one-ulp change in a logit can move a whole hypothesis window).
 #include "common.h"
+#include "prims.h"
 #include "reduce_f64.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using mvsprim::f32x4;
+using mvsprim::resolve_count;
 constexpr int CHUNK = 4096;            // elements of one (b, c) row handled by a block (256 threads x 4 x 4)
 
 // Activation codes of the BatchNorm kernels' `relu` argument (0 / 1 keep their old meaning): 0 none, 1 ReLU (the 3-D regularizer and the
@@ -83,13 +85,6 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
         o[c] = s;
         o[C + c] = q;
     }
-}
-
-// Element count per channel: a host value, or (SyncBatchNorm) two floats {n / 4096, n % 4096} that rode through the same
-// all-reduce as the sums - each stays exactly representable in fp32 up to 2^36 elements, so the total is exact and the
-// host never has to read it back.
-__device__ __forceinline__ double resolve_count(double count_host, const float* __restrict__ count_dev) {
-    return count_dev ? (double)count_dev[0] * 4096.0 + (double)count_dev[1] : count_host;
 }
 
 // mean/var from the (possibly all-reduced) sums; eval-style scale/shift for the apply kernel; running-stat update

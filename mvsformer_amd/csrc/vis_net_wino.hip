@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "prims.h"
 
 namespace {
 using namespace mvsconv;
@@ -51,8 +52,8 @@ __global__ void vis_wino_prepare_kernel(const float* __restrict__ prm, float* __
     out[idx] = v;
 }
 
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }   // v_pk_fma_f32
+using mvsprim::f32x2;
+using mvsprim::pk_fma;
 // a - b in one packed instruction.  The backend has no packed fsub (a <2 x float> fsub is split into two v_sub_f32), so the
 // subtraction is spelled b * -1 + a: exact product, one rounding - bit-identical to a - b.
 // (The -1 comes out of an opaque asm so that the optimizer cannot fold the fma back into the fsub it would then split.)

@@ -16,11 +16,17 @@
 
 #include "common.h"
 #include "geometry.h"
+#include "prims.h"
 #include "split3.h"
 
 namespace {
 using mvsx3::bf16x8;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using mvsprim::f32x4;
+using mvsprim::buf_load4;
+using mvsprim::OOB;
+using mvsprim::cc1;
+using mvsprim::cc2;
+using mvsprim::gelu_erf;
 
 constexpr int BM = 64, BN = 64, BK = 32;
 constexpr int ROWB = BK * 2 + 16;                            // LDS bytes per tile row (32 bf16 + 16 bytes: rows 20 banks apart)
@@ -66,8 +72,6 @@ __device__ __forceinline__ float conv_elem(const GemmArgs& a, const float* __res
     if ((unsigned)iy >= (unsigned)a.cH || (unsigned)ix >= (unsigned)a.cW) return 0.0f;
     return base[((size_t)c * a.cH + iy) * a.cW + ix];
 }
-
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 // 8 consecutive k of row m of the A operand (zeros beyond M / K / the image)
 __device__ __forceinline__ void load_a8(const GemmArgs& a, const float* __restrict__ Ab, int m, int k0, int cls, float (&v)[8]) {
@@ -265,10 +269,6 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const GemmArgs a) {
 // so every wait is a full drain and a K step pays most of a global round trip: 18 % of the split-form rate.  Here every load is a
 // 16-byte buffer load whose out-of-range cases (rows beyond M / N, tiles beyond K) are OFFSETS beyond the descriptor - no branches, a
 // fixed number of loads per tile, so the wait before a tile's commit leaves the next tile's loads flying.
-__device__ __forceinline__ f32x4 buf_load4(mvs::rsrc_t r, unsigned voff_bytes) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, 0, 0));
-}
-
 __device__ __forceinline__ const float* uniform_ptr(const float* p) {
     const unsigned long long v = reinterpret_cast<unsigned long long>(p);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
@@ -279,7 +279,6 @@ template <int RT>
 __global__ __launch_bounds__(256) void gemm_x3_fast_kernel(const GemmArgs a) {
     using mvs::rsrc_t;
     constexpr int TERMA = RT * TERMB;
-    constexpr unsigned OOB = 0x80000000u;
     __shared__ __attribute__((aligned(16))) unsigned char lds[3 * TERMA + 3 * TERMB];
     unsigned char* tA = lds;
     unsigned char* tB = lds + 3 * TERMA;
@@ -452,7 +451,6 @@ __global__ __launch_bounds__(256, 4) void attention_x3_kernel(const float* __res
     // All loads are 16-byte BUFFER loads (keys beyond N / tiles beyond the last: offsets beyond the descriptor -> zeros): no branches, a
     // fixed number of loads per tile, so TWO tiles of loads can be in flight with counted waits (the scheduler's order is pinned below).
     const int kkey = tid >> 3, kd = (tid & 7) * 8, vd = tid >> 2, vk = (tid & 3) * 8;
-    constexpr unsigned OOB = 0x80000000u;
     const mvs::rsrc_t rk = mvs::make_rsrc(qrow, (unsigned)((size_t)N * 3 * C * 4));
     const mvs::rsrc_t rv = mvs::make_rsrc(vt + ((size_t)b * NH + h) * 64 * ldv, (unsigned)((size_t)64 * ldv * 4));
     const unsigned kbase = (unsigned)(((size_t)kkey * 3 * C + C + kd) * 4), vbase = (unsigned)(((size_t)vd * ldv + vk) * 4);
@@ -640,8 +638,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------------------------- bicubic resize
 // ATen upsample_bicubic2d, align_corners = False: src = (dst + 0.5) * rscale - 0.5, rscale = 1 / scale_factor when one was given (else
 // in / out - the caller passes whichever applies), taps floor(src) - 1 .. + 2 clamped to the image, cubic convolution with A = -0.75.
-__device__ __forceinline__ float cc1(float x) { return ((-0.75f + 2.0f) * x - (-0.75f + 3.0f)) * x * x + 1.0f; }
-__device__ __forceinline__ float cc2(float x) { return ((-0.75f * x - 5.0f * -0.75f) * x + 8.0f * -0.75f) * x - 4.0f * -0.75f; }
 __device__ __forceinline__ void cubic_coeffs(float t, float (&c)[4]) {
     c[0] = cc2(t + 1.0f), c[1] = cc1(t), c[2] = cc1(1.0f - t), c[3] = cc2(2.0f - t);
 }

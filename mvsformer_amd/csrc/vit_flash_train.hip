@@ -21,12 +21,13 @@
 // position 8 kb + 4 nt + r - so that chunk kb of a row is exactly the eight tokens a lane of group kb holds accumulators for.  16-byte chunks
 // are xor-swizzled against bank conflicts as in csrc/vit.hip.
 #include "common.h"
+#include "prims.h"
 #include "split3.h"
 
 namespace {
 using mvsx3::bf16x8;
 using mvsx3::Split3;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using mvsprim::f32x4;
 
 constexpr int FT_TOK = 32;                                   // tokens per LDS tile
 constexpr int FT_RTERM = FT_TOK * 128, FT_TTERM = 64 * 64;   // bytes of one term of a row-major / transposed tile

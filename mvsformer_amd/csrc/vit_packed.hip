@@ -23,22 +23,22 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "prims.h"
 #include "split3.h"
 
 namespace {
 using mvsx3::bf16x8;
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+using mvsprim::rsrc_t;
+using mvsprim::f32x4;
+using mvsprim::u32x4;
+using mvsprim::u32x2;
+using mvsprim::make_rsrc;
+using mvsprim::gelu_erf;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int PIECE = 1024;                                  // bytes of one fragment (16 rows x 32 k, one term)
 constexpr int KSTEP = 3 * PIECE;                             // the three terms of one (row tile, k step)
 
-__device__ __forceinline__ rsrc_t rsrc_of(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
 // LDS-DMA of the three terms of one (row tile, k step) - 3 KiB contiguous in memory AND in LDS: lane l moves 16 bytes from src + voff(l) +
 // soff (+ immediate) to lds_dst + 16 l (+ immediate).  The instruction's immediate offset is added to BOTH addresses, so one M0 (LDS base)
 // write serves the three pieces.  (In a __device__ helper on purpose: with the builtin directly in a __global__ template body hipcc drops the
@@ -51,7 +51,6 @@ __device__ __forceinline__ void dma16x3(rsrc_t src, unsigned char* lds_dst, unsi
 __device__ __forceinline__ bf16x8 ldfrag(rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, soff_bytes, 0));
 }
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 // four fp32 values -> three 8-byte words (4 bf16 each): the h, m, l terms
 __device__ __forceinline__ void split4(const float (&v)[4], u32x2& h, u32x2& m, u32x2& l) {
@@ -224,8 +223,8 @@ __global__ __launch_bounds__(NW * 64, (TI == 64 || NW == 8) ? 2 : 1) void gemm_x
     const int mb = (slot / a.nbn) * 8 + xcd, nb = slot % a.nbn;
     if (mb >= a.nbm) return;
     const int KS = a.K >> 5;
-    const rsrc_t rA = rsrc_of(a.Ap, (unsigned)((size_t)a.art * (MODE == 0 && a.a_mode ? a.Cp >> 5 : KS) * KSTEP));
-    const rsrc_t rB = rsrc_of(reinterpret_cast<const unsigned char*>(a.Bp) + (MODE == 0 ? (size_t)blockIdx.y * a.b_class_bytes : 0), (unsigned)((size_t)a.brt * KS * KSTEP));
+    const rsrc_t rA = make_rsrc(a.Ap, (unsigned)((size_t)a.art * (MODE == 0 && a.a_mode ? a.Cp >> 5 : KS) * KSTEP));
+    const rsrc_t rB = make_rsrc(reinterpret_cast<const unsigned char*>(a.Bp) + (MODE == 0 ? (size_t)blockIdx.y * a.b_class_bytes : 0), (unsigned)((size_t)a.brt * KS * KSTEP));
     // LDS-DMA roles: the stage's RTS row tiles are dealt to the wavefronts TPW at a time
     const unsigned voff = lane * 16;
     // implicit convolution: the pixel (image base row, y, x) of this lane's row in each activation row tile the wavefront fills
@@ -486,8 +485,8 @@ __global__ __launch_bounds__(256, 2) void attention_x3p_kernel(const void* __res
     const size_t bh = (size_t)img * NH + head;
     const unsigned char* kbase = reinterpret_cast<const unsigned char*>(Kp) + bh * RT * 2 * KSTEP;
     const unsigned char* vbase = reinterpret_cast<const unsigned char*>(Vp) + bh * 4 * KSV * KSTEP;
-    const rsrc_t rq = rsrc_of(reinterpret_cast<const unsigned char*>(Qp) + bh * RT * 2 * KSTEP, (unsigned)((size_t)RT * 2 * KSTEP));
-    const rsrc_t rk = rsrc_of(kbase, (unsigned)((size_t)RT * 2 * KSTEP)), rv = rsrc_of(vbase, (unsigned)((size_t)4 * KSV * KSTEP));
+    const rsrc_t rq = make_rsrc(reinterpret_cast<const unsigned char*>(Qp) + bh * RT * 2 * KSTEP, (unsigned)((size_t)RT * 2 * KSTEP));
+    const rsrc_t rk = make_rsrc(kbase, (unsigned)((size_t)RT * 2 * KSTEP)), rv = make_rsrc(vbase, (unsigned)((size_t)4 * KSV * KSTEP));
     const unsigned voff = lane * 16;
     const int qt0 = blockIdx.x * 8 + wave * 2;                // the wavefront's two query tiles (tiles >= RT read zeros, store nothing)
 

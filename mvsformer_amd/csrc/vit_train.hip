@@ -13,8 +13,11 @@
 //   mvs_bicubic_resize_bwd    the adjoint of mvs_bicubic_resize in gather form (two separable passes, each output element sums its own taps
 //                             in a fixed order)
 #include "common.h"
+#include "prims.h"
 
 namespace {
+using mvsprim::cc1;
+using mvsprim::cc2;
 
 // ---------------------------------------------------------------------------------------------------------------- LayerNorm
 // One wavefront per row (C <= 1024), the arithmetic of csrc/vit.hip layernorm_kernel.
@@ -163,8 +166,6 @@ __global__ __launch_bounds__(256) void attention_softmax_bwd_kernel(const float*
 // The forward's taps (csrc/vit.hip bicubic_kernel): output o reads inputs clamp(floor(s) - 1 + t, 0, In - 1), t = 0..3, s = (o + 0.5) * r - 0.5,
 // weights cubic_coeffs(s - floor(s)).  An interior input i is read only by outputs with floor(s) in [i - 2, i + 1]; the edge inputs also
 // receive the clamped taps, so their range runs to the end of the axis.  Each output of the adjoint sums its contributions in order of o.
-__device__ __forceinline__ float cc1(float x) { return ((-0.75f + 2.0f) * x - (-0.75f + 3.0f)) * x * x + 1.0f; }
-__device__ __forceinline__ float cc2(float x) { return ((-0.75f * x - 5.0f * -0.75f) * x + 8.0f * -0.75f) * x - 4.0f * -0.75f; }
 
 // weight of input i in output o along one axis
 __device__ __forceinline__ float tap_weight(int o, int i, float r, int In) {

@@ -315,3 +315,43 @@ def test_counter_traffic_evidence_matches_the_kernel_sources():
         assert k in tj["kernels"], k
         assert all(os.path.exists(os.path.join(_sources.CSRC, f)) for f in _sources.files_of(k))
     assert len(_sources.files_of("vis_x3_kernel")) < 6          # a known kernel maps to ITS files, not to all of csrc/
+
+
+def _project_includes(path, seen=None):
+    """Project headers (paths relative to csrc/) that the file at csrc/<path> pulls in with #include "...", transitively."""
+    from mvsformer_amd import _sources
+    seen = set() if seen is None else seen
+    here = os.path.dirname(path)
+    for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(_sources.CSRC, path)).read(), flags=re.M):
+        rel = os.path.normpath(os.path.join(here, inc))
+        if rel not in seen:
+            seen.add(rel)
+            _project_includes(rel, seen)
+    return seen
+
+
+def test_source_rules_list_every_included_header_and_find_every_kernel():
+    """mvsformer_amd/_sources.py by hand-written rule against the sources themselves: (1) a rule lists every header of csrc/ its .hip file
+    includes, directly or through another header - a header missing from a rule would let an edit to it pass as "kernel unchanged";
+    (2) every kernel of profiles/traffic_by_kernel.json resolves to the .hip file that holds its definition: the __global__ function of
+    that name, or - for the launch tags of mvsformer_amd/ops.py, which bench.py reports under - the extern "C" entry point (named by the
+    tag itself, or called by the ops.py function that writes the tag) whose kernels the launch runs."""
+    from mvsformer_amd import _sources
+    assert "prims.h" in _sources.file_digests()
+    for pat, files in _sources._RULES:
+        hip = [f for f in files if f.endswith(".hip")]
+        assert len(hip) == 1 and files[0] == hip[0], pat
+        want = {f for f in _project_includes(hip[0]) if not f.startswith("..")}          # within csrc/
+        assert want <= {os.path.normpath(f) for f in files[1:]}, (hip[0], sorted(want - {os.path.normpath(f) for f in files[1:]}))
+    src = {f: open(os.path.join(_sources.CSRC, f)).read() for f in os.listdir(_sources.CSRC) if f.endswith(".hip")}
+    tj = json.load(open(os.path.join(REPO, "profiles", "traffic_by_kernel.json")))
+    n_rules = max(len(files) for _, files in _sources._RULES)
+    ops_defs = re.split(r"^def ", open(os.path.join(REPO, "mvsformer_amd", "ops.py")).read(), flags=re.M)
+    for k in tj["kernels"]:
+        base = re.match(r"\w+", k).group(0)
+        holders = {f for f, s in src.items() if re.search(r"__global__(?:\s+__launch_bounds__\((?:[^()]|\([^()]*\))*\))?\s+void\s+%s\s*\(" % base, s)}
+        entries = [base] + [e for body in ops_defs if re.search(r'"%s\b' % base, body) for e in re.findall(r'_call\(\s*"(mvs_\w+)"', body)]
+        holders = holders or {f for f, s in src.items() for e in entries if re.search(r'extern "C"[^;{(]*\b%s\s*\(' % e, s)}
+        assert holders, "%s: no __global__ or extern \"C\" function of that name in csrc/" % k
+        files = _sources.files_of(k)
+        assert len(files) <= n_rules and files[0] in holders, (k, files[0], sorted(holders))
