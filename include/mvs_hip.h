@@ -13,7 +13,9 @@
  *     layout given in brackets).  Nothing is allocated or freed; scratch comes in as a caller workspace.
  *   - launches are asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream); the
  *     device is the caller's current HIP device.  No global mutable state beyond two per-device caches (the CU count, "dynamic LDS
- *     limit already raised for this kernel"): re-entrant across streams, threads and devices.
+ *     limit already raised for this kernel") and the values of the diagnostic environment knobs that are read once per process
+ *     (README.md, "Environment knobs of libmvs_hip.so": each knob's name, default, meaning and whether it is read once or per call):
+ *     re-entrant across streams, threads and devices.
  *   - Arithmetic.  Data is fp32 in, fp32 out (the reference forces fp32 for the cost volume, mvsformer_model.py:65-78).  Sweeps,
  *     heads, schedulers, filters and the `mvs_conv3d_fwd` / `mvs_deconv3d_fwd` family compute in IEEE fp32 (VALU / fp32 MFMA); the two
  *     entry points that also offer a shortcut form (reciprocal instead of IEEE division, hardware exp2/log2) say so at their `flags`

@@ -12,31 +12,31 @@ import re
 from typing import Dict, List
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "mvs_hip.h")
+PUB = "../../include/mvs_hip.h"          # the public header as common.h includes it: a path from csrc/, so no file name inside csrc/ can collide with it
 
 # kernel-name / launch-tag prefix -> the .hip file with the __global__ function (+ the csrc/ headers it includes, directly or through another header:
 # tests/test_abi.py checks the lists against the #include lines); first match wins
 _RULES = [
-    (r"^(cv_|nchw_to_nhwc|mvs_nchw_to_nhwc)", ["cost_volume.hip", "common.h", "geometry.h"]),
-    (r"^(vis_x3|mvs_vis)", ["vis_net_x3.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^(x3_tail|tail_x3)", ["tail_x3.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^x3_small", ["conv3d_x3_small.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^(x3_conv|x3_deconv|x3_pack|x3_deconv_pack)", ["conv3d_x3.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^conv3d_kernel", ["conv3d_fwd.hip", "conv_common.h", "common.h"]),
-    (r"^(deconv3d_kernel|prob3)", ["conv3d.hip", "conv_common.h", "common.h"]),
-    (r"^pack_deconv_s1", ["deconv3d_s1.hip", "conv_common.h", "common.h"]),
-    (r"^(head_|prob1_kernel|mvs_prob1_fwd|init_inverse|schedule_inverse|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|mvs_conf)", ["head.hip", "common.h"]),
-    (r"^(proj_|mvs_proj)", ["proj.hip", "common.h"]),
-    (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h"]),
-    (r"^(fpn8_cp|mvs_fpn_level_cp)", ["fpn_cp.hip", "conv_common.h", "common.h", "split3.h", "prims.h"]),
-    (r"^(conv2d_x3s|mvs_conv2d_x3s)", ["conv2d_x3s.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^(enc_x3|mvs_conv2d_x3)", ["conv2d_x3.hip", "conv_common.h", "common.h", "split3.h"]),
-    (r"^(fpn8_x3|fpn_level_x3|mvs_fpn_level_x3)", ["fpn_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h"]),
+    (r"^(cv_|nchw_to_nhwc|mvs_nchw_to_nhwc)", ["cost_volume.hip", "common.h", "geometry.h", "prims.h", PUB]),
+    (r"^(vis_x3|mvs_vis)", ["vis_net_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(x3_tail|tail_x3)", ["tail_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^x3_small", ["conv3d_x3_small.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(x3_conv|x3_deconv|x3_pack|x3_deconv_pack)", ["conv3d_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^conv3d_kernel", ["conv3d_fwd.hip", "conv_common.h", "common.h", "prims.h", PUB]),
+    (r"^(deconv3d_kernel|prob3)", ["conv3d.hip", "conv_common.h", "common.h", "prims.h", PUB]),
+    (r"^pack_deconv_s1", ["deconv3d_s1.hip", "conv_common.h", "common.h", "prims.h", PUB]),
+    (r"^(head_|prob1_kernel|mvs_prob1_fwd|init_inverse|schedule_inverse|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|mvs_conf)", ["head.hip", "common.h", PUB]),
+    (r"^(proj_|mvs_proj)", ["proj.hip", "common.h", PUB]),
+    (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(fpn8_cp|mvs_fpn_level_cp)", ["fpn_cp.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(conv2d_x3s|mvs_conv2d_x3s)", ["conv2d_x3s.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(enc_x3|mvs_conv2d_x3)", ["conv2d_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(fpn8_x3|fpn_level_x3|mvs_fpn_level_x3)", ["fpn_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
     (r"^(layernorm_stats|layernorm_bwd|colsum|gelu_|attention_softmax_bwd|bicubic_bwd|mvs_layernorm_stats|mvs_layernorm_bwd|mvs_colsum|mvs_gelu|"
-     r"mvs_attention_softmax_bwd|mvs_bicubic_resize_bwd|vit_train)", ["vit_train.hip", "common.h", "prims.h"]),
-    (r"^(flash_train|mvs_attention_train)", ["vit_flash_train.hip", "common.h", "split3.h", "prims.h"]),
-    (r"^(x3p_|gemm_x3p|attention_x3p|layernorm_x3p|cls_attention)", ["vit_packed.hip", "common.h", "split3.h", "prims.h"]),
-    (r"^(x3_gemm|x3_attention|gemm_x3|attention_x3|layernorm|softmax_rows|bicubic)", ["vit.hip", "common.h", "geometry.h", "split3.h", "prims.h"]),
+     r"mvs_attention_softmax_bwd|mvs_bicubic_resize_bwd|vit_train)", ["vit_train.hip", "common.h", "prims.h", PUB]),
+    (r"^(flash_train|mvs_attention_train)", ["vit_flash_train.hip", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(x3p_|gemm_x3p|attention_x3p|layernorm_x3p|cls_attention)", ["vit_packed.hip", "common.h", "split3.h", "prims.h", PUB]),
+    (r"^(x3_gemm|x3_attention|gemm_x3|attention_x3|layernorm|softmax_rows|bicubic)", ["vit.hip", "common.h", "geometry.h", "split3.h", "prims.h", PUB]),
 ]
 
 
@@ -46,7 +46,7 @@ def files_of(kernel: str) -> List[str]:
     for pat, files in _RULES:
         if re.match(pat, name):
             return list(files)
-    return sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
+    return sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [PUB]
 
 
 def file_digests() -> Dict[str, str]:
@@ -55,6 +55,7 @@ def file_digests() -> Dict[str, str]:
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".h")):
             out[f] = hashlib.sha256(open(os.path.join(CSRC, f), "rb").read()).hexdigest()[:16]
+    out[PUB] = hashlib.sha256(open(os.path.join(CSRC, PUB), "rb").read()).hexdigest()[:16]
     return out
 
 

@@ -791,7 +791,7 @@ bool chan_ok(int c) { return c == 8 || c == 16 || c == 32 || c == 64; }
 // per block that traffic is what bounds a larger launch: measured per call (tools/exp_small_conv.py, 64 -> 64 stride 1), split / not split:
 // 256 items 14 / 37 us, 512 items 28 / 39 us, 1024 items 53 / 41 us (32 -> 64 stride (1,2,2): 11 / 21, 21 / 22, 41 / 24 us).
 bool conv_ksplit(int cin, int items, int taps) {
-    static const int lim = [] { const char* e = getenv("MVS_BF16_KSPLIT_ITEMS"); return e ? atoi(e) : 768; }();
+    static const int lim = mvs::env_int("MVS_BF16_KSPLIT_ITEMS", 768);
     return taps == 27 && cin >= 32 && items <= lim;
 }
 
@@ -1003,7 +1003,7 @@ WgradPlan wgrad_plan(int nbatch, int CA, int CB, int Dp, int Hp, int Wp, int shw
     p.npc = (Wp + WG_PW - 1) / WG_PW;
     // two resident blocks per CU over all channel groups (three for the single-tile instance was measured: no faster, and every block
     // writes a slab the reduce kernel reads back)
-    static const int gblocks = [] { const char* e = getenv("MVS_WGRAD_GROUP_BLOCKS"); return e ? atoi(e) : 0; }();       // diagnostics
+    static const int gblocks = mvs::env_int("MVS_WGRAD_GROUP_BLOCKS", 0);       // diagnostics
     const int target = (grouped ? (gblocks > 0 ? gblocks : p.TA * p.TB == 1 ? 256 : 128) : 512) / p.gy;
     p.nseg = wgrad_nseg(nbatch * p.npr * p.npc, Dp, target);
     p.dseg = (Dp + p.nseg - 1) / p.nseg;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include "../../include/mvs_hip.h"
 
@@ -33,6 +34,11 @@ void launch_partials_reduce_grouped(const float* part, int bps, int nsamples, in
 int device_cus();                                              // compute units of the current device (256 on MI355X)
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for `func`, once per (function, device); MVS_OK or a negative error with set_error()
 int ensure_dynamic_lds(const void* func, int bytes, const char* who);
+
+// The environment knobs (README.md, "Environment knobs") are read through these two and nowhere else.  Neither caches: a knob that is read
+// once per process keeps the result in a `static` at its site, the others are read on every call.
+inline const char* env_str(const char* name) { return getenv(name); }                                              // nullptr when unset
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }    // atoi: "" and text give 0
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }

@@ -19,6 +19,9 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsx3::mfma6;
+using mvsprim::u32x2;
+using mvsprim::u32x4;
 
 constexpr int TW = 16, RB = 4, STEPS = 8, CO = 8;
 
@@ -37,16 +40,6 @@ struct Enc {
     static constexpr int PASSES = (UNITS + 63) / 64;                 // 2
     static constexpr int PRO = KS == 7 ? 2 : 1;                      // prologue builds (2P rows in chunks of four)
 };
-
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[0], c, 0, 0, 0);
-    return c;
-}
 
 // prepared[(step * 3 + term)][lane][8]: the MFMA A operand, lane = kb * 16 + m, m = (dy = m >> 3, co = m & 7), K block t = 4 * step + kb; the
 // folded BatchNorm scale of the output channel is multiplied in before the split.
@@ -138,7 +131,6 @@ __global__ __launch_bounds__(256, 2) void enc_x3_kernel(const float* __restrict_
             slot = slot >= RINGN ? slot - RINGN : slot;
             unsigned char* dst = ring + slot * ROWB + (smeta[p] & 0xffffu);
             if constexpr (KS == 5) {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                 u32x4 th, tm, tl;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -150,7 +142,6 @@ __global__ __launch_bounds__(256, 2) void enc_x3_kernel(const float* __restrict_
                 *reinterpret_cast<u32x4*>(dst + TERM) = tm;
                 *reinterpret_cast<u32x4*>(dst + 2 * TERM) = tl;
             } else {
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 u32x2 th, tm, tl;
                 unsigned xh, xm, xl;
                 mvsx3::split3_pair<true>(sreg[p][0], sreg[p][1], xh, xm, xl);

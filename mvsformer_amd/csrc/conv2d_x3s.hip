@@ -13,20 +13,12 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsx3::mfma6;
+using mvsprim::u32x4;
 
 constexpr int TH = 4, TW = 32, HR = TH + 2, HC = TW + 2, NPIX = HR * HC;   // 204 halo pixels <= 256 threads
 constexpr int CS = 208;                                                    // pixel slots of the split tile
 constexpr int OCTB = CS * 16, TERMB = 2 * OCTB, STEPS = 5;
-
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[0], c, 0, 0, 0);
-    return c;
-}
 
 // prepared[(((chunk * STEPS + step) * NT + nt) * 3 + term)][lane][8]: the MFMA A operand, lane = kb * 16 + m: output channel 16 nt + m,
 // K block t = 4 step + kb = (tap = t / 2, octet = t % 2) (t >= 18: zero), input channel 16 chunk + 8 octet + e; scale[co] multiplied in
@@ -74,7 +66,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_x3s_kernel(const float* __restr
         if (p < NPIX) {
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                 u32x4 th, tm, tl;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

@@ -100,7 +100,6 @@ __global__ __launch_bounds__(256) void deconv3d_kernel(const float* __restrict__
 
     constexpr int RPW = (CC * ID * IH + NWAVES - 1) / NWAVES;
     constexpr int NWV = ((CC / 4) * WSLAB / 4 + 255) / 256;
-    constexpr unsigned OOB = 0x80000000u;
     static_assert(IW <= 64, "one load per row per lane");
     float sreg[RPW];
     f32x4 wreg[NWV];
@@ -437,8 +436,7 @@ extern "C" int mvs_prob3_fwd(const float* x, const float* w, int B, int C, int D
         const int pd = waves1 >= 4 * 2048 ? 4 : (waves1 >= 2 * 2048 ? 2 : 1);
         // four consecutive rows per block: their wavefronts share 2 of every 3 input rows through the CU's L1 (one row per block sent
         // every row to the L2 three times - the kernel ran at the L2's rate: 43 us for a 57 MB volume); MVS_PROB3_ROWS overrides
-        const char* e = getenv("MVS_PROB3_ROWS");
-        const int rows = e ? atoi(e) : 4;
+        const int rows = mvs::env_int("MVS_PROB3_ROWS", 4);
         MVS_REQUIRE(rows == 1 || rows == 2 || rows == 4, "MVS_PROB3_ROWS must be 1, 2 or 4");
         dim3 grid(mvs::ceil_div(W / 4, 64), mvs::ceil_div(H, rows), B * mvs::ceil_div(D, pd)), block(64, rows);
         MVS_REQUIRE((int64_t)B * mvs::ceil_div(D, pd) <= 65535, "mvs_prob3_fwd: bad shape");

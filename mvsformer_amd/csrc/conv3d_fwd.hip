@@ -225,7 +225,7 @@ int dispatch_tile(const ConvArgs& a) {
     auto blocks = [&](int td, int th, int tw) {
         return (long)mvs::ceil_div(a.Wo, tw) * mvs::ceil_div(a.Ho, th) * mvs::ceil_div(a.Do, td) * a.B;
     };
-    static const char* force = getenv("MVS_CONV_TILE");     // tuning knob for tools/bench_conv.py: 42 | 22 | 22s
+    static const char* force = mvs::env_str("MVS_CONV_TILE");     // tuning knob for tools/bench_conv.py: 42 | 22 | 22s
     if (force) {
         if constexpr (SD == 1) { if (!strcmp(force, "42") && a.Do >= 3) return launch<NTF, NP, SD, SHW, 4, 2, 4>(a); }
         if (!strcmp(force, "22")) return launch<NTF, NP, SD, SHW, 2, 2, 4>(a);

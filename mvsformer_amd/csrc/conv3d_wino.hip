@@ -292,8 +292,7 @@ extern "C" int mvs_conv3d_wino_fwd(const float* x, const float* wpacked, const f
                 H, W);
     hipStream_t s = MVS_STREAM(stream);
     // all output channels in one block up to 32 (128 accumulator registers); 48/64 channels split over blocks
-    const char* env = getenv("MVS_WINO_NT");
-    const int nt = (env && atoi(env) == 2 && Cout % 32 == 0) ? 2 : 1;
+    const int nt = (mvs::env_int("MVS_WINO_NT", 0) == 2 && Cout % 32 == 0) ? 2 : 1;
     MVS_REQUIRE((int64_t)B * mvs::ceil_div(H, 8) <= 65535 && mvs::ceil_div(W, 32) <= 65535, "mvs_conv3d_wino_fwd: grid limit");
     if (nt == 2) return launch_wino<2>(x, wpacked, scale, shift, residual, y, B, Cin, Cout, D, H, W, relu, s);
     return launch_wino<1>(x, wpacked, scale, shift, residual, y, B, Cin, Cout, D, H, W, relu, s);

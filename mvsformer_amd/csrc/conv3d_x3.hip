@@ -40,10 +40,7 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
-
-__device__ __forceinline__ float stage_load(rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff_bytes, soff_bytes, X3_STAGE_AUX));
-}
+using mvsprim::stage_load;
 using mvsx3::Split3;
 using mvsx3::split3;
 
@@ -285,7 +282,7 @@ __global__ __launch_bounds__(256, Cfg::MIN_BLOCKS) void x3_conv_kernel(const X3A
     auto issue = [&](int it, int pp, int cc) {
         const size_t base = (size_t)(cc * CK) * DHW + (size_t)pp * HW;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) pre[it][e] = stage_load(xin, voff[it], (unsigned)((base + (size_t)e * DHW) * 4));
+        for (int e = 0; e < 8; ++e) pre[it][e] = stage_load<X3_STAGE_AUX>(xin, voff[it], (unsigned)((base + (size_t)e * DHW) * 4));
     };
     auto commit = [&]() {
 #pragma unroll
@@ -671,7 +668,7 @@ __global__ __launch_bounds__(256, 2) void x3_deconv_kernel(const X3Args a) {
 #pragma unroll
                 for (int it = 0; it < NI; ++it)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) pre[it][e] = stage_load(xin, voff[it], (unsigned)((base + (size_t)e * DHW) * 4));
+                    for (int e = 0; e < 8; ++e) pre[it][e] = stage_load<X3_STAGE_AUX>(xin, voff[it], (unsigned)((base + (size_t)e * DHW) * 4));
             }
             __syncthreads();
 #pragma unroll
@@ -745,10 +742,7 @@ bool x3_plan(int Cin, int Cout, int sd, int shw, X3Plan* pl) {
 // three-blocks-per-CU instances (conv1, conv2) keep the old bound (conv2 at stage 3: 0.081 split in two against 0.086 unsplit).
 // MVS_X3_SEG_BLOCKS overrides both (diagnostics).
 int seg_blocks(int blocks_per_cu) {
-    static const int env = [] {
-        const char* e = getenv("MVS_X3_SEG_BLOCKS");
-        return e ? std::max(1, atoi(e)) : 0;
-    }();
+    static const int env = mvs::env_str("MVS_X3_SEG_BLOCKS") ? std::max(1, mvs::env_int("MVS_X3_SEG_BLOCKS", 0)) : 0;
     return env ? env : (blocks_per_cu >= 3 ? 1536 : 384);
 }
 

@@ -358,7 +358,7 @@ extern "C" int mvs_conv3d_small_fwd(const float* x, const void* wpacked, const f
     // K split over a block's four wavefronts where an item is a long serial chain (>= 16 steps: 32 / 64 input channels) and the items
     // alone would not fill the chip anyway
     const int KQ = Cin / 8, nsteps = transposed ? steps_of(8 * KQ) : steps_of(27 * KQ);
-    static const char* env = getenv("MVS_SMALL_KSPLIT");   // diagnostics: 0 = never, 1 = always
+    static const char* env = mvs::env_str("MVS_SMALL_KSPLIT");   // diagnostics: 0 = never, 1 = always
     const bool split = env ? atoi(env) != 0 : (nsteps >= 16 && items <= 16384);
     if (split) {
         const dim3 grid((unsigned)items);

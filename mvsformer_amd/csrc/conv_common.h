@@ -1,23 +1,17 @@
 // Shared pieces of the fp32-MFMA 3-D convolution kernels (conv3d_fwd.hip, conv3d.hip).
 #pragma once
 #include "common.h"
+#include "prims.h"
 
 namespace mvsconv {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using rsrc_t = __amdgpu_buffer_rsrc_t;
+using mvsprim::f32x4;
+using mvsprim::rsrc_t;
+using mvsprim::OOB;
+using mvsprim::make_rsrc;
+using mvsprim::buf_load;
 
 constexpr int NWAVES = 4;
-constexpr unsigned OOB = 0x80000000u;     // buffer offset beyond every descriptor range used here => load returns 0
-
-// wave-uniform buffer descriptor: loads beyond `bytes` (or with OOB as offset) return 0, which is how zero padding,
-// the tile halo outside the volume and channel padding are produced without branches
-__device__ __forceinline__ rsrc_t make_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float buf_load(rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff_bytes, soff_bytes, 0));
-}
 
 constexpr int np_of(int NT) { return NT == 1 ? 16 : (NT == 2 ? 48 : 80); }   // packed cout row, == 16 (mod 32)
 constexpr int pad_cs(int raw, int shw) {

@@ -36,22 +36,15 @@ namespace {
 
 constexpr int G = 8;
 constexpr int NW = 4;                         // wavefronts per block
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
-__device__ __forceinline__ f32x4 buf_load4(mvs::rsrc_t r, unsigned voff_bytes) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, 0, 0));
-}
+using mvsprim::f32x4;
+using mvsprim::u32x4;
+using mvsprim::buf_load4;
+using mvsprim::dpp_add;
 
 // Cross-lane sums over the LPP lanes of a pixel as DPP row operations (full-rate VALU, no LDS crossbar traffic; the
 // ds_bpermute form of __shfl_xor was ~25 LDS-path instructions per gather step in the similarity branch).
 //   quad_perm xor 1 / xor 2, then row_half_mirror (i <-> 7-i) and row_mirror (i <-> 15-i): valid as "xor 4 / xor 8"
 //   partners because after the quad steps all 4 lanes of a quad already hold the same partial sum.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true);
-    return v + __builtin_bit_cast(float, o);
-}
 constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140, DPP_ROR4 = 0x124, DPP_ROR8 = 0x128;
 
 // sum over the LPP lanes of a pixel (lanes pixel*LPP .. pixel*LPP+LPP-1); every lane gets the total

@@ -22,14 +22,10 @@
 
 namespace {
 using namespace mvsconv;
+using mvsprim::dpp_add;
 
 // sum over the 8 lanes of an aligned group (every lane gets the total): quad_perm xor 1, xor 2, then row_half_mirror
 // (i <-> 7-i), which pairs the two quads once each quad holds its own sum
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true);
-    return v + __builtin_bit_cast(float, o);
-}
 __device__ __forceinline__ float group8_sum(float v) {
     v = dpp_add<0xB1>(v);
     v = dpp_add<0x4E>(v);

@@ -30,6 +30,7 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsx3::mfma6;
 using mvsprim::swish;
 
 constexpr int FC = 64, CK = 8, T = 16, HT = T + 2;       // fine tile, with the 3x3 halo
@@ -46,16 +47,6 @@ constexpr int NW = 5 * 2 * 3, NWL = 3 * 3;                // weight fragments: c
 
 // the block exchanges data through LDS only: no wait for global loads / stores at a barrier (__syncthreads() is a workgroup-scope release)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[0], c, 0, 0, 0);
-    return c;
-}
 
 // prepared[frag][lane][8], lane = kb * 16 + m; the BatchNorm scale of the output channel is multiplied in before the split
 //   frag < 30: (M tile mt, K step ks, term): row idx = 16 mt + m = (tap = idx / 8, co = idx % 8) (idx >= 72: zero), channel 32 ks + 8 kb + e

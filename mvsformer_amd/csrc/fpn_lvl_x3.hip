@@ -14,6 +14,8 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsx3::mfma6;
+using mvsprim::u32x4;
 using mvsprim::swish;
 
 constexpr int FC = 64;
@@ -25,16 +27,6 @@ constexpr int CS = 208;                      // channel stride of the fp32 LDS t
 constexpr int SH = 6, SW = 20, SS = SH * SW; // LDS window of the coarser level
 constexpr int OCTB = CS * 16, TERMB = 2 * OCTB;   // split tile: [term][octet][pixel][16 B]
 constexpr int STEPS = 5;                     // 9 taps x 2 octets = 18 K blocks (+ 2 zero)
-
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[0], c, 0, 0, 0);
-    return c;
-}
 
 // prepared[(((chunk * STEPS + step) * NT + nt) * 3 + term)][lane][8]: the MFMA A operand, lane = kb * 16 + m: output channel 16 nt + m,
 // K block t = 4 step + kb = (tap = t / 2, octet = t % 2) (t >= 18: zero), channel 16 chunk + 8 octet + e; scale[co] multiplied in
@@ -171,7 +163,6 @@ __global__ __launch_bounds__(256, (CK == 32 ? 2 : 3)) void fpn_level_x3s_kernel(
             }
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                 u32x4 th, tm, tl;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

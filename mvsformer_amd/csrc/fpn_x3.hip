@@ -29,6 +29,9 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
+using mvsx3::mfma6;
+using mvsprim::u32x2;
+using mvsprim::u32x4;
 using mvsprim::swish;
 
 constexpr int FC = 64, CK = 8;
@@ -79,16 +82,6 @@ __global__ void fpn8_x3_prepare_kernel(const float* __restrict__ w3 /*[8,64,3,3]
         v[e] = mvsx3::split3_term(f, term);
     }
     out[idx] = v;
-}
-
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[0], c, 0, 0, 0);
-    return c;
 }
 
 __global__ __launch_bounds__(256, 2) void fpn8_x3_kernel(const float* __restrict__ prev /*[N,64,h,w]*/, const float* __restrict__ lat /*[N,8,2h,2w]*/,
@@ -157,7 +150,6 @@ __global__ __launch_bounds__(256, 2) void fpn8_x3_kernel(const float* __restrict
     };
     auto lat_commit = [&]() {
         if (lane < 2 * HC) {
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             u32x4 th, tm, tl;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -233,7 +225,6 @@ __global__ __launch_bounds__(256, 2) void fpn8_x3_kernel(const float* __restrict
                 int slot4 = 4 * slot0 + (int)(bB[p] >> 16 & 15u);
                 slot4 = slot4 >= 4 * RING ? slot4 - 4 * RING : slot4;
                 unsigned char* dst = ring + (bB[p] & 0xffffu) + slot4 * (ROWB / 4);
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 u32x2 th, tm, tl;
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {

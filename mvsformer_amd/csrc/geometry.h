@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "prims.h"
+
 namespace mvs {
 
 struct Taps {
@@ -109,15 +111,9 @@ __device__ __forceinline__ Taps sweep_taps_fast(const float* __restrict__ rt, fl
 // offset goes in the 32-bit voffset, the channel plane (c*H*W*4 bytes) in the scalar soffset, so a gather
 // costs no 64-bit address arithmetic and the compiler issues a whole batch of loads back to back behind
 // counted vmcnt waits (with flat addressing hipcc serialized them: 2-4 loads per s_waitcnt vmcnt(0)).
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-
-__device__ __forceinline__ rsrc_t make_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
-}
-
-__device__ __forceinline__ float buf_load(rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff_bytes, soff_bytes, 0));
-}
+using mvsprim::rsrc_t;
+using mvsprim::make_rsrc;
+using mvsprim::buf_load;
 
 // N consecutive channel planes starting at plane c0: issue all 4*N tap loads, then interpolate.
 template <int N>

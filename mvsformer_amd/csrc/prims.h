@@ -1,7 +1,8 @@
 // Device primitives every kernel family shares: vector types, wave-uniform buffer descriptors and their loads, the DPP add, and the few
 // scalar formulas (activations, bicubic weights, BatchNorm element count) that more than one .hip file evaluates.  A .hip file pulls what
-// it needs in with `using mvsprim::name;`.  geometry.h (mvs::), conv_common.h (mvsconv::) and split3.h (mvsx3::) still carry their own
-// copies of the descriptor pieces and the bf16 vectors (the same types and bodies).  Nothing here has state, nothing here is host code.
+// it needs in with `using mvsprim::name;`.  geometry.h (mvs::), conv_common.h (mvsconv::) and split3.h (mvsx3::) include this file and
+// re-export the names their users spell through them; the definitions are here and nowhere else.  Nothing here has state, nothing here is
+// host code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +35,11 @@ __device__ __forceinline__ float buf_load(rsrc_t r, unsigned voff_bytes, unsigne
 }
 __device__ __forceinline__ f32x4 buf_load4(rsrc_t r, unsigned voff_bytes) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, 0, 0));
+}
+// buf_load with the cache policy AUX (aux of raw_buffer_load: 0 = default, 2 = nt): the staging / skip-tensor loads of the split-form 3-D kernels
+template <int AUX>
+__device__ __forceinline__ float stage_load(rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff_bytes, soff_bytes, AUX));
 }
 
 // ---- cross-lane ----------------------------------------------------------------------------------------------------------------------

@@ -7,11 +7,13 @@
 //   * +-Inf / NaN: the remainder v - h is Inf / NaN, so at least one term is non-finite and every output the value reaches is non-finite;
 //   * subnormal v: h, m, l are subnormal bf16 values; the matrix cores may flush them (absolute error <= 2^-126 per operand).
 #pragma once
+#include "prims.h"
 
 namespace mvsx3 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using mvsprim::bf16x8;
+using mvsprim::bf16x4;
+using mvsprim::f32x4;
 
 constexpr float BF16_MAX = 3.3895313892515355e38f;         // 0x7F7F0000
 
@@ -36,9 +38,8 @@ __device__ __forceinline__ void split3_bounded(float v, __bf16& h, __bf16& m, __
 // compiler makes of two scalar splits (it converts every value alone, then converts again to pack).  Bit-identical to split3 per value.
 // Each result word = {bf16(a) in the low half, bf16(b) in the high half}: consecutive elements of a bf16 vector.
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
-    const f32x2_t v = {a, b};
+    const mvsprim::f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
 template <bool CLAMP>
@@ -50,9 +51,8 @@ __device__ __forceinline__ void split3_pair(float a, float b, unsigned& h, unsig
 }
 
 struct Split3 { bf16x8 h, m, l; };
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ Split3 split3(const float (&v)[8]) {
-    u32x4_t h, m, l;
+    mvsprim::u32x4 h, m, l;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         unsigned a, b, c;
@@ -76,15 +76,25 @@ __device__ __forceinline__ __bf16 split3_term(float f, int term) {
 }
 
 // six MFMAs of one fp32-equivalent K = 32 step, smallest products first; a = first MFMA operand's terms, b = second's
-__device__ __forceinline__ __attribute__((ext_vector_type(4))) float mfma6(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
-                                                                          const bf16x8& bm, const bf16x8& bl,
-                                                                          __attribute__((ext_vector_type(4))) float c) {
+// six-argument form, order m*m, h*l, l*h, h*m, m*h, h*h: NOT the array form's order below, on purpose (fp32 accumulation order is observable)
+__device__ __forceinline__ f32x4 mfma6(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh, const bf16x8& bm, const bf16x8& bl,
+                                       f32x4 c) {
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+    return c;
+}
+// array form ([0] = h, [1] = m, [2] = l), order m*m, l*h, h*l, m*h, h*m, h*h: NOT the six-argument form's order above, on purpose
+__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], x[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[2], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[0], c, 0, 0, 0);
     return c;
 }
 

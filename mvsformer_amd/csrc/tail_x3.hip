@@ -40,10 +40,7 @@
 namespace {
 using namespace mvsconv;
 using mvsx3::bf16x8;
-
-__device__ __forceinline__ float stage_load(rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff_bytes, soff_bytes, X3_STAGE_AUX));
-}
+using mvsprim::stage_load;
 using mvsx3::mfma6;
 using mvsx3::Split3;
 using mvsx3::split3;
@@ -173,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void tail_x3_kernel(const TailArgs a) {
 #pragma unroll
         for (int it = 0; it < NI; ++it)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) pre[it][e] = TAIL_ABLATE(a, 1) ? 1.0f : stage_load(xin, voff[it], (unsigned)((base + (size_t)e * DHW) * 4));
+            for (int e = 0; e < 8; ++e) pre[it][e] = TAIL_ABLATE(a, 1) ? 1.0f : stage_load<X3_STAGE_AUX>(xin, voff[it], (unsigned)((base + (size_t)e * DHW) * 4));
     };
     auto commit = [&](unsigned char* buf) {
 #pragma unroll
@@ -212,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void tail_x3_kernel(const TailArgs a) {
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) rs[r][ph][e] = stage_load(rin, roff[r][ph], (unsigned)((base + (size_t)e * D * HWo) * 4));
+                for (int e = 0; e < 4; ++e) rs[r][ph][e] = stage_load<X3_STAGE_AUX>(rin, roff[r][ph], (unsigned)((base + (size_t)e * D * HWo) * 4));
     };
     // finished output plane od: BatchNorm, ReLU, the 1x1x1 conv over this lane's 4 channels (+ the skip tensor's share), the other 4
     // channels from lane ^ 16, the other column parity from lane ^ 32, 8-byte stores
@@ -289,10 +286,10 @@ __global__ __launch_bounds__(256, 2) void tail_x3_kernel(const TailArgs a) {
             auto load_slot = [&](int k) {                  // k = 0 .. 31, compile-time at every call site
                 if (k < 16) {
                     const int r = k >> 3, ph = (k >> 2) & 1, e = k & 3;
-                    if (res_now && r < R) rs[r][ph][e] = stage_load(rin, roff[r][ph], (unsigned)((rbase + (size_t)e * D * HWo) * 4));
+                    if (res_now && r < R) rs[r][ph][e] = stage_load<X3_STAGE_AUX>(rin, roff[r][ph], (unsigned)((rbase + (size_t)e * D * HWo) * 4));
                 } else {
                     const int it = (k - 16) >> 3, e = (k - 16) & 7;
-                    if (stage_next && it < NI) pre[it][e] = stage_load(xin, voff[it], (unsigned)((sbase + (size_t)e * DHW) * 4));
+                    if (stage_next && it < NI) pre[it][e] = stage_load<X3_STAGE_AUX>(xin, voff[it], (unsigned)((sbase + (size_t)e * DHW) * 4));
                 }
             };
             static_assert(R == 2 && NI == 2, "load_slot's schedule is written for two rows per wavefront and two staging items per thread");
@@ -410,10 +407,7 @@ extern "C" int mvs_tail_x3_fwd(const float* x, const void* wpacked, const float*
     nseg = mvs::ceil_div(D, a.seg_planes);
     a.nseg = nseg;
 #ifdef X3_ABLATE            // experiment builds only (make exp EXPFLAGS=-DX3_ABLATE): bit 0 constant inputs, bit 2 no MFMAs, bit 3 no stores
-    {
-        const char* e = getenv("MVS_X3_ABLATE");
-        a.ablate = e ? atoi(e) : 0;
-    }
+    a.ablate = mvs::env_int("MVS_X3_ABLATE", 0);
 #else
     a.ablate = 0;
 #endif

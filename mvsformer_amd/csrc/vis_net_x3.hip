@@ -31,7 +31,7 @@
 // environment-dependent path (as tail_x3.hip)
 #ifdef X3_ABLATE
 #define VIS_ABLATE(a, bit) (((a) & (bit)) != 0)
-static int vis_ablate_bits() { const char* e = getenv("MVS_VIS_ABLATE"); return e ? atoi(e) : 0; }
+static int vis_ablate_bits() { return mvs::env_int("MVS_VIS_ABLATE", 0); }
 #else
 #define VIS_ABLATE(a, bit) false
 static constexpr int vis_ablate_bits() { return 0; }
@@ -41,6 +41,8 @@ namespace {
 using namespace mvsconv;
 using mvsx3::bf16x4;
 using mvsx3::bf16x8;
+using mvsx3::mfma6;
+using mvsprim::u32x2;
 using mvsx3::split3;
 
 constexpr int T = 16;                                      // output tile edge
@@ -92,21 +94,9 @@ __global__ void vis_x3_prepare_kernel(const float* __restrict__ prm, bf16x8* __r
     out[idx] = v;
 }
 
-// six MFMAs of one fp32-equivalent K = 32 step, smallest products first (the order of conv3d_x3.hip)
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&x)[3], f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], x[0], c, 0, 0, 0);
-    return c;
-}
-
 // the lane's 4 channels (4*kb .. 4*kb+3) of pixel `pix`, split and stored: [term][octet = kb >> 1][pix][(kb & 1) * 8 bytes]
 template <int OCT, int TERM>
 __device__ __forceinline__ void store_split(unsigned char* base, int pix, int kb, const float (&v)[4]) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     u32x2 h, m, l;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {

@@ -668,8 +668,8 @@ __global__ __launch_bounds__(256) void bicubic_kernel(const float* __restrict__ 
 
 namespace {
 void launch_gemm(const GemmArgs& a, int nbatch, hipStream_t s) {
-    static const int big = [] { const char* e = getenv("MVS_GEMM_BIG_M"); return e ? atoi(e) : 2048; }();     // rows from which the 128-row tile is used
-    static const bool fast_on = [] { const char* e = getenv("MVS_GEMM_FAST"); return !e || atoi(e) != 0; }();
+    static const int big = mvs::env_int("MVS_GEMM_BIG_M", 2048);     // rows from which the 128-row tile is used
+    static const bool fast_on = mvs::env_int("MVS_GEMM_FAST", 1) != 0;
     const bool aligned = a.K % 32 == 0 && a.lda % 4 == 0 && a.ldb % 4 == 0 && a.sA1 % 4 == 0 && a.sA2 % 4 == 0 && a.sB1 % 4 == 0 && a.sB2 % 4 == 0 &&
                          (reinterpret_cast<uintptr_t>(a.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.B) & 15) == 0 &&
                          (int64_t)a.M * a.lda * 4 < ((int64_t)1 << 31) && (int64_t)a.N * a.ldb * 4 < ((int64_t)1 << 31);

@@ -747,7 +747,7 @@ namespace {
 struct PCfg { int gtt, ti, nw, wj; };
 PCfg env_cfg(const char* name) {
     PCfg c{0, 0, 0, 0};
-    if (const char* e = getenv(name)) sscanf(e, "%d,%d,%d,%d", &c.gtt, &c.ti, &c.nw, &c.wj);
+    if (const char* e = mvs::env_str(name)) sscanf(e, "%d,%d,%d,%d", &c.gtt, &c.ti, &c.nw, &c.wj);
     return c;
 }
 template <int MODE, int GTT, int TI, int NW, int WJ>

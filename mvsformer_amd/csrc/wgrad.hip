@@ -298,7 +298,7 @@ extern "C" int mvs_conv3d_wgrad(const float* A, const float* Bt, float* dW, int 
     MVS_REQUIRE((sd == 1 || sd == 2) && (shw == 1 || shw == 2), "mvs_conv3d_wgrad: stride (%d,%d,%d) not built", sd, shw, shw);
     MVS_REQUIRE((int64_t)CA * Dp * Hp * Wp * 4 < ((int64_t)1 << 31) && (int64_t)CB * Db * Hb * Wb * 4 < ((int64_t)1 << 31),
                 "mvs_conv3d_wgrad: one batch item exceeds the 2 GiB buffer window");
-    if (!(getenv("MVS_WGRAD_V1") && atoi(getenv("MVS_WGRAD_V1")))) {
+    if (!mvs::env_int("MVS_WGRAD_V1", 0)) {
         hipStream_t s2 = MVS_STREAM(stream);
         const int mt2 = mvs::ceil_div(CA, 16);
         int rc2 = MVS_OK;

@@ -314,7 +314,7 @@ def test_counter_traffic_evidence_matches_the_kernel_sources():
     for k in ("vis_x3_kernel", "cv_aggregate_kernel<2,true>", "cv_entropy_kernel<2>", "nchw_to_nhwc_multi"):      # the bench line's roofline kernels
         assert k in tj["kernels"], k
         assert all(os.path.exists(os.path.join(_sources.CSRC, f)) for f in _sources.files_of(k))
-    assert len(_sources.files_of("vis_x3_kernel")) < 6          # a known kernel maps to ITS files, not to all of csrc/
+    assert len(_sources.files_of("vis_x3_kernel")) < 7          # a known kernel maps to ITS files (one .hip, four csrc/ headers, the public header), not to all of csrc/
 
 
 def _project_includes(path, seen=None):
@@ -355,3 +355,41 @@ def test_source_rules_list_every_included_header_and_find_every_kernel():
         assert holders, "%s: no __global__ or extern \"C\" function of that name in csrc/" % k
         files = _sources.files_of(k)
         assert len(files) <= n_rules and files[0] in holders, (k, files[0], sorted(holders))
+
+
+def test_device_helpers_and_the_env_reader_have_one_home():
+    """Plain source checks over csrc/: the shared vector types, the buffer-descriptor pieces and ``dpp_add`` are defined in prims.h and nowhere
+    else (function bodies included), ``stage_load`` likewise, both forms of ``mfma6`` only in split3.h, and ``getenv`` is spelled only in
+    common.h (``mvs::env_int`` / ``mvs::env_str``).  The public header is part of ``file_digests()`` and of every rule."""
+    import hashlib
+    from mvsformer_amd import _sources
+    src = {f: open(os.path.join(_sources.CSRC, f)).read() for f in sorted(os.listdir(_sources.CSRC)) if f.endswith((".hip", ".h"))}
+
+    def homes(pattern):
+        return {f: n for f, n in ((f, len(re.findall(pattern, s))) for f, s in src.items()) if n}
+
+    for name in ("f32x2", "f32x4", "u32x2", "u32x4", "bf16x8", "bf16x4", "rsrc_t"):
+        assert homes(r"\busing\s+%s\s*=|\btypedef\b[^;]*\b%s\b[^;]*;" % (name, name)) == {"prims.h": 1}, name
+    assert homes(r"\bunsigned\s+OOB\s*=") == {"prims.h": 1}
+    fn = r"__device__[^;{}()]*\b%s\s*\("           # a declaration or definition, not a call
+    for name, n in (("make_rsrc", 2), ("buf_load", 1), ("buf_load4", 1), ("dpp_add", 1), ("stage_load", 1)):
+        assert homes(fn % name) == {"prims.h": n}, name
+    assert homes(fn % "mfma6") == {"split3.h": 2}
+    assert homes(r"getenv") == {"common.h": 2}
+    digests = _sources.file_digests()
+    assert _sources.PUB not in src and "/" in _sources.PUB
+    assert digests[_sources.PUB] == hashlib.sha256(open(os.path.join(REPO, "include", "mvs_hip.h"), "rb").read()).hexdigest()[:16]
+    assert all(_sources.PUB in files for _, files in _sources._RULES)
+
+
+def test_env_reader_matches_atoi_under_sanitizers(tmp_path):
+    """tests/env_reader_check.cpp: a stand-alone host program (its own main, host code only, nothing of it enters the library) built with
+    the sanitizers on the host side only (each flag behind -Xarch_host; there is no device code in it).  ``mvs::env_int`` / ``mvs::env_str`` return what ``e ? atoi(e) : default`` on getenv's result returned
+    for a variable that is unset, empty, non-numeric, negative, a large number and a 4 KB string, and the run is clean."""
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "env_reader_check")
+    subprocess.check_call([hipcc, "-std=c++17", "-x", "hip", "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           os.path.join(REPO, "tests", "env_reader_check.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok" and not run.stderr.strip(), (run.returncode, run.stdout, run.stderr)
