@@ -15,9 +15,11 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 import torch  # noqa: F401  (load order, see above)
 
+from . import switches as sw
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
-LIB_PATH = os.environ.get("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
+LIB_PATH = sw.text("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
 ABI_VERSION = 46
 
 from ctypes import c_double  # noqa: E402

@@ -9,14 +9,13 @@ parameters; ``depth`` (arg-max gather) and ``photometric_confidence`` are not di
 """
 from __future__ import annotations
 
-import os
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, switches as sw
 
 
 def _sync_sums(sums: torch.Tensor, count: float, bn):
@@ -79,7 +78,7 @@ def _wino_ok(stride, cin, cout, x) -> bool:
     disables).  The eval path prefers the split-form bf16 kernels instead (module.Conv3d: Winograd there is opt-in, MVS_CONV_WINO=1);
     training keeps fp32 MFMA arithmetic end to end, and the Winograd kernel is bit-reproducible in the shipped build (no packed fp32
     instructions: DESIGN.md 4.7c)."""
-    return tuple(stride) == (1, 1) and os.environ.get("MVS_CONV_WINO", "1") != "0" and \
+    return tuple(stride) == (1, 1) and sw.text("MVS_CONV_WINO") != "0" and \
         ops.conv3d_wino_supported(cin, cout, *x.shape[2:])
 
 
@@ -314,7 +313,7 @@ def embed_conv2d_weight(w2d: torch.Tensor, cin_pad: int) -> torch.Tensor:
 
 def _fused_layers() -> bool:
     """MVS_TRAIN_FUSED=0 keeps the round-4 chain of separate conv / BatchNorm autograd nodes (diagnostics, A/B timing)."""
-    return os.environ.get("MVS_TRAIN_FUSED", "1") != "0"
+    return sw.flag("MVS_TRAIN_FUSED")
 
 
 def vis_train(entropy: torch.Tensor, vis: nn.Sequential) -> torch.Tensor:
@@ -337,10 +336,10 @@ def vis_train_views(entropy: torch.Tensor, vis: nn.Sequential) -> torch.Tensor:
     statistics, running-stat updates and gradients of ``Vs`` separate per-view calls (reference mvsformer_model.py:91 calls
     the CNN once per view): the convolutions see a batch of ``B*Vs`` maps, BatchNorm works per (view, channel) group."""
     B, Vs, H, W = entropy.shape
-    if os.environ.get("MVS_VIS_PER_VIEW", "0") == "1" or Vs == 1:
+    if sw.flag("MVS_VIS_PER_VIEW") or Vs == 1:
         return torch.cat([vis_train(entropy[:, v:v + 1], vis) for v in range(Vs)], dim=1)
     from .module import autocast_bf16
-    if autocast_bf16() and os.environ.get("MVS_VIS_BF16", "1") != "0":
+    if autocast_bf16() and sw.flag("MVS_VIS_BF16"):
         # under autocast the reference runs this CNN in half precision too (it is inside the autocast region,
         # trainer/mvsformer_trainer.py:104-106): bf16 channel-last kernels, fp32 statistics, the 1x1 conv + sigmoid in fp32
         # batch index b*Vs + v; entropy is detached (no gradient)
@@ -446,7 +445,7 @@ class WgradFlushFn(torch.autograd.Function):
 
 
 def _wgrad_group_on() -> bool:
-    return os.environ.get("MVS_TRAIN_WGRAD_GROUP", "1") != "0"
+    return sw.flag("MVS_TRAIN_WGRAD_GROUP")
 
 
 def route_of(conv):

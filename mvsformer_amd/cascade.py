@@ -5,13 +5,12 @@ start from precomputed per-stage feature maps (the bench, the tests, inference s
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Sequence
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, switches as sw
 from .module import init_inverse_range, schedule_inverse_range
 from .stagenet import StageNet
 
@@ -44,7 +43,7 @@ class CascadeMVS(nn.Module):
         from . import autograd as ag
         from .module import autocast_bf16
         stages = list(self.fusions)
-        shared = autocast_bf16() and ag._fused_layers() and os.environ.get("MVS_TRAIN_WGRAD_SCOPE", "cascade") != "stage" \
+        shared = autocast_bf16() and ag._fused_layers() and sw.text("MVS_TRAIN_WGRAD_SCOPE") != "stage" \
             and ag.route_weights([st.train_pack() for st in stages])
         if not shared:
             return self._forward(features, proj_matrices, depth_values, tmp)
@@ -64,7 +63,7 @@ class CascadeMVS(nn.Module):
         prob_maps = torch.zeros(B, Hf, Wf, dtype=torch.float32, device=last.device)
         outputs: Dict[str, object] = {}
         stage_out = None
-        if not self.training and n <= 4 and last.is_cuda and os.environ.get("MVS_TRANSPOSE_MULTI", "1") != "0":
+        if not self.training and n <= 4 and last.is_cuda and sw.flag("MVS_TRANSPOSE_MULTI"):
             # eval: the four stages' NCHW -> NHWC transposes in ONE launch up front (each stage then finds its map channel-last already)
             keys = ["stage%d" % (i + 1) for i in range(n)]
             cl = ops.to_channels_last_multi([features[k].detach().to(torch.float32) for k in keys])

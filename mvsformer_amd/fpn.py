@@ -22,12 +22,11 @@ bilinear x2 upsampling + lateral add and its adjoint in ``csrc/fpn_train.hip``. 
 """
 from __future__ import annotations
 
-import os
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, ops, switches as sw
 from .module import _publish_cache, _versions
 
 ACT_LRELU, ACT_SWISH = 2, 3          # activation codes of the BatchNorm kernels (csrc/train.hip)
@@ -143,9 +142,9 @@ class FPNDecoder(nn.Module):
                 inner, seq = getattr(self, "inner%d" % k), getattr(self, "out%d" % k)
                 scale, shift = self._fold(seq)
                 x3 = None
-                if k == 3 and os.environ.get("MVS_FPN_X3", "1") != "0":      # the full-resolution level in split form (csrc/fpn_cp.hip, fpn_x3.hip)
+                if k == 3 and sw.text("MVS_FPN_X3") != "0":      # the full-resolution level in split form (csrc/fpn_cp.hip, fpn_x3.hip)
                     x3 = ops.fpn_level_x3_prepare(seq[0].weight.detach().contiguous(), inner.weight.detach(), inner.bias.detach(), scale, shift)
-                elif os.environ.get("MVS_FPN_X3", "1") != "0":               # levels 1-2: the 3x3 convolution in split form (csrc/fpn_lvl_x3.hip)
+                elif sw.text("MVS_FPN_X3") != "0":               # levels 1-2: the 3x3 convolution in split form (csrc/fpn_lvl_x3.hip)
                     x3 = ops.fpn_level_x3s_prepare(seq[0].weight.detach().contiguous(), scale)
                 levels.append((inner.weight.detach().reshape(ops.FPN_CH // 2, 2, -1).permute(0, 2, 1).contiguous(), inner.bias.detach().contiguous(),
                                ops.fpn_pack_weights(seq[0].weight.detach().contiguous()), scale, shift, x3))
@@ -175,13 +174,13 @@ class FPNDecoder(nn.Module):
                 w_in, b_in, packed, scale, shift, x3 = levels[i]
                 if i == 2 and x3 is not None:                # MVS_FPN_X3: 1 (default) = csrc/fpn_cp.hip, strip = csrc/fpn_x3.hip, 0 = csrc/fpn.hip
                     prepared, shift_x, border, prepared_cp = x3
-                    if os.environ.get("MVS_FPN_X3", "1") == "strip":
+                    if sw.text("MVS_FPN_X3") == "strip":
                         out = ops.fpn_level_x3(intra, lateral.float().contiguous(), prepared, shift_x, border)
                     else:
                         out = ops.fpn_level_cp(_channels_last(intra), _channels_last(lateral), prepared_cp, shift_x, border)
                 else:
                     # the level below the full-resolution one hands its intra map over channel-last when csrc/fpn_cp.hip will read it
-                    nhwc = i == 1 and levels[2][5] is not None and os.environ.get("MVS_FPN_X3", "1") != "strip"
+                    nhwc = i == 1 and levels[2][5] is not None and sw.text("MVS_FPN_X3") != "strip"
                     if x3 is not None:
                         intra, out = ops.fpn_level_x3s(intra, lateral.float().contiguous(), w_in, b_in, x3, shift, want_intra=True, intra_nhwc=nhwc)
                     else:
@@ -342,9 +341,9 @@ class FPNEncoder(nn.Module):
                 shift = m.bn.bias.detach().double() - m.bn.running_mean.double() * scale
                 wt = m.conv.weight.detach().contiguous()
                 x3 = None                                    # conv00 / conv01: the split form (csrc/conv2d_x3.hip)
-                if os.environ.get("MVS_FPN_X3", "1") != "0" and ops.conv2d_x3_supported(wt.shape[1], wt.shape[0], k, stride):
+                if sw.text("MVS_FPN_X3") != "0" and ops.conv2d_x3_supported(wt.shape[1], wt.shape[0], k, stride):
                     x3 = ops.conv2d_x3_prepare(wt, scale.float().contiguous())
-                elif os.environ.get("MVS_FPN_X3", "1") != "0" and ops.conv2d_x3s_supported(wt.shape[1], wt.shape[0], k, stride):
+                elif sw.text("MVS_FPN_X3") != "0" and ops.conv2d_x3s_supported(wt.shape[1], wt.shape[0], k, stride):
                     x3 = ops.conv2d_x3s_prepare(wt, scale.float().contiguous(), stride)      # the layers below full resolution (csrc/conv2d_x3s.hip)
                 layers.append((ops.conv2d_pack_weights(wt), scale.float().contiguous(), shift.float().contiguous(), m.conv.out_channels, k, stride, x3))
             _publish_cache()

@@ -9,20 +9,20 @@ DDP and SyncBatchNorm conversion working); every forward runs the hand-written H
 ``libmvs_hip.so`` through :mod:`mvsformer_amd.ops`.  There is no PyTorch/CPU fallback.
 
 Eval-mode BatchNorm is folded into a per-channel ``scale``/``shift`` pair applied in the conv epilogue;
-folded parameters and the MFMA-friendly weight packing are cached and rebuilt when any parameter changes.
+folded parameters and the MFMA-friendly weight packing are cached and rebuilt when a parameter or a pack-time switch changes.
 Training mode (``module.train()``) runs raw conv -> batch-statistics BatchNorm -> ReLU (+ skip) through the autograd
 functions of :mod:`mvsformer_amd.autograd`, whose forward and backward are HIP kernels as well.
 """
 from __future__ import annotations
 
-import os
-from typing import Dict, List, Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, switches as sw
 from ._lib import MvsHipError
+from .switches import SMALL_MAX_WORK, _parse_small_limit
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -39,10 +39,10 @@ def _bn_fold(bn: nn.modules.batchnorm._BatchNorm) -> Tuple[torch.Tensor, torch.T
     return scale.contiguous(), (b - mean * scale).contiguous()
 
 
-def _versions(mod: nn.Module) -> tuple:
-    """Cache key of everything derived from a module's parameters / buffers: torch's (data_ptr, _version) per tensor + the epoch of
+def _versions(*mods: Optional[nn.Module]) -> tuple:
+    """Cache key of everything derived from the modules' parameters / buffers: torch's (data_ptr, _version) per tensor + the epoch of
     raw-pointer writes (``ops.bump_weights_epoch``: FusedAdamW, training-mode BatchNorm kernels, replayed hipGraphs)."""
-    return (ops.weights_epoch(),) + tuple((t.data_ptr(), t._version) for t in list(mod.parameters()) + list(mod.buffers()))
+    return (ops.weights_epoch(),) + tuple((t.data_ptr(), t._version) for m in mods if m is not None for t in list(m.parameters()) + list(m.buffers()))
 
 
 def _publish_cache() -> None:
@@ -57,7 +57,7 @@ def autocast_bf16() -> bool:
     """True inside ``torch.autocast('cuda', dtype=torch.bfloat16)`` (how BASELINE configs[2] trains; the reference trainer wraps
     the model in ``torch.cuda.amp.autocast``, trainer/mvsformer_trainer.py:104-106) or with MVS_TRAIN_BF16=1: the regularizer
     then runs on bf16 channel-last activations and the bf16 matrix cores."""
-    if os.environ.get("MVS_TRAIN_BF16", "") == "1":
+    if sw.flag("MVS_TRAIN_BF16"):
         return True
     try:
         if hasattr(torch, "get_autocast_dtype"):
@@ -79,7 +79,7 @@ def _multi_use(t, link=None):
 def _skip_links(x, n=3):
     """``n`` SkipLinks for one forward of a U-Net on the fused bf16 training layers, else Nones (MVS_TRAIN_SKIPLINK=0: autograd adds)."""
     from . import autograd as ag
-    if x.dtype == torch.bfloat16 and ag._fused_layers() and os.environ.get("MVS_TRAIN_SKIPLINK", "1") != "0":
+    if x.dtype == torch.bfloat16 and ag._fused_layers() and sw.flag("MVS_TRAIN_SKIPLINK"):
         return tuple(ag.SkipLink() for _ in range(n))
     return (None,) * n
 
@@ -93,7 +93,7 @@ def _train_conv_bn_act(x, conv, bn, relu, residual, transposed_sd=None, take=Non
             raise MvsHipError("bf16 training layer without BatchNorm / with bias is not built")
         # MVS_BN_FUSED_STATS=1: the convolution's epilogue takes the batch statistics of its output instead of a separate pass over y.
         # Measured 13.5 vs 13.3 ms per step (one partial row per wavefront makes the fixed-order reduce long): off by default.
-        fused = 1 if os.environ.get("MVS_BN_FUSED_STATS", "0") == "1" else 0
+        fused = 1 if sw.flag("MVS_BN_FUSED_STATS") else 0
         pk = ag.packed_of(conv)                              # this step's layouts if the stage's StagePack made them (one launch per stage)
         if ag._fused_layers() and not ag._bn_synced(bn):
             # statistics stay on this rank: the whole layer is one autograd node (conv with the statistics in its epilogue -> finalize ->
@@ -124,160 +124,200 @@ def _train_conv_bn_act(x, conv, bn, relu, residual, transposed_sd=None, take=Non
 
 
 # ---------------------------------------------------------------------------------------------------------
-# layer holders (reference models/module.py:83-165, 168-197)
+# layer holders (reference models/module.py:83-165, 168-197); first, which kernel serves one in eval mode: pure functions of plain values
 # ---------------------------------------------------------------------------------------------------------
-X3_MIN_VOXELS = 40 * 1024      # output voxels from which the split-form conv is used (MVS_CONV_X3_MIN_VOXELS overrides)
-# The small-volume split-form kernel (csrc/conv3d_x3_small.hip) serves a layer while voxels x Cin x Cout stays below these bounds (output voxels
-# of a convolution, input voxels of a transposed convolution): measured per layer at the two coarse config-2 stages (profiles/r04_bench_small.txt),
-# it wins 4-21 us per launch below them and loses above (its vector ALU bound grows with the volume, the tiled kernels' latency chains do not).
-SMALL_MAX_WORK = (16 << 20, 8 << 20)      # (Conv3d, Deconv3d); MVS_CONV_SMALL_MAX_WORK="conv,deconv" overrides, "0,0" = never
+_SMALL_LIMITS = _parse_small_limit(sw.text("MVS_CONV_SMALL_MAX_WORK"))      # (Conv3d, Deconv3d); read once: not on every forward of every layer
+_WINDOW = 1 << 31        # bytes a buffer descriptor of the split-form kernels addresses
 
 
-def _parse_small_limit(text) -> Tuple[int, int]:
-    """``"conv,deconv"`` or one value for both; anything else is a configuration error reported at import, not in the middle of a forward."""
-    if not text:
-        return SMALL_MAX_WORK
-    try:
-        v = [int(t) for t in text.split(",")]
-    except ValueError:
-        v = []
-    if len(v) == 1:
-        v = v * 2
-    if len(v) != 2 or min(v) < 0:
-        raise ValueError("MVS_CONV_SMALL_MAX_WORK must be 'conv,deconv' or one non-negative integer, got %r" % (text,))
-    return v[0], v[1]
+class RouteSwitches(NamedTuple):
+    """The switch values one eval forward of a regularizer routes by (read once per forward, :func:`route_switches`)."""
+    min_voxels: int = sw.TABLE["MVS_CONV_X3_MIN_VOXELS"].default      # output voxels from which a layer takes the split form
+    small_limit: Tuple[int, int] = SMALL_MAX_WORK      # (Conv3d, Deconv3d)
+    conv_x3: str = "1"                                 # MVS_CONV_X3: "0" off, "strided" / "s1" one kind of convolution only (diagnostics)
+    conv_wino: Optional[str] = None                    # MVS_CONV_WINO: "1" packs the Winograd form of the stride-1 convolutions
+    tail: str = "x3"                                   # MVS_TAIL
+    fuse_prob: bool = True                             # MVS_FUSE_PROB
 
 
-_SMALL_LIMITS = _parse_small_limit(os.environ.get("MVS_CONV_SMALL_MAX_WORK"))      # read once: not on every forward of every layer
-_WINDOW = 1 << 31        # bytes a buffer descriptor of the split-form kernels addresses (per sample for conv / deconv, per call for the tail)
+def route_switches() -> RouteSwitches:
+    return RouteSwitches(sw.integer("MVS_CONV_X3_MIN_VOXELS"), _SMALL_LIMITS, sw.text("MVS_CONV_X3"), sw.text("MVS_CONV_WINO"),
+                         sw.text("MVS_TAIL"), sw.flag("MVS_FUSE_PROB"))
 
 
-def _small_limit(transposed: bool) -> int:
-    if os.environ.get("MVS_CONV_X3", "1") == "0":
-        return 0
-    return _SMALL_LIMITS[1 if transposed else 0]
+def _small_limit(rs: RouteSwitches, transposed: bool) -> int:
+    return 0 if rs.conv_x3 == "0" else rs.small_limit[1 if transposed else 0]      # MVS_CONV_X3=0 turns every split form off
+
+
+def conv_route(cin, cout, stride, in_shape, forms, rs: RouteSwitches, wino_ok: bool = False) -> str:
+    """Kernel of a 3x3x3 convolution with ``stride = (depth, height/width)`` on an input of ``in_shape = (D, H, W)`` voxels per channel.
+    ``forms``: the packed forms the layer has; ``wino_ok``: ``ops.conv3d_wino_supported`` of the shape."""
+    D, H, W = in_shape
+    # 3-term bf16 split form (csrc/conv3d_x3.hip: fp32-equivalent, bf16 matrix cores) from min_voxels output voxels up - below that the launch
+    # is too small to fill the chip with its 16 x 16 x D tiles and the fp32-MFMA kernel wins.  (The count floors H and W by the stride.)
+    # A sample beyond the kernel's 2 GiB buffer window falls through to the 64-bit-addressed fp32-MFMA kernel.
+    if "x3" in forms and rs.conv_x3 != "0" and D * (H // stride[1]) * (W // stride[1]) >= rs.min_voxels and cin * D * H * W * 4 < _WINDOW:
+        return "x3"
+    # small-volume split form (csrc/conv3d_x3_small.hip): CostRegNet's inner layers at the coarse stages, by output voxels x Cin x Cout
+    if "small" in forms and ((D - 1) // stride[0] + 1) * ((H - 1) // stride[1] + 1) * ((W - 1) // stride[1] + 1) * cin * cout <= _small_limit(rs, False):
+        return "small"
+    if "wino" in forms and wino_ok:                      # Winograd F(2x2,3x3) fp32 MFMA, where MVS_CONV_WINO=1 packed it
+        return "wino"
+    return "fp32"
+
+
+def deconv_route(cin, cout, sd, in_shape, forms, rs: RouteSwitches, x3_ok: bool = False, residual_bytes: int = 0) -> str:
+    """Kernel of a 3x3x3 transposed convolution of stride ``(sd, 2, 2)``.  ``x3_ok``: ``ops.deconv3d_x3_supported`` of the layer;
+    ``residual_bytes``: one sample of the skip tensor added in the epilogue (0 without one)."""
+    D, H, W = in_shape
+    if sd == 1:
+        # split-form transposed conv (csrc/conv3d_x3.hip) where it beats the fp32-MFMA kernel: conv7 / conv9 at real sizes; 8 output channels
+        # (conv11) fill half a matrix tile.  It handles column pairs, and its window is 2 GiB per input sample, 4 GiB per residual sample.
+        if cout >= 16 and rs.conv_x3 != "0" and x3_ok and W % 2 == 0 and 4 * D * H * W >= rs.min_voxels \
+                and cin * D * H * W * 4 < _WINDOW and residual_bytes < 2 * _WINDOW:
+            return "x3"
+        return "fp32"
+    if "small" in forms and D * H * W * cin * cout <= _small_limit(rs, True):      # small-volume split form, by INPUT voxels x Cin x Cout
+        return "small"
+    return "fp32"
+
+
+def tail_route(cin, cout, sd, in_shape, rs: RouteSwitches, skip_bytes: int = 0) -> str:
+    """conv11 (transposed, stride ``(sd, 2, 2)``) + the 1x1x1 ``prob``: one launch or two.  ``skip_bytes``: the WHOLE batch of the skip
+    volume - unlike the layers' per-sample windows, the tail kernel's descriptor covers the call."""
+    D, H, W = in_shape
+    if not (cout == 8 and sd == 1 and W % 4 == 0 and rs.fuse_prob):      # the fused kernels are built for 8 channels, four columns per lane
+        return "unfused"
+    # split form (csrc/tail_x3.hip) for the shape it is built for (16 -> 8) from min_voxels up; MVS_TAIL=fp32 keeps the fp32-MFMA tail
+    if cin == 16 and rs.conv_x3 != "0" and rs.tail == "x3" and 4 * D * H * W >= rs.min_voxels and skip_bytes < _WINDOW:
+        return "tail_x3"
+    return "tail_fp32"
+
+
+class _EvalLayer:
+    """Eval-mode state of ONE 3x3x3 (transposed) convolution with its BatchNorm or bias: the check of what is built, the folded
+    ``scale`` / ``shift``, the packed weight forms and the key they were made under (the tensors' versions + the pack-time switches, so a
+    parameter update or an environment change rebuilds on the next forward).  Not an ``nn.Module`` - no ``state_dict`` key - and it holds no
+    module either: the owner passes ``conv`` / ``bn`` in, so SyncBatchNorm conversion or a replaced child cannot leave it behind."""
+
+    _key = None
+
+    @staticmethod
+    def check(conv) -> Tuple[int, int]:
+        """-> ``(depth stride, height/width stride)`` of a layer the kernels are built for, else MvsHipError."""
+        s = tuple(conv.stride)
+        if isinstance(conv, nn.ConvTranspose3d):
+            if tuple(conv.kernel_size) != (3, 3, 3) or tuple(conv.padding) != (1, 1, 1) or conv.groups != 1:
+                raise MvsHipError("Deconv3d: only kernel 3, padding 1, groups 1 is built (got %s)" % conv)
+            if (s, tuple(conv.output_padding)) not in (((2, 2, 2), (1, 1, 1)), ((1, 2, 2), (0, 1, 1))):
+                raise MvsHipError("Deconv3d: stride %s / output_padding %s is not built" % (s, tuple(conv.output_padding)))
+        elif tuple(conv.kernel_size) != (3, 3, 3) or tuple(conv.padding) != (1, 1, 1) or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1:
+            raise MvsHipError("Conv3d: only kernel 3, padding 1, dilation 1, groups 1 is built (got %s)" % conv)
+        elif s not in ((1, 1, 1), (2, 2, 2), (1, 2, 2)):
+            raise MvsHipError("Conv3d: stride %s is not built" % (s,))
+        return s[0], s[1]
+
+    def _sync(self, conv, bn, rs: RouteSwitches) -> None:
+        key = (_versions(conv, bn), rs.conv_x3, rs.conv_wino, rs.small_limit)
+        if key == self._key:
+            return
+        self.transposed = isinstance(conv, nn.ConvTranspose3d)
+        self.cin, self.cout, self.stride = cin, cout, s = conv.in_channels, conv.out_channels, self.check(conv)
+        w = _f32c(conv.weight)
+        self.forms = forms = {"fp32": ops.conv3d_pack(w, self.transposed, s[0])}
+        # the split forms of the stride-(1,2,2) transposed layers (deconv x3, the tail) are packed by the first forward that routes to them
+        self.x3_ok = self.transposed and s[0] == 1 and ops.deconv3d_x3_supported(cin, cout, 1)
+        if self.transposed:
+            if s[0] == 2 and cout >= 16 and _small_limit(rs, True) > 0 and ops.conv3d_small_supported(cin, cout, 2, True):
+                forms["small"] = ops.conv3d_small_pack(w, 2, True)
+        else:
+            # Winograd F(2x2,3x3) fp32-MFMA image of the stride-1 layers (conv2 / conv4 / conv6): opt-in for eval (MVS_CONV_WINO=1) because the
+            # split form is as fast at the sizes that matter (reproducible under concurrent streams since DESIGN.md 4.7c: test_hip_multistream.py)
+            if s == (1, 1) and cin % 4 == 0 and cout % 16 == 0 and cout <= 64 and rs.conv_wino == "1":
+                forms["wino"] = ops.conv3d_wino_pack(w)
+            # split form for every layer shape it is built for (stride (1,1,1) and (1,2,2)); MVS_CONV_X3 = "strided" / "s1": one kind only
+            if rs.conv_x3 != "0" and ops.conv3d_x3_supported(cin, cout, s) \
+                    and not (rs.conv_x3 == "strided" and s[1] == 1) and not (rs.conv_x3 == "s1" and s[1] == 2):
+                forms["x3"] = ops.conv3d_x3_pack(w, s)
+            if s[0] == s[1] and _small_limit(rs, False) > 0 and ops.conv3d_small_supported(cin, cout, s[0], False):
+                forms["small"] = ops.conv3d_small_pack(w, s[0], False)
+        self.scale, self.shift = _bn_fold(bn) if bn is not None else (None, _f32c(conv.bias) if conv.bias is not None else None)
+        _publish_cache()
+        self._key = key
+
+    def _late_form(self, name: str, conv, pack):
+        if name not in self.forms:
+            self.forms[name] = pack(_f32c(conv.weight))
+            _publish_cache()
+        return self.forms[name]
+
+    def run(self, conv, bn, relu: bool, x, residual, rs: RouteSwitches):
+        """The layer on ``x [B,Cin,D,H,W]`` (+ ``residual`` before the ReLU) through the kernel its route names."""
+        self._sync(conv, bn, rs)
+        cin, cout, stride, f, scale, shift = self.cin, self.cout, self.stride, self.forms, self.scale, self.shift
+        if not self.transposed:
+            route = conv_route(cin, cout, stride, x.shape[2:], f, rs, "wino" in f and ops.conv3d_wino_supported(cin, cout, *x.shape[2:]))
+            if route == "x3":
+                return ops.conv3d_x3(x, f["x3"], cin, cout, stride, scale, shift, residual, relu=relu)
+            if route == "small":
+                return ops.conv3d_small(x, f["small"], cin, cout, stride[0], False, scale, shift, residual, relu=relu)
+            if route == "wino":
+                return ops.conv3d_wino(x, f["wino"], cin, cout, scale, shift, residual, relu=relu)
+            return ops.conv3d(x, f["fp32"], cin, cout, stride, scale, shift, residual, relu=relu, tag="conv3d_%dto%d_s%d%d" % (cin, cout, *stride))
+        sd = stride[0]
+        route = deconv_route(cin, cout, sd, x.shape[2:], f, rs, self.x3_ok, 0 if residual is None else residual[0].numel() * 4)
+        if route == "x3":
+            return ops.deconv3d_x3(x, self._late_form("x3", conv, lambda w: ops.deconv3d_x3_pack(w, sd)), cin, cout, sd, scale, shift, residual, relu=relu)
+        if route == "small":
+            return ops.conv3d_small(x, f["small"], cin, cout, 2, True, scale, shift, residual, relu=relu)
+        return ops.deconv3d(x, f["fp32"], cin, cout, sd, scale, shift, residual, relu=relu, tag="deconv3d_%dto%d_s%d" % (cin, cout, sd))
+
+    def run_tail(self, conv, bn, x, skip, w1, b1, rs: RouteSwitches):
+        """The layer (ReLU, ``skip`` added) followed by the 1x1x1 convolution ``(w1, b1)`` to one channel: ``[B,D,2H,2W]``, as ONE launch
+        (the 8-channel volume between the two is never written) when the shape allows, else as two."""
+        self._sync(conv, bn, rs)
+        route = tail_route(self.cin, self.cout, self.stride[0], x.shape[2:], rs, skip.numel() * 4)
+        if route == "tail_x3":
+            return ops.tail_x3(x, self._late_form("tail_x3", conv, ops.tail_x3_pack), self.scale, self.shift, skip, w1, b1, relu=True)
+        if route == "tail_fp32":
+            return ops.deconv3d_prob1(x, self.forms["fp32"], self.cin, self.scale, self.shift, skip, w1, b1, relu=True)
+        return ops.prob1(self.run(conv, bn, True, x, skip, rs), w1, b1).squeeze(1)
 
 
 class Conv3d(nn.Module):
     """conv(bias = not bn) -> BatchNorm3d -> ReLU, as reference ``Conv3d`` (module.py:83-123)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, relu=True, bn=True, bn_momentum=0.1,
-                 init_method="xavier", **kwargs):
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, relu=True, bn=True, bn_momentum=0.1, init_method="xavier", **kwargs):
         super().__init__()
         self.out_channels = out_channels
         self.kernel_size = kernel_size
         self.conv = nn.Conv3d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
         self.bn = nn.BatchNorm3d(out_channels, momentum=bn_momentum) if bn else None
         self.relu = relu
-        self._cache = None
+        self._layer = _EvalLayer()
 
-    def _prepared(self):
-        key = _versions(self)
-        if self._cache is None or self._cache[0] != key:
-            conv = self.conv
-            if tuple(conv.kernel_size) != (3, 3, 3) or tuple(conv.padding) != (1, 1, 1) or tuple(conv.dilation) != (1, 1, 1) \
-                    or conv.groups != 1:
-                raise MvsHipError("Conv3d: only kernel 3, padding 1, dilation 1, groups 1 is built (got %s)" % conv)
-            s = tuple(conv.stride)
-            if s not in ((1, 1, 1), (2, 2, 2), (1, 2, 2)):
-                raise MvsHipError("Conv3d: stride %s is not built" % (s,))
-            packed = ops.conv3d_pack(_f32c(conv.weight), transposed=False)
-            # Winograd F(2x2,3x3) fp32-MFMA image of the stride-1 layers (conv2 / conv4 / conv6): opt-in for eval (MVS_CONV_WINO=1) because the
-            # split form below is as fast at the sizes that matter.  (Round 3 saw its output move from run to run under concurrent streams;
-            # round 4 traced that to packed-fp32 instructions reading an SGPR pair's high half - a gfx950 hazard reproduced stand-alone in
-            # tools/probe/pk_mfma_race.hip, DESIGN.md 4.7c - and the library is built without packed fp32, so the kernel is reproducible:
-            # tests/test_hip_multistream.py[conv_wino].)
-            wino = None
-            if s == (1, 1, 1) and conv.in_channels % 4 == 0 and conv.out_channels % 16 == 0 and conv.out_channels <= 64 \
-                    and os.environ.get("MVS_CONV_WINO", "0") == "1":
-                wino = ops.conv3d_wino_pack(_f32c(conv.weight))
-            # 3-term bf16 split form (csrc/conv3d_x3.hip: fp32-equivalent, bf16 matrix cores) for every layer shape it is built for
-            # (stride (1,1,1) and (1,2,2)); forward() uses it from X3_MIN_VOXELS output voxels up (below that the launch is too small to
-            # fill the chip with its 16 x 16 x D tiles and the fp32-MFMA kernel wins).  MVS_CONV_X3=0 turns it off.
-            x3 = None
-            x3_mode = os.environ.get("MVS_CONV_X3", "1")        # "1" all built shapes, "strided" / "s1" one kind only (diagnostics), "0" off
-            if x3_mode != "0" and ops.conv3d_x3_supported(conv.in_channels, conv.out_channels, (s[0], s[1])) \
-                    and not (x3_mode == "strided" and s[1] == 1) and not (x3_mode == "s1" and s[1] == 2):
-                x3 = ops.conv3d_x3_pack(_f32c(conv.weight), (s[0], s[1]))
-            # small-volume split form (csrc/conv3d_x3_small.hip) for stride (1,1,1) / (2,2,2): CostRegNet's inner layers at the coarse stages
-            small = None
-            if s[0] == s[1] and _small_limit(False) > 0 and ops.conv3d_small_supported(conv.in_channels, conv.out_channels, s[0], False):
-                small = ops.conv3d_small_pack(_f32c(conv.weight), s[0], False)
-            if self.bn is not None:
-                scale, shift = _bn_fold(self.bn)
-            else:
-                scale = None
-                shift = _f32c(conv.bias) if conv.bias is not None else None
-            _publish_cache()
-            self._cache = (key, packed, scale, shift, (s[0], s[1]), wino, x3, small)
-        return self._cache[1:]
-
-    def forward(self, x, residual: Optional[torch.Tensor] = None, take=None):
+    def forward(self, x, residual: Optional[torch.Tensor] = None, take=None, _rs: Optional[RouteSwitches] = None):
         if self.training:
             return _train_conv_bn_act(x, self.conv, self.bn, self.relu, residual, take=take)
-        packed, scale, shift, stride, wino, x3, small = self._prepared()
-        # (a sample beyond the split-form kernel's 2 GiB buffer window falls through to the 64-bit-addressed fp32-MFMA kernel below)
-        if x3 is not None and x.shape[2] * (x.shape[3] // stride[1]) * (x.shape[4] // stride[1]) >= int(os.environ.get("MVS_CONV_X3_MIN_VOXELS", X3_MIN_VOXELS)) \
-                and x[0].numel() * 4 < _WINDOW:
-            return ops.conv3d_x3(x, x3, self.conv.in_channels, self.conv.out_channels, stride, scale, shift, residual, relu=self.relu)
-        if small is not None and ((x.shape[2] - 1) // stride[0] + 1) * ((x.shape[3] - 1) // stride[1] + 1) * ((x.shape[4] - 1) // stride[1] + 1) \
-                * self.conv.in_channels * self.conv.out_channels <= _small_limit(False):
-            return ops.conv3d_small(x, small, self.conv.in_channels, self.conv.out_channels, stride[0], False, scale, shift, residual, relu=self.relu)
-        if wino is not None and ops.conv3d_wino_supported(self.conv.in_channels, self.conv.out_channels, *x.shape[2:]):
-            return ops.conv3d_wino(x, wino, self.conv.in_channels, self.conv.out_channels, scale, shift, residual, relu=self.relu)
-        return ops.conv3d(x, packed, self.conv.in_channels, self.conv.out_channels, stride, scale, shift, residual,
-                          relu=self.relu, tag="conv3d_%dto%d_s%d%d" % (self.conv.in_channels, self.conv.out_channels, *stride))
+        return self._layer.run(self.conv, self.bn, self.relu, x, residual, _rs or route_switches())
 
 
 class Deconv3d(nn.Module):
     """conv_transpose(bias = not bn) -> BatchNorm3d -> ReLU, as reference ``Deconv3d`` (module.py:126-165)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, relu=True, bn=True, bn_momentum=0.1,
-                 init_method="xavier", **kwargs):
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, relu=True, bn=True, bn_momentum=0.1, init_method="xavier", **kwargs):
         super().__init__()
         self.out_channels = out_channels
         self.conv = nn.ConvTranspose3d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
         self.bn = nn.BatchNorm3d(out_channels, momentum=bn_momentum) if bn else None
         self.relu = relu
-        self._cache = None
+        self._layer = _EvalLayer()
 
-    def forward(self, x, residual: Optional[torch.Tensor] = None, give=None):
+    def forward(self, x, residual: Optional[torch.Tensor] = None, give=None, _rs: Optional[RouteSwitches] = None):
         if self.training:
-            _prepare_deconv_check(self.conv)
+            _EvalLayer.check(self.conv)
             return _train_conv_bn_act(x, self.conv, self.bn, self.relu, residual, transposed_sd=self.conv.stride[0], give=give)
-        key = _versions(self)
-        if self._cache is None or self._cache[0] != key:
-            prepared = _prepare_deconv(self.conv, self.bn)
-            cin, cout = self.conv.in_channels, self.conv.out_channels
-            small = None
-            if tuple(self.conv.stride) == (2, 2, 2) and cout >= 16 and _small_limit(True) > 0 and ops.conv3d_small_supported(cin, cout, 2, True):
-                small = ops.conv3d_small_pack(_f32c(self.conv.weight), 2, True)
-            _publish_cache()
-            self._cache = (key,) + prepared + (small,)
-        _, packed, scale, shift, sd, small = self._cache
-        if small is not None and x.shape[2] * x.shape[3] * x.shape[4] * self.conv.in_channels * self.conv.out_channels <= _small_limit(True):
-            return ops.conv3d_small(x, small, self.conv.in_channels, self.conv.out_channels, 2, True, scale, shift, residual, relu=self.relu)
-        return ops.deconv3d(x, packed, self.conv.in_channels, self.conv.out_channels, sd, scale, shift, residual,
-                            relu=self.relu, tag="deconv3d_%dto%d_s%d" % (self.conv.in_channels, self.conv.out_channels, sd))
-
-
-def _prepare_deconv_check(conv: nn.ConvTranspose3d):
-    s, op = tuple(conv.stride), tuple(conv.output_padding)
-    if tuple(conv.kernel_size) != (3, 3, 3) or tuple(conv.padding) != (1, 1, 1) or conv.groups != 1:
-        raise MvsHipError("Deconv3d: only kernel 3, padding 1, groups 1 is built (got %s)" % conv)
-    if not ((s == (2, 2, 2) and op == (1, 1, 1)) or (s == (1, 2, 2) and op == (0, 1, 1))):
-        raise MvsHipError("Deconv3d: stride %s / output_padding %s is not built" % (s, op))
-    return s
-
-
-def _prepare_deconv(conv: nn.ConvTranspose3d, bn):
-    s = _prepare_deconv_check(conv)
-    packed = ops.conv3d_pack(_f32c(conv.weight), transposed=True, sd=s[0])
-    if bn is not None:
-        scale, shift = _bn_fold(bn)
-    else:
-        scale, shift = None, (_f32c(conv.bias) if conv.bias is not None else None)
-    return packed, scale, shift, s[0]
+        return self._layer.run(self.conv, self.bn, self.relu, x, residual, _rs or route_switches())
 
 
 class ConvBnReLU(nn.Module):
@@ -315,6 +355,21 @@ def pack_vis_params(vis: nn.Sequential) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------------------
 # regularizers (reference models/module.py:469-505, 550-594)
 # ---------------------------------------------------------------------------------------------------------
+def _volume_input(net, x: torch.Tensor, strided: int, bf16_ok: bool):
+    """The cost volume as the layers of ``net`` take it: fp32 ``[B,C,D,H,W]`` - or, if ``bf16_ok``, the bf16 channel-last ``[B,D,H,W,C]`` it already
+    is (autograd.AggregateFn as_bf16).  -> (x, whether it is the latter).  ``strided``: how many of D, H, W (from the right) the U-Net halves."""
+    if not isinstance(net.inner, nn.Identity):
+        raise MvsHipError("%s: in_channels != base channels (1x1x1 'inner' conv) is not built" % type(net).__name__)
+    pre16 = bf16_ok and x.dtype == torch.bfloat16
+    if not pre16:
+        x = x.to(torch.float32)
+    x = x if x.is_contiguous() else x.contiguous()
+    dhw = tuple(x.shape[1:4] if pre16 else x.shape[2:])[-strided:]
+    if any(n % 8 for n in dhw):
+        raise MvsHipError("%s needs %s divisible by 8 (three stride-2 levels), got %s" % (type(net).__name__, ("H, W", "D, H, W")[strided - 2], dhw))
+    return x, pre16
+
+
 class CostRegNet(nn.Module):
     """3-D U-Net with stride-2 down/up-sampling in D, H, W (reference ``CostRegNet``).  ``forward(x[B,Cin,D,H,W])``
     returns ``[B,1,D,H,W]`` logits (``[B,base,D,H,W]`` features if ``last_layer=False``)."""
@@ -341,23 +396,16 @@ class CostRegNet(nn.Module):
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
         """Everything up to (not including) ``prob``; residual adds are fused into the deconv epilogues."""
-        if not isinstance(self.inner, nn.Identity):
-            raise MvsHipError("CostRegNet: in_channels != base_channels (1x1x1 'inner' conv) is not built")
-        pre16 = self.training and x.dtype == torch.bfloat16       # already bf16 channel-last [B,D,H,W,C] (autograd.AggregateFn as_bf16)
-        if not pre16:
-            x = x.to(torch.float32)
-        x = x if x.is_contiguous() else x.contiguous()
-        dhw = x.shape[1:4] if pre16 else x.shape[2:]
-        if dhw[0] % 8 or dhw[1] % 8 or dhw[2] % 8:
-            raise MvsHipError("CostRegNet needs D, H, W divisible by 8 (three stride-2 levels), got %s" % (tuple(dhw),))
+        x, pre16 = _volume_input(self, x, 3, self.training)
         if self.training and autocast_bf16() and not pre16:
             from . import autograd as ag
             x = ag.ToBf16Fn.apply(x)                     # fp32 cost volume -> bf16 channel-last; every layer below follows the dtype
         if not self.training:
-            c2 = self.conv2(self.conv1(x))
-            c4 = self.conv4(self.conv3(c2))
-            y = self.conv7(self.conv6(self.conv5(c4)), residual=c4)
-            return self.conv11(self.conv9(y, residual=c2), residual=x)
+            rs = route_switches()
+            c2 = self.conv2(self.conv1(x, _rs=rs), _rs=rs)
+            c4 = self.conv4(self.conv3(c2, _rs=rs), _rs=rs)
+            y = self.conv7(self.conv6(self.conv5(c4, _rs=rs), _rs=rs), residual=c4, _rs=rs)
+            return self.conv11(self.conv9(y, residual=c2, _rs=rs), residual=x, _rs=rs)
         # training: each skip tensor's two gradients meet in the strided convolution's data-gradient epilogue (autograd.SkipLink)
         l0, l2, l4 = _skip_links(x)
         c2 = _multi_use(self.conv2(self.conv1(x, take=l0)), l2)
@@ -416,91 +464,42 @@ class CostRegNet3D(nn.Module):
         else:
             self.inner = nn.Identity()
         self.prob = nn.Conv3d(base_channel, 1, 1, stride=1, padding=0)
-        self._dcache: Dict[str, tuple] = {}
+        self._layers = {name: _EvalLayer() for name in ("conv7", "conv9", "conv11")}
 
-    def _up(self, name: str, x, residual, give=None):
+    def _up(self, name: str, x, residual, give=None, _rs: Optional[RouteSwitches] = None):
         seq = getattr(self, name)
         if self.training:
-            _prepare_deconv_check(seq[0])
+            _EvalLayer.check(seq[0])
             return _train_conv_bn_act(x, seq[0], seq[1], True, residual, transposed_sd=seq[0].stride[0], give=give)
-        key = _versions(seq)
-        c = self._dcache.get(name)
-        if c is None or c[0] != key:
-            c = (key,) + _prepare_deconv(seq[0], seq[1])
-            _publish_cache()
-            self._dcache[name] = c
-        _, packed, scale, shift, sd = c
-        cin, cout = seq[0].in_channels, seq[0].out_channels
-        # split-form transposed conv (csrc/conv3d_x3.hip) where it beats the fp32-MFMA kernel: conv7 / conv9 at real sizes; conv11
-        # (8 output channels fill half a matrix tile, and its fp32 kernel fuses the 1x1x1 prob) stays
-        if cout >= 16 and os.environ.get("MVS_CONV_X3", "1") != "0" and ops.deconv3d_x3_supported(cin, cout, sd) and x.shape[4] % 2 == 0 \
-                and 4 * x.shape[2] * x.shape[3] * x.shape[4] >= int(os.environ.get("MVS_CONV_X3_MIN_VOXELS", X3_MIN_VOXELS)) \
-                and x[0].numel() * 4 < _WINDOW and (residual is None or residual[0].numel() * 4 < 2 * _WINDOW):
-            px = self._dcache.get(name + ".x3")
-            if px is None or px[0] != key:
-                px = (key, ops.deconv3d_x3_pack(_f32c(seq[0].weight), sd))
-                _publish_cache()
-                self._dcache[name + ".x3"] = px
-            return ops.deconv3d_x3(x, px[1], cin, cout, sd, scale, shift, residual, relu=True)
-        return ops.deconv3d(x, packed, cin, cout, sd, scale, shift, residual, relu=True, tag="deconv3d_%dto%d_s%d" % (cin, cout, sd))
+        return self._layers[name].run(seq[0], seq[1], True, x, residual, _rs or route_switches())
 
     def logits(self, x: torch.Tensor) -> torch.Tensor:
-        """Eval-mode ``forward`` without the channel axis, ``[B,D,H,W]``: conv11 and the 1x1x1 ``prob`` run as ONE launch
-        (the 8-channel volume between them is never written) when the shape allows, else as two."""
-        y, skip = self._trunk(x)
-        seq = self.conv11
-        w, b = self.prob_params()
-        if not self.training and seq[0].out_channels == 8 and tuple(seq[0].stride) == (1, 2, 2) and y.shape[4] % 4 == 0 \
-                and os.environ.get("MVS_FUSE_PROB", "1") != "0":
-            key = _versions(seq)
-            c = self._dcache.get("conv11")
-            if c is None or c[0] != key:
-                c = (key,) + _prepare_deconv(seq[0], seq[1])
-                _publish_cache()
-                self._dcache["conv11"] = c
-            _, packed, scale, shift, _sd = c
-            # split form (csrc/tail_x3.hip) for the shape it is built for (16 -> 8) from X3_MIN_VOXELS up; MVS_TAIL=fp32 keeps the fp32-MFMA tail
-            # (the tail's window covers the whole batch of the skip volume: a larger call takes the fp32-MFMA tail below)
-            if seq[0].in_channels == 16 and os.environ.get("MVS_CONV_X3", "1") != "0" and os.environ.get("MVS_TAIL", "x3") == "x3" \
-                    and 4 * y.shape[2] * y.shape[3] * y.shape[4] >= int(os.environ.get("MVS_CONV_X3_MIN_VOXELS", X3_MIN_VOXELS)) \
-                    and skip.numel() * 4 < _WINDOW:
-                px = self._dcache.get("conv11.x3")
-                if px is None or px[0] != key:
-                    px = (key, ops.tail_x3_pack(_f32c(seq[0].weight)))
-                    _publish_cache()
-                    self._dcache["conv11.x3"] = px
-                return ops.tail_x3(y, px[1], scale, shift, skip, w, b, relu=True)
-            return ops.deconv3d_prob1(y, packed, seq[0].in_channels, scale, shift, skip, w, b, relu=True)
-        return ops.prob1(self._up("conv11", y, skip), w, b).squeeze(1)
+        """Eval-mode ``forward`` without the channel axis, ``[B,D,H,W]``: conv11 and the 1x1x1 ``prob`` as one launch where that is built."""
+        rs = None if self.training else route_switches()
+        y, skip = self._trunk(x, rs)
+        if self.training:
+            return ops.prob1(self._up("conv11", y, skip), *self.prob_params()).squeeze(1)
+        return self._layers["conv11"].run_tail(self.conv11[0], self.conv11[1], y, skip, *self.prob_params(), rs)
 
-    def _trunk(self, x: torch.Tensor):
-        """Everything up to conv9: returns (conv9 output, skip tensor of conv11 = the input volume)."""
-        if not isinstance(self.inner, nn.Identity):
-            raise MvsHipError("CostRegNet3D: in_channels != base_channel (1x1x1 'inner' conv) is not built")
-        x = x.to(torch.float32)
-        x = x if x.is_contiguous() else x.contiguous()
-        if x.shape[3] % 8 or x.shape[4] % 8:
-            raise MvsHipError("CostRegNet3D needs H, W divisible by 8 (three stride-2 levels), got %s" % (tuple(x.shape[3:]),))
-        c2 = self.conv2(self.conv1(x))
-        c4 = self.conv4(self.conv3(c2))
-        y = self.conv6(self.conv5(c4))
-        y = self._up("conv7", y, c4)
-        return self._up("conv9", y, c2), x
+    def _trunk(self, x: torch.Tensor, rs: Optional[RouteSwitches]):
+        """Everything up to conv9, without SkipLinks: returns (conv9 output, skip tensor of conv11 = the input volume)."""
+        x, _ = _volume_input(self, x, 2, False)
+        c2 = self.conv2(self.conv1(x, _rs=rs), _rs=rs)
+        c4 = self.conv4(self.conv3(c2, _rs=rs), _rs=rs)
+        y = self.conv6(self.conv5(c4, _rs=rs), _rs=rs)
+        y = self._up("conv7", y, c4, _rs=rs)
+        return self._up("conv9", y, c2, _rs=rs), x
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
-        if not isinstance(self.inner, nn.Identity):
-            raise MvsHipError("CostRegNet3D: in_channels != base_channel (1x1x1 'inner' conv) is not built")
-        pre16 = self.training and x.dtype == torch.bfloat16       # already bf16 channel-last [B,D,H,W,C] (autograd.AggregateFn as_bf16)
-        if not pre16:
-            x = x.to(torch.float32)
-        x = x if x.is_contiguous() else x.contiguous()
-        hw = x.shape[2:4] if pre16 else x.shape[3:]
-        if hw[0] % 8 or hw[1] % 8:
-            raise MvsHipError("CostRegNet3D needs H, W divisible by 8 (three stride-2 levels), got %s" % (tuple(hw),))
-        if self.training and autocast_bf16() and not pre16:
+        if not self.training:
+            rs = route_switches()
+            y, skip = self._trunk(x, rs)
+            return self._up("conv11", y, skip, _rs=rs)
+        x, pre16 = _volume_input(self, x, 2, True)
+        if autocast_bf16() and not pre16:
             from . import autograd as ag
             x = ag.ToBf16Fn.apply(x)                     # fp32 cost volume -> bf16 channel-last; every layer below follows the dtype
-        l0, l2, l4 = _skip_links(x) if self.training else (None,) * 3
+        l0, l2, l4 = _skip_links(x)
         c2 = _multi_use(self.conv2(self.conv1(x, take=l0)), l2)
         c4 = _multi_use(self.conv4(self.conv3(c2, take=l2)), l4)
         y = self.conv6(self.conv5(c4, take=l4))

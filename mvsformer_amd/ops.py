@@ -9,13 +9,12 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-import os
 from collections import defaultdict
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, switches as sw
 
 VIS_PARAM_FLOATS = 3689
 
@@ -182,9 +181,8 @@ def _cv_flags(exact: Optional[bool]) -> int:
     """bit 0 of the sweeps' ``flags``: 1 = the reference's op order with IEEE divisions and libm exp/log (the default: measured no
     slower than the shortcut form on MI355X, profiles/r03_bench_sweeps.txt), 0 = one reciprocal + Newton step and hardware
     exp2/log2 (``exact=False``, or MVS_CV_FAST=1 to flip the default)."""
-    import os
     if exact is None:
-        exact = os.environ.get("MVS_CV_FAST", "0") != "1"
+        exact = not sw.flag("MVS_CV_FAST")
     return 1 if exact else 0
 
 
@@ -1000,20 +998,19 @@ def cv_aggregate_bwd(feat_cl, rt, depth, weight, volume, gvolume, G: int, stats:
     B, V, H, W, C = feat_cl.shape
     D = depth.shape[1]
     dfeat = torch.zeros_like(feat_cl)
-    mode = os.environ.get("MVS_CV_BWD", "own")
     if gvolume.dtype == torch.bfloat16:
         # (the default scatter kernel reading this form directly was built and measured: its strided 2-byte loads cost it 0.3 ms per step,
         #  three times what the conversion pass costs - NOTEBOOK.md)
         gvolume = bf16_to_f32(_chk16(gvolume, "grad"))
     _chk(gvolume, "grad")
-    if mode not in ("own", "lds", "direct"):
-        raise _lib.MvsHipError("MVS_CV_BWD=%r: expected 'own', 'lds' or 'direct'" % mode)
+    mode = sw.text("MVS_CV_BWD", error=_lib.MvsHipError)      # own | lds | direct
     if mode != "direct":
         # "own" (default): per-wavefront LDS windows with owner election - no atomics in the common case; "lds": block-shared window with
         # LDS float atomics; "direct": global atomics with per-lane run merging (DESIGN.md §4.5 for the measurements).
         # MVS_CV_BWD_WINDOW="log2(WX),WY" overrides the texel window.
         own = mode == "own"
-        wxl, wy = (int(v) for v in os.environ.get("MVS_CV_BWD_WINDOW", "5,20" if own else "6,24").split(","))
+        window = sw.text("MVS_CV_BWD_WINDOW")
+        wxl, wy = (int(v) for v in (("5,20" if own else "6,24") if window is None else window).split(","))
         part = torch.empty((C // 8,) + tuple(weight.shape), device=weight.device, dtype=torch.float32)
         fn = "mvs_cv_aggregate_bwd_own" if own else "mvs_cv_aggregate_bwd_lds"
         _call(fn, "cv_aggregate_bwd_%s_kernel<%d>" % (mode, C), _ptr(feat_cl), _ptr(rt), _ptr(depth), _ptr(weight),
@@ -1563,7 +1560,7 @@ def bf16_conv3d_wgrad(A: torch.Tensor, Bt: torch.Tensor, stride, taps: int = 27,
     if nws <= 0:
         raise _lib.MvsHipError("bf16 wgrad: channels must be 8/16/32/64 (CA=%d CB=%d)" % (CA, CB))
     ws = torch.empty(nws, device=A.device, dtype=torch.uint8)
-    name = "bf16_wgrad_kernel" if os.environ.get("MVS_TAG_SHAPES", "0") != "1" else \
+    name = "bf16_wgrad_kernel" if not sw.flag("MVS_TAG_SHAPES") else \
         "bf16_wgrad<%d,%d,s%d%d,%dx%dx%dx%d>" % (CA, CB, stride[0], stride[1], N, Dp, Hp, Wp)
     tag = (name, "flops", 2.0 * taps * CA * CB * N * Dp * Hp * Wp)
     _call("mvs_bf16_conv3d_wgrad_taps", tag, _ptr(A), _ptr(Bt), _ptr(dW), _ptr(ws), N, CA, CB, cb_out, Dp, Hp, Wp, Db, Hb, Wb, stride[0],

@@ -19,12 +19,11 @@ hypotheses a random-weight cascade predicts).
 """
 from __future__ import annotations
 
-import os
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, switches as sw
 from ._lib import MvsHipError
 from .module import ConvBnReLU, CostRegNet, CostRegNet3D, _versions, pack_vis_params
 
@@ -43,8 +42,8 @@ def _store_plan(feat_cl, D, G) -> int:
 
 def _store_plan_bytes(nbytes: int, H: int) -> int:
     """:func:`_store_plan` from the store's size (``ops.cv_store_bytes``; <= 0: not built for the shape) and the image height."""
-    limit = float(os.environ.get("MVS_CV_STORE_MAX_MB", "160")) * 2 ** 20
-    max_bands = int(os.environ.get("MVS_CV_STORE_BANDS", "1"))
+    limit = sw.number("MVS_CV_STORE_MAX_MB") * 2 ** 20
+    max_bands = sw.integer("MVS_CV_STORE_BANDS")
     if nbytes <= 0 or limit <= 0:
         return 0
     if nbytes <= limit:
@@ -79,13 +78,11 @@ class StageNet(nn.Module):
 
     def _vis_params(self):
         """-> (parameter block, the 3x3 layers' weights prepared for the selected kernel or None for the all-VALU form)."""
-        key = _versions(self.vis)
+        # MVS_VIS = x3 (default: split-form bf16 MFMA) | wino (Winograd fp32 MFMA) | valu (the all-VALU reference form)
+        mode = sw.text("MVS_VIS") or ("x3" if sw.flag("MVS_VIS_WINO") else "valu")
+        key = (_versions(self.vis), mode)
         if self._vis_cache is None or self._vis_cache[0] != key:
             params = pack_vis_params(self.vis)
-            # MVS_VIS = x3 (default: split-form bf16 MFMA) | wino (Winograd fp32 MFMA) | valu (the all-VALU reference form)
-            mode = os.environ.get("MVS_VIS", "x3" if os.environ.get("MVS_VIS_WINO", "1") != "0" else "valu")
-            if mode not in ("x3", "wino", "valu"):
-                raise ValueError("MVS_VIS must be x3, wino or valu, not %r" % mode)
             prepared = ops.vis_x3_prepare(params) if mode == "x3" else ops.vis_wino_prepare(params) if mode == "wino" else None
             from .module import _publish_cache
             _publish_cache()                                    # cached tensors are read from any stream afterwards
@@ -120,7 +117,7 @@ class StageNet(nn.Module):
         # Sweep plan per stage: MVS_CV_TILED=1 opts into the LDS-tiled sweeps (they lose on the noisy hypotheses a
         # random-weight cascade predicts); coarse stages whose per-view correlation volumes fit the Infinity Cache keep them
         # (mvs_cv_corr_fwd) and merge by streaming (mvs_cv_merge_fwd); everything else recomputes the correlation in sweep B.
-        tiled = os.environ.get("MVS_CV_TILED", "0") == "1" and ops.cv_tiled_supported(feat)
+        tiled = sw.flag("MVS_CV_TILED") and ops.cv_tiled_supported(feat)
         if tiled:                                               # LDS-tiled sweeps straight from the decoder's NCHW maps
             entropy = ops.cv_tiled_entropy(feat, rt, hyp, G)
             weight = self._vis_weight(entropy, vis_params, vis_prepared)

@@ -13,14 +13,13 @@ multiply and one mean over 6 heads).  ``mvsformer_amd.install(features=True)`` r
 from __future__ import annotations
 
 import math
-import os
 from functools import partial
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, ops, switches as sw
 from .module import _publish_cache, _versions
 
 
@@ -122,7 +121,7 @@ class VisionTransformer(nn.Module):
     def _packed_ok(self) -> bool:
         """The pre-split path (csrc/vit_packed.hip) covers heads of 64 with C a multiple of 128 up to 512 (ViT-small)."""
         C, NH = self.embed_dim, self.num_heads
-        return C == NH * 64 and C % 128 == 0 and C <= 512 and os.environ.get("MVS_VIT_PACKED", "1") != "0"
+        return C == NH * 64 and C % 128 == 0 and C <= 512 and sw.flag("MVS_VIT_PACKED")
 
     def _run_packed(self, x: torch.Tensor, want_cls: bool):
         """The 12 blocks on pre-split operands: LayerNorm -> packed, qkv GEMM -> packed Q / K / V^T per head, flash attention -> packed,
@@ -194,7 +193,7 @@ class VisionTransformer(nn.Module):
             qkv = torch.empty(B, N, 3 * C, device=x.device, dtype=torch.float32)
             ops.gemm_x3(y, qw, qkv, B * N, 3 * C, C, C, C, 3 * C, shift=qb)
             last = want_att and i == len(blocks) - 1
-            if hd == 64 and not last and os.environ.get("MVS_VIT_FLASH", "1") != "0":
+            if hd == 64 and not last and sw.flag("MVS_VIT_FLASH"):
                 # flash form: softmax(Q K^T / sqrt(hd)) V without the N x N matrix (csrc/vit.hip attention_x3_kernel); V handed over
                 # TRANSPOSED with 16-byte aligned rows ([B, heads, hd, N rounded up to 4], one strided copy into a buffer reused by all blocks)
                 vt_pad = ops.attention_vt(qkv, NH, vt_pad)
@@ -316,7 +315,7 @@ def attention_flash_train_bwd(qkv: torch.Tensor, out: torch.Tensor, lse: torch.T
 
 
 def _train_flash_on() -> bool:
-    return os.environ.get("MVS_VIT_TRAIN_FLASH", "1") != "0"
+    return sw.flag("MVS_VIT_TRAIN_FLASH")
 
 
 class _ViTTrainFn(torch.autograd.Function):
@@ -605,7 +604,7 @@ class VITDecoderStage4Single(nn.Module):
     def _packed_ok(self) -> bool:
         a, d = self.attn, self.decoder
         chans = (a.conv_r[0].in_channels, a.proj.out_channels, d[0].out_channels)
-        return all(c % 32 == 0 for c in chans) and d[3].out_channels % 4 == 0 and os.environ.get("MVS_VIT_PACKED", "1") != "0"
+        return all(c % 32 == 0 for c in chans) and d[3].out_channels % 4 == 0 and sw.flag("MVS_VIT_PACKED")
 
     def _forward_packed(self, p, xc, ac):
         """The decoder on pre-split operands: every convolution is an implicit GEMM whose A operand is gathered from a packed channel-last map

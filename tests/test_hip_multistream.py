@@ -22,8 +22,6 @@ def _reset_caches(net):
     for mod in net.modules():
         if hasattr(mod, "_cache"):
             mod._cache = None
-        if hasattr(mod, "_dcache"):
-            mod._dcache = {}
         if hasattr(mod, "_vis_cache"):
             mod._vis_cache = None
 

@@ -263,7 +263,6 @@ def test_costregnet3d_logits_paths_agree(dev):
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         try:
-            net._dcache = {}
             outs.append(net.logits(x))
         finally:
             for k, v in old.items():
