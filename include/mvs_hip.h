@@ -46,7 +46,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 46
+#define MVS_ABI_VERSION 47
 
 typedef void* mvs_stream_t;
 
@@ -569,6 +569,18 @@ int64_t mvs_fpn_level_cp_prepared_bytes(int Ck);
 int mvs_fpn_level_cp_prepare(const float* w3, const float* wc, const float* scale, int Ck, void* prepared, mvs_stream_t stream);
 int mvs_fpn_level_cp(const float* intra_prev, const float* lateral, const void* prepared, const float* shift, const float* border, int N,
                      int Ck, int h, int w, float* out, mvs_stream_t stream);
+/* The full-resolution tail of FPNDecoderV2, models/module.py:299-300 (feat_chs[:2] = [8,16]), as one kernel (csrc/fpn_v2_tail.hip):
+ *   out4 = Swish(BN4(conv3x3(ReLU(BN3(ConvTranspose2d(k 4, s 2, p 1)(out3))) + conv01))), channel-last in and out, fp32 FMAs; the up map stays
+ * in LDS, its positions outside the image are the 3x3 convolution's zero padding.  Channel counts other than Cin -> Cmid -> Cout = 16 -> 8 -> 8
+ * return MVS_EINVAL (prepared_bytes: -1).  scale_* = gamma / sqrt(var + eps), shift_* = beta + (conv bias - mean) * scale_*.
+ *   prepare: wt [16,8,4,4] (upsample3.0.weight), scale_up [8], w3 [8,8,3,3] (out4.0.weight), scale_out [8] -> prepared,
+ *            mvs_fpn_v2_tail_prepared_bytes(16, 8, 8) bytes
+ *   tail:    out3 [N,h,w,16], conv01 [N,2h,2w,8], shift_up [8], shift_out [8] -> out [N,2h,2w,8] */
+int64_t mvs_fpn_v2_tail_prepared_bytes(int Cin, int Cmid, int Cout);
+int mvs_fpn_v2_tail_prepare(const float* wt, const float* scale_up, const float* w3, const float* scale_out, int Cin, int Cmid, int Cout,
+                            void* prepared, mvs_stream_t stream);
+int mvs_fpn_v2_tail(const float* out3, const float* conv01, const void* prepared, const float* shift_up, const float* shift_out, int N, int Cin,
+                    int Cmid, int Cout, int h, int w, float* out, mvs_stream_t stream);
 /* conv00 / conv01 (the two full-resolution layers: (Cin,Cout,K,stride) = (3,8,7,1), (8,8,5,1)) in three-term bf16 split form (csrc/conv2d_x3.hip):
  * same contract as mvs_conv2d_bn_lrelu - fp32 NCHW in and out, fp32-equivalent - with the BatchNorm scale folded into the pre-split weights.
  *   prepare: w [8,Cin,K,K], scale [8] -> prepared, mvs_conv2d_x3_prepared_bytes(Cin, 8, K) bytes

@@ -13,7 +13,7 @@ from . import synth  # noqa: F401
 __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "CascadeMVS", "homo_warping_3D_with_mask",
            "homo_warping_3D", "homo_warping", "depth_regression", "conf_regression", "init_inverse_range",
            "schedule_inverse_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
-           "VITDecoderStage4Single", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference"]
+           "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference"]
 
 
 def __getattr__(name):
@@ -33,7 +33,7 @@ def __getattr__(name):
     if name in ("FPNDecoder", "FPNDecoderV2", "FPNEncoder"):
         from . import fpn
         return getattr(fpn, name)
-    if name in ("vit_small", "VisionTransformer", "VITDecoderStage4Single"):
+    if name in ("vit_small", "VisionTransformer", "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt"):
         from . import vit
         return getattr(vit, name)
     if name == "DINOMVSNet":

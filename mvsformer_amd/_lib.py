@@ -20,7 +20,7 @@ from . import switches as sw
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = sw.text("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 from ctypes import c_double  # noqa: E402
 
@@ -217,6 +217,9 @@ SIGNATURES = {
     "mvs_fpn_level_cp_prepared_bytes": (L, [I]),
     "mvs_fpn_level_cp_prepare": (I, [P, P, P, I, P, P]),
     "mvs_fpn_level_cp": (I, [P, P, P, P, P, I, I, I, I, P, P]),
+    "mvs_fpn_v2_tail_prepared_bytes": (L, [I, I, I]),
+    "mvs_fpn_v2_tail_prepare": (I, [P, P, P, P, I, I, I, P, P]),
+    "mvs_fpn_v2_tail": (I, [P, P, P, P, P, I, I, I, I, I, I, P, P]),
     "mvs_conv2d_x3s_supported": (I, [I, I, I, I]),
     "mvs_conv2d_x3s_prepared_bytes": (L, [I, I, I, I]),
     "mvs_conv2d_x3s_prepare": (I, [P, P, I, I, I, I, P, P]),

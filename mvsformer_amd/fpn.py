@@ -198,7 +198,8 @@ class FPNDecoderV2(nn.Module):
     concatenation [decoder map | transformer map], joined by ConvTranspose2d(4, 2, 1) + BatchNorm + ReLU upsamplings with the encoder
     maps added.  Eval mode on the split-form implicit GEMMs of csrc/vit.hip (``mvs_gemm_x3``: 3x3 convolution = A rows gathered from the
     channel-last map, the transposed convolution = four output-parity classes of 2x2 taps; BatchNorm folded, activation in the epilogue):
-    fp32-equivalent.  ``forward(conv01, conv11, conv21, conv31, vit1, vit2, vit3) -> [out1 (1/8), out2 (1/4), out3 (1/2), out4 (full)]``,
+    fp32-equivalent; the full-resolution tail (``upsample3`` + ``conv01`` + ``out4``) is one fused kernel (csrc/fpn_v2_tail.hip) unless
+    ``MVS_FPN_V2_TAIL=0``.  ``forward(conv01, conv11, conv21, conv31, vit1, vit2, vit3) -> [out1 (1/8), out2 (1/4), out3 (1/2), out4 (full)]``,
     logical NCHW over channel-last memory.  Training mode (``_forward_train``): batch-statistics BatchNorm, every gradient, fp32 NCHW.  (Twins
     itself cannot be pinned here: models/gvt.py needs timm.)"""
 
@@ -214,10 +215,11 @@ class FPNDecoderV2(nn.Module):
         self.out3 = nn.Sequential(nn.Conv2d(c[1] * 2, c[1], kernel_size=3, padding=1), nn.BatchNorm2d(c[1]), Swish())
         self.upsample3 = nn.Sequential(nn.ConvTranspose2d(c[1], c[0], kernel_size=4, stride=2, padding=1), nn.BatchNorm2d(c[0]), nn.ReLU(True))
         self.out4 = nn.Sequential(nn.Conv2d(c[0], c[0], kernel_size=3, padding=1), nn.BatchNorm2d(c[0]), Swish())
+        self._tail_chs = c[:2] == [8, 16]                     # what csrc/fpn_v2_tail.hip is built for (every shipped config)
         self._cache = None
 
     def _prepared(self):
-        from .vit import _conv3_matrix, _convT_matrices, _fold
+        from .vit import _conv3_matrix, _convT_matrices, _f, _fold
         key = _versions(self)
         if self._cache is None or self._cache[0] != key:
             prep = {}
@@ -227,6 +229,8 @@ class FPNDecoderV2(nn.Module):
             for k in (1, 2, 3):
                 seq = getattr(self, "upsample%d" % k)
                 prep["up%d" % k] = (_convT_matrices(seq[0].weight), _fold(seq[0], seq[1]))
+            if self._tail_chs and sw.flag("MVS_FPN_V2_TAIL"):       # the full-resolution tail as one kernel (csrc/fpn_v2_tail.hip)
+                prep["tail"] = ops.fpn_v2_tail_prepare(_f(self.upsample3[0].weight), prep["up3"][1], _f(self.out4[0].weight), prep["out4"][1])
             _publish_cache()
             self._cache = (key, prep)
         return self._cache[1]
@@ -277,6 +281,9 @@ class FPNDecoderV2(nn.Module):
             for k, (skip, vit) in enumerate(((conv21, vit2), (conv11, vit3), (conv01, None)), start=1):
                 out = self._conv3(x, *p["out%d" % k])
                 outs.append(out)
+                if vit is None and "tail" in p:               # MVS_FPN_V2_TAIL (default): upsample3 + conv01 + out4 fused, the up map never written
+                    outs.append(ops.fpn_v2_tail(out, cl(skip), *p["tail"]))
+                    break
                 up = VITDecoderStage4Single._up(out, p["up%d" % k][0], p["up%d" % k][1], ACT_RELU_GEMM)      # [B,2h,2w,C/2]
                 s = cl(skip)
                 if vit is None:
@@ -286,7 +293,8 @@ class FPNDecoderV2(nn.Module):
                     x = torch.empty(up.shape[:-1] + (2 * C,), device=up.device, dtype=torch.float32)
                     torch.add(up, s, out=x[..., :C])
                     x[..., C:] = cl(vit)
-            outs.append(self._conv3(x, *p["out4"]))
+            if len(outs) == 3:
+                outs.append(self._conv3(x, *p["out4"]))
         return [o.permute(0, 3, 1, 2) for o in outs]
 
 

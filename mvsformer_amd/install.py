@@ -30,15 +30,17 @@ _SYMBOLS = {
 }
 # the rows before the path: rebound on request (eval and training mode are both built; the ViT itself is frozen / eval-only)
 _FEATURE_SYMBOLS = {"FPNDecoder": _f.FPNDecoder, "FPNDecoderV2": _f.FPNDecoderV2, "FPNEncoder": _f.FPNEncoder,
-                    "VITDecoderStage4Single": _v.VITDecoderStage4Single}
+                    "VITDecoderStage4Single": _v.VITDecoderStage4Single, "VITDecoderStage4": _v.VITDecoderStage4,
+                    "VITDecoderStage4NoAtt": _v.VITDecoderStage4NoAtt}
 # DINOMVSNet builds its backbone as ``vits.__dict__[vit_arch](...)`` (mvsformer_model.py:180): the factory is rebound in that module
 _VIT_MODULE, _VIT_FACTORIES = "models.vision_transformer", {"vit_small": _v.vit_small}
 
 
 def install(model_module: str = "models.mvsformer_model", also=("models.module", "models.warping"), features: bool = False) -> dict:
     """Rebind the hot-path names inside the reference's modules.  Returns ``{module: [names rebound]}``.
-    ``features=True`` also rebinds ``FPNEncoder`` / ``FPNDecoder`` / ``VITDecoderStage4Single``, the ``vit_small`` factory of
-    ``models.vision_transformer`` (the DINO branch of MVSFormer-P) and ``DINOMVSNet`` itself.  The FPN and the ViT decoder run in eval AND
+    ``features=True`` also rebinds ``FPNEncoder`` / ``FPNDecoder`` / ``FPNDecoderV2``, the three ViT decoders (``VITDecoderStage4Single`` /
+    ``VITDecoderStage4`` / ``VITDecoderStage4NoAtt``), the ``vit_small`` factory of ``models.vision_transformer`` (the DINO branch of MVSFormer-P)
+    and ``DINOMVSNet`` itself, which takes ``multi_scale`` and ``att_fusion`` as the reference's class does.  The FPN and the ViT decoder run in eval AND
     training mode; the ViT is eval-only (MVSFormer-P freezes it, ``"fix": true``; a model that fine-tunes the ViT must keep the reference's)."""
     done = {}
     symbols = dict(_SYMBOLS, **(_FEATURE_SYMBOLS if features else {}))

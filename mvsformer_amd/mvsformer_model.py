@@ -6,8 +6,10 @@ constructor arguments (``configs/config_mvsformer-p.json`` ``arch.args``), sub-m
 Composition only: every piece is a HIP-backed module of this package (``FPNEncoder`` / ``FPNDecoder`` csrc/conv2d.hip + fpn.hip, the DINO
 ViT-small branch csrc/vit_packed.hip, the four ``StageNet``s).  Eval mode runs the V views of all B samples as ONE batch through the 2-D
 networks (the reference loops over views, mvsformer_model.py:238-271; with eval BatchNorm the results per image are the same) and hands the
-feature maps to the cascade channel-last.  Only what the shipped MVSFormer-P config builds is built: ``multi_scale=False``, ``att_fusion=True``,
-``vit_arch='vit_small'``; Twins (``TwinMVSNet``) needs ``timm``.  ``"fix": false`` trains the ViT too (mvsformer_model.py:219), and
+feature maps to the cascade channel-last.  The constructor's variants are the reference's (mvsformer_model.py:173-176,195-201): ``multi_scale=True``
+feeds the ViT into the three coarse pyramid levels (``VITDecoderStage4`` + ``FPNDecoderV2``, whose full-resolution tail is csrc/fpn_v2_tail.hip),
+``att_fusion=False`` replaces the attention fusion by ``VITDecoderStage4NoAtt``; both together crash in the reference's forward and are refused
+here at construction.  ``vit_arch='vit_small'`` only; Twins (``TwinMVSNet``) needs ``timm``.  ``"fix": false`` trains the ViT too (mvsformer_model.py:219), and
 ``vit_args['vit_path']`` loads the pretrained DINO weights (mvsformer_model.py:182-193).
 """
 from __future__ import annotations
@@ -19,8 +21,8 @@ import torch.nn as nn
 
 from . import _lib
 from .cascade import CascadeMVS
-from .fpn import FPNDecoder, FPNEncoder
-from .vit import VITDecoderStage4Single, vit_branch, vit_small
+from .fpn import FPNDecoder, FPNDecoderV2, FPNEncoder
+from .vit import VITDecoderStage4, VITDecoderStage4NoAtt, VITDecoderStage4Single, vit_branch, vit_small
 
 
 def _load_vit_weights(vit, path: str) -> None:
@@ -44,17 +46,23 @@ class DINOMVSNet(CascadeMVS):
     def __init__(self, args: dict):
         super().__init__(args)                               # ndepths, depth_interals_ratio, fusions (mvsformer_model.py:166-170,203)
         a = self.args
-        if a.get("multi_scale", False):
-            raise _lib.MvsHipError("DINOMVSNet: multi_scale=True (VITDecoderStage4 + FPNDecoderV2 wiring) is not built; no shipped DINO config uses it")
+        self.multi_scale = bool(a.get("multi_scale", False))
         va = dict(a["vit_args"])
-        if va.get("vit_arch", "vit_small") != "vit_small" or not va.get("att_fusion", True) or va.get("twin", False):
-            raise _lib.MvsHipError("DINOMVSNet: only vit_arch='vit_small' with att_fusion=True is built (configs/config_mvsformer-p.json)")
+        if va.get("vit_arch", "vit_small") != "vit_small" or va.get("twin", False):
+            raise _lib.MvsHipError("DINOMVSNet: only vit_arch='vit_small' is built (configs/config_mvsformer-p.json)")
+        att_fusion = bool(va.get("att_fusion", True))
+        if self.multi_scale and not att_fusion:
+            raise _lib.MvsHipError("DINOMVSNet: multi_scale=True with att_fusion=False is not a model: the reference builds VITDecoderStage4NoAtt, which "
+                                   "returns one map, and its forward unpacks three (mvsformer_model.py:195-196,225,256)")
         self.vit_args = va
         self.encoder = FPNEncoder(feat_chs=a["feat_chs"])
-        self.decoder = FPNDecoder(feat_chs=a["feat_chs"])
+        self.decoder = (FPNDecoderV2 if self.multi_scale else FPNDecoder)(feat_chs=a["feat_chs"])
         self.vit = vit_small(patch_size=va["patch_size"], qk_scale=va["qk_scale"])
         _load_vit_weights(self.vit, va.get("vit_path", ""))
-        self.decoder_vit = VITDecoderStage4Single(va)
+        if not att_fusion:
+            self.decoder_vit = VITDecoderStage4NoAtt(va)
+        else:
+            self.decoder_vit = (VITDecoderStage4 if self.multi_scale else VITDecoderStage4Single)(va)
         fusions = self.fusions                               # registered last, as the reference does (state_dict key ORDER too)
         del self.fusions
         self.fusions = fusions
@@ -85,8 +93,11 @@ class DINOMVSNet(CascadeMVS):
             vit_out = self.decoder_vit(feat, vb["att_cls"].reshape(B * V, -1, hp, wp))
         else:
             vit_out = vb["vit_out"]
-        conv31 = conv31 + vit_out                            # mvsformer_model.py:229,263
-        feats = self.decoder(conv01, conv11, conv21, conv31)
+        if self.multi_scale:                                 # mvsformer_model.py:224-226,255-257: the three ViT maps join the decoder's levels
+            feats = self.decoder(conv01, conv11, conv21, conv31, *vit_out)
+        else:
+            conv31 = conv31 + vit_out                        # mvsformer_model.py:229,263
+            feats = self.decoder(conv01, conv11, conv21, conv31)
         return {"stage%d" % (i + 1): f.reshape(B, V, *f.shape[1:]) for i, f in enumerate(feats)}
 
     def forward(self, imgs, proj_matrices, depth_values, tmp=2.0):

@@ -1872,6 +1872,39 @@ def fpn_level_cp(intra_prev_cl: torch.Tensor, lateral_cl: torch.Tensor, prepared
     return out
 
 
+def fpn_v2_tail_prepare(w_up: torch.Tensor, fold_up, w_out: torch.Tensor, fold_out):
+    """Operands of :func:`fpn_v2_tail` from ``upsample3.0.weight [16,8,4,4]``, ``out4.0.weight [8,8,3,3]`` and the two folded BatchNorms
+    ``(scale, shift)``: the weight tables with the scales folded in (csrc/fpn_v2_tail.hip) and the two shifts."""
+    _chk(w_up, "transposed convolution weight"), _chk(w_out, "3x3 weight")
+    for t in (*fold_up, *fold_out):
+        _chk(t, "scale / shift")
+    Cin, Cmid, Cout = w_up.shape[0], w_up.shape[1], w_out.shape[0]
+    n = int(_lib.load().mvs_fpn_v2_tail_prepared_bytes(Cin, Cmid, Cout))
+    if n <= 0 or w_up.shape != (Cin, Cmid, 4, 4) or w_out.shape != (Cout, Cmid, 3, 3) or fold_up[0].numel() != Cmid or fold_out[0].numel() != Cout:
+        raise _lib.MvsHipError("fpn_v2_tail_prepare: unsupported weights %s, %s" % (tuple(w_up.shape), tuple(w_out.shape)))
+    prepared = torch.empty(n, device=w_up.device, dtype=torch.uint8)
+    _call("mvs_fpn_v2_tail_prepare", None, _ptr(w_up.contiguous()), _ptr(fold_up[0]), _ptr(w_out.contiguous()), _ptr(fold_out[0]), Cin, Cmid, Cout,
+          _ptr(prepared), _stream())
+    return prepared, fold_up[1].contiguous(), fold_out[1].contiguous(), (Cin, Cmid, Cout)
+
+
+def fpn_v2_tail(out3_cl: torch.Tensor, conv01_cl: torch.Tensor, prepared: torch.Tensor, shift_up: torch.Tensor, shift_out: torch.Tensor, chans) -> torch.Tensor:
+    """``Swish(BN(conv3x3(ReLU(BN(ConvTranspose2d(out3))) + conv01)))`` (models/module.py:299-300) in one kernel, channel-last:
+    ``out3_cl [N,h,w,16]``, ``conv01_cl [N,2h,2w,8]`` -> ``[N,2h,2w,8]``."""
+    _chk(out3_cl, "out3"), _chk(conv01_cl, "conv01"), _chk(prepared, "prepared", torch.uint8), _chk(shift_up, "shift"), _chk(shift_out, "shift")
+    Cin, Cmid, Cout = chans
+    N, h, w, C = out3_cl.shape
+    if C != Cin or conv01_cl.shape != (N, 2 * h, 2 * w, Cmid):
+        raise _lib.MvsHipError("fpn_v2_tail: out3 [N,h,w,%d] %s needs conv01 [N,2h,2w,%d], got %s" % (Cin, tuple(out3_cl.shape), Cmid, tuple(conv01_cl.shape)))
+    if prepared.numel() != int(_lib.load().mvs_fpn_v2_tail_prepared_bytes(Cin, Cmid, Cout)) or shift_up.numel() != Cmid or shift_out.numel() != Cout:
+        raise _lib.MvsHipError("fpn_v2_tail: operands do not match %d -> %d -> %d channels" % chans)
+    out = torch.empty(N, 2 * h, 2 * w, Cout, device=out3_cl.device, dtype=torch.float32)
+    tag = ("fpn_v2_tail_kernel", "flops", 2.0 * (4 * Cin * Cmid + 9 * Cmid * Cout) * N * 4 * h * w)
+    _call("mvs_fpn_v2_tail", tag, _ptr(out3_cl), _ptr(conv01_cl), _ptr(prepared), _ptr(shift_up), _ptr(shift_out), N, Cin, Cmid, Cout, h, w, _ptr(out),
+          _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- FPN encoder layers
 def conv2d_x3s_supported(Cin: int, Cout: int, K: int, stride: int) -> bool:
     return bool(_lib.load().mvs_conv2d_x3s_supported(Cin, Cout, K, stride))

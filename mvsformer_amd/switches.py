@@ -49,6 +49,8 @@ _ROWS = (
     # feature extraction
     Switch("MVS_FPN_X3", "1", "str", "`0` = the FPN's full-resolution layers on the fp32 matrix cores; `strip` = the decoder's last level as the split-form "
            "strip kernel (`csrc/fpn_x3.hip`) instead of the contraction-first kernel (`csrc/fpn_cp.hip`)", "pack"),
+    Switch("MVS_FPN_V2_TAIL", True, "on", "`0` = `FPNDecoderV2`'s full-resolution tail through the generic split-form GEMMs (up map written, added, read back) "
+           "instead of the fused kernel (`csrc/fpn_v2_tail.hip`)", "pack"),
     Switch("MVS_VIT_PACKED", True, "on", "`0` = the ViT with operands split inside every GEMM block instead of pre-split"),
     Switch("MVS_VIT_FLASH", True, "on", "`0` = materialized attention in every block of the unpacked eval ViT (`MVS_VIT_PACKED=0`)"),
     Switch("MVS_VIT_TRAIN_FLASH", True, "on", "`0` = ViT training (`\"fix\": false`) with materialized attention instead of `csrc/vit_flash_train.hip`"),

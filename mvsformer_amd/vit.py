@@ -8,7 +8,8 @@ matrix product - patch embedding, QKV, attention scores, attention x V, projecti
 convolutions as implicit GEMMs - runs in ``csrc/vit.hip`` on the bf16 matrix cores in three-term split form (fp32-equivalent), LayerNorm,
 softmax and the bicubic resizes are HIP kernels too; torch only reshapes / concatenates / slices (no arithmetic beyond one broadcast
 multiply and one mean over 6 heads).  ``mvsformer_amd.install(features=True)`` rebinds ``models.vision_transformer.vit_small`` and
-``VITDecoderStage4Single``.  Twins (``models/gvt.py``) needs ``timm`` and is not built.
+``VITDecoderStage4Single``, and the decoders of the ``multi_scale`` / ``att_fusion: false`` variants: ``VITDecoderStage4`` (:305-350) and
+``VITDecoderStage4NoAtt`` (:371-386).  Twins (``models/gvt.py``) needs ``timm`` and is not built.
 """
 from __future__ import annotations
 
@@ -569,46 +570,68 @@ class MulFn(torch.autograd.Function):
 ACT_GELU_BN = 4                          # GELU(erf) in the fp32 BatchNorm kernels (csrc/train.hip); 3 = Swish
 
 
-class VITDecoderStage4Single(nn.Module):
-    """models/module.py:353-368: ``forward(x [B,vit_ch,h,w], att [B,nhead,h,w]) -> [B,out_ch,4h,4w]`` (added to ``conv31``)."""
+def _fold_up(conv, bn):
+    """(scale, shift) of a transposed convolution's epilogue: its bias, through the BatchNorm ``bn`` where one follows (None: the raw output)."""
+    if bn is not None:
+        return _fold(conv, bn)
+    return torch.ones_like(conv.bias, dtype=torch.float32).contiguous(), _f(conv.bias)
 
-    def __init__(self, args):
-        super().__init__()
-        ch, vit_ch = args["out_ch"], args["vit_ch"]
-        assert args["att_fusion"] is True
-        self.attn = AttentionFusionSimple(vit_ch, ch * 4, args["nhead"])
-        self.decoder = nn.Sequential(nn.ConvTranspose2d(ch * 4, ch * 2, 4, stride=2, padding=1), nn.BatchNorm2d(ch * 2), nn.GELU(),
-                                     nn.ConvTranspose2d(ch * 2, ch, 4, stride=2, padding=1), nn.BatchNorm2d(ch), nn.GELU())
-        self._cache = None
+
+class _DecoderBase(nn.Module):
+    """What the ViT decoders of models/module.py:305-386 share on the HIP path: ``AttentionFusionSimple`` (:450-466) and chains of
+    ``ConvTranspose2d(4, 2, 1)`` (+ BatchNorm + GELU), in eval as implicit GEMMs - on pre-split operands (``mvs_conv_x3p``) where the channel
+    counts allow it, ``_up`` (``mvs_gemm_x3``) otherwise - and in training as autograd-tracked HIP ops."""
+
+    def _ups(self):
+        """The transposed convolutions of the module: ``[(name, conv, bn or None)]``, ``bn`` = the BatchNorm whose (+ GELU's) output the NEXT layer
+        of that chain reads - folded into the epilogue of the layer's run that feeds it."""
+        raise NotImplementedError
+
+    def _mid_channels(self):
+        """Channel counts of every map a transposed convolution READS (packed K) and of the fp32 outputs."""
+        reads = [conv.in_channels for _, conv, _ in self._ups()]
+        return reads, [conv.out_channels for _, conv, _ in self._ups()]
+
+    def _packed_ok(self) -> bool:
+        reads, outs = self._mid_channels()
+        a = getattr(self, "attn", None)
+        chans = list(reads) + ([a.conv_r[0].in_channels, a.proj.out_channels] if a is not None else [])
+        return all(c % 32 == 0 for c in chans) and all(c % 4 == 0 for c in outs) and sw.flag("MVS_VIT_PACKED")
 
     def _prepared(self):
         key = _versions(self)
         if self._cache is None or self._cache[0] != key:
-            a = self.attn
-            cl_in = a.conv_l[0].in_channels
-            cp = (cl_in + 7) // 8 * 8
-            prep = dict(cp=cp, wl=_conv3_matrix(a.conv_l[0].weight, cp), fl=_fold(a.conv_l[0], a.conv_l[1]),
-                        wr=_conv3_matrix(a.conv_r[0].weight, a.conv_r[0].in_channels), fr=_fold(a.conv_r[0], a.conv_r[1]),
-                        wp=_f(a.proj.weight).reshape(a.proj.out_channels, -1), bp=_f(a.proj.bias),
-                        w1=_convT_matrices(self.decoder[0].weight), f1=_fold(self.decoder[0], self.decoder[1]),
-                        w2=_convT_matrices(self.decoder[3].weight), f2=_fold(self.decoder[3], self.decoder[4]))
-            if self._packed_ok():
-                # the same matrices split once into MFMA fragments (csrc/vit_packed.hip; channels of the [x | att] map padded to a multiple of 32)
-                cpp = (cl_in + 31) // 32 * 32
-                prep.update(cpp=cpp, wl_p=ops.x3p_pack(_conv3_matrix(a.conv_l[0].weight, cpp)), wr_p=ops.x3p_pack(prep["wr"]), wp_p=ops.x3p_pack(prep["wp"]),
-                            w1_p=ops.x3p_pack_classes(prep["w1"], 128), w2_p=ops.x3p_pack_classes(prep["w2"], 128))
+            packed = self._packed_ok()
+            prep = dict(packed=packed)
+            a = getattr(self, "attn", None)
+            if a is not None:
+                cl_in = a.conv_l[0].in_channels
+                cp = (cl_in + 7) // 8 * 8
+                prep.update(cp=cp, wl=_conv3_matrix(a.conv_l[0].weight, cp), fl=_fold(a.conv_l[0], a.conv_l[1]),
+                            wr=_conv3_matrix(a.conv_r[0].weight, a.conv_r[0].in_channels), fr=_fold(a.conv_r[0], a.conv_r[1]),
+                            wp=_f(a.proj.weight).reshape(a.proj.out_channels, -1), bp=_f(a.proj.bias))
+                if packed:
+                    # the same matrices split once into MFMA fragments (csrc/vit_packed.hip; channels of the [x | att] map padded to a multiple of 32)
+                    cpp = (cl_in + 31) // 32 * 32
+                    prep.update(cpp=cpp, wl_p=ops.x3p_pack(_conv3_matrix(a.conv_l[0].weight, cpp)), wr_p=ops.x3p_pack(prep["wr"]), wp_p=ops.x3p_pack(prep["wp"]))
+            for name, conv, bn in self._ups():
+                wm = _convT_matrices(conv.weight)
+                u = dict(w=wm, raw=_fold_up(conv, None), fold=_fold_up(conv, bn) if bn is not None else None)
+                if packed:
+                    u["w_p"] = ops.x3p_pack_classes(wm, 128)
+                prep[name] = u
+            self._extra_prepare(prep)
             _publish_cache()
             self._cache = (key, prep)
         return self._cache[1]
 
-    def _packed_ok(self) -> bool:
-        a, d = self.attn, self.decoder
-        chans = (a.conv_r[0].in_channels, a.proj.out_channels, d[0].out_channels)
-        return all(c % 32 == 0 for c in chans) and d[3].out_channels % 4 == 0 and sw.flag("MVS_VIT_PACKED")
+    def _extra_prepare(self, prep):
+        pass
 
-    def _forward_packed(self, p, xc, ac):
-        """The decoder on pre-split operands: every convolution is an implicit GEMM whose A operand is gathered from a packed channel-last map
-        by LDS-DMA (``mvs_conv_x3p``); intermediate maps are written packed by the producing epilogue."""
+    # ---- AttentionFusionSimple, eval
+    @staticmethod
+    def _attn_packed(p, xc, ac):
+        """-> the fused map as a packed ``[M][out_ch]`` matrix with a zero row behind its pixels."""
         B, h, w, C = xc.shape
         M, nh, dev = B * h * w, ac.shape[-1], xc.device
         ra = (M + 128) // 128 * 128                           # rows allocated: the pixels + at least one zero row (taps outside the image)
@@ -623,13 +646,29 @@ class VITDecoderStage4Single(nn.Module):
         co = p["wp"].shape[0]
         y = ops.Packed(M, co, dev, rows_alloc=ra, zero=True)
         ops.gemm_x3p(x12, p["wp_p"], co, shift=p["bp"], out=y)
-        c1, c2 = p["w1"].shape[1], p["w2"].shape[1]
-        y1 = ops.Packed(4 * M, c1, dev, rows_alloc=(4 * M + 128) // 128 * 128, zero=True)
-        ops.conv_x3p(y, p["w1_p"], 2, B, h, w, c1, scale=p["f1"][0], shift=p["f1"][1], act=1, out=y1)
-        out = torch.empty(B, 4 * h, 4 * w, c2, device=dev, dtype=torch.float32)
-        ops.conv_x3p(y1, p["w2_p"], 2, B, 2 * h, 2 * w, c2, C=out.view(16 * M, c2), scale=p["f2"][0], shift=p["f2"][1], act=1)
-        return out.permute(0, 3, 1, 2)
+        return y
 
+    @staticmethod
+    def _attn_plain(p, xc, ac):
+        """-> the fused map ``[B,h,w,out_ch]`` fp32 channel-last."""
+        B, h, w, C = xc.shape
+        nh = ac.shape[-1]
+        cat = torch.zeros(B, h, w, p["cp"], device=xc.device, dtype=torch.float32)
+        cat[..., :C] = xc
+        cat[..., C:C + nh] = ac
+        x1 = torch.empty(B, h * w, C, device=xc.device, dtype=torch.float32)
+        ops.gemm_x3(cat, p["wl"], x1, h * w, C, 9 * p["cp"], 0, 9 * p["cp"], C, nb1=B, sA=(h * w * p["cp"], 0), sC=(h * w * C, 0), a_mode=1, H=h, W=w,
+                    Cp=p["cp"], scale=p["fl"][0], shift=p["fl"][1], act=2)
+        xr = (xc * ac.mean(dim=-1, keepdim=True)).contiguous()
+        x12 = torch.empty_like(x1)
+        ops.gemm_x3(xr, p["wr"], x12, h * w, C, 9 * C, 0, 9 * C, C, nb1=B, sA=(h * w * C, 0), sC=(h * w * C, 0), a_mode=1, H=h, W=w, Cp=C,
+                    scale=p["fr"][0], shift=p["fr"][1], act=2, mul=x1)
+        co = p["wp"].shape[0]
+        y = torch.empty(B, h, w, co, device=xc.device, dtype=torch.float32)
+        ops.gemm_x3(x12, p["wp"], y, B * h * w, co, C, C, C, co, shift=p["bp"])
+        return y
+
+    # ---- one ConvTranspose2d(4, 2, 1) in eval, either route: x = (map, B, h, w) with map a Packed or an fp32 [B,h,w,C] tensor
     @staticmethod
     def _up(x_cl, wm, fold, act):
         """One ConvTranspose2d(4, 2, 1) + folded BatchNorm + activation on a channel-last map ``[B,h,w,C]`` -> ``[B,2h,2w,Cout]``."""
@@ -640,15 +679,48 @@ class VITDecoderStage4Single(nn.Module):
                     a_mode=2, H=h, W=w, Cp=C, scale=fold[0], shift=fold[1], act=act)
         return tmp.view(B, 2, 2, h, w, cout).permute(0, 3, 1, 4, 2, 5).reshape(B, 2 * h, 2 * w, cout).contiguous()
 
-    def _forward_train(self, x, att):
-        """models/module.py:365-368 + :459-466 with batch statistics, every op an autograd-tracked HIP kernel (fp32 NCHW like the FPN's training
-        path): conv_l / conv_r / proj through ``Conv2dFn`` + ``BiasFn``, BatchNorm + Swish / GELU through ``BnActFn`` (SyncBatchNorm-aware), the
-        gated product through ``MulFn``, the two ``ConvTranspose2d`` through ``ConvT2dFn``."""
+    def _up_layer(self, p, x, name, raw: bool, act: bool):
+        """The layer ``name`` on ``x`` -> up to two maps of the doubled size: its raw output (bias only; fp32 ``[B,2h,2w,C]``: a module output) and
+        ``GELU(BatchNorm(.))`` of it for the next layer (packed on the packed route).  Both come from the accumulators of the same product, each
+        through its own epilogue: the BatchNorm + GELU act on the data BEFORE the next layer packs / gathers it, and the zero row that taps
+        outside the image read stays zero (it would be GELU(shift) had the affine map been moved behind the gather)."""
+        m, B, h, w = x
+        u = p[name]
+        cout = u["w"].shape[1]
+        out_raw = out_act = None
+        if p["packed"]:
+            M4 = 4 * B * h * w
+            if raw:
+                out_raw = torch.empty(B, 2 * h, 2 * w, cout, device=m.buf.device, dtype=torch.float32)
+                ops.conv_x3p(m, u["w_p"], 2, B, h, w, cout, C=out_raw.view(M4, cout), scale=u["raw"][0], shift=u["raw"][1], act=0)
+            if act:
+                out_act = ops.Packed(M4, cout, m.buf.device, rows_alloc=(M4 + 128) // 128 * 128, zero=True)
+                ops.conv_x3p(m, u["w_p"], 2, B, h, w, cout, scale=u["fold"][0], shift=u["fold"][1], act=1, out=out_act)
+        else:
+            if raw:
+                out_raw = self._up(m, u["w"], u["raw"], 0)
+            if act:
+                out_act = self._up(m, u["w"], u["fold"], 1)
+        return out_raw, (out_act, B, 2 * h, 2 * w)
+
+    def _final(self, p, x, name):
+        """The chain's last layer with BatchNorm + GELU as a module output: fp32 ``[B,2h,2w,C]``."""
+        m, B, h, w = x
+        u = p[name]
+        cout = u["w"].shape[1]
+        if not p["packed"]:
+            return self._up(m, u["w"], u["fold"], 1)
+        out = torch.empty(B, 2 * h, 2 * w, cout, device=m.buf.device, dtype=torch.float32)
+        ops.conv_x3p(m, u["w_p"], 2, B, h, w, cout, C=out.view(4 * B * h * w, cout), scale=u["fold"][0], shift=u["fold"][1], act=1)
+        return out
+
+    # ---- training
+    @staticmethod
+    def _attn_train(a, x, att):
+        """models/module.py:459-466 with batch statistics: conv_l / conv_r / proj through ``Conv2dFn`` + ``BiasFn``, BatchNorm + Swish through
+        ``BnActFn`` (SyncBatchNorm-aware), the gated product through ``MulFn``."""
         from .autograd import BnActFn
         from .fpn import ACT_SWISH, BiasFn, Conv2dFn
-        a, d = self.attn, self.decoder
-        x = x.to(torch.float32).contiguous()
-        att = att.to(torch.float32).contiguous()
 
         def conv_bn(t, seq):
             y = BiasFn.apply(Conv2dFn.apply(t, seq[0].weight, 1, 1), seq[0].bias)
@@ -657,10 +729,49 @@ class VITDecoderStage4Single(nn.Module):
         x1 = conv_bn(torch.cat([x, att], dim=1), a.conv_l)
         gate = att.mean(dim=1, keepdim=True)                  # inputs come from the frozen ViT: no gradient flows through these two torch ops
         x2 = conv_bn(x * gate if not (x.requires_grad or att.requires_grad) else MulFn.apply(x, gate.expand_as(x)), a.conv_r)
-        y = BiasFn.apply(Conv2dFn.apply(MulFn.apply(x1, x2), a.proj.weight, 1, 0), a.proj.bias)
+        return BiasFn.apply(Conv2dFn.apply(MulFn.apply(x1, x2), a.proj.weight, 1, 0), a.proj.bias)
+
+    @staticmethod
+    def _convT_train(y, conv):
+        from .fpn import BiasFn
+        return BiasFn.apply(ConvT2dFn.apply(y, conv.weight, conv.stride[0], conv.padding[0]), conv.bias)
+
+    @staticmethod
+    def _bn_gelu_train(y, bn):
+        from .autograd import BnActFn
+        return BnActFn.apply(y, bn.weight, bn.bias, None, bn, ACT_GELU_BN)
+
+    @staticmethod
+    def _channels_last_inputs(x, att):
+        # channel-last views ([B, vit_ch, h, w] made from tokens is a permuted view of [B, h*w, vit_ch]: contiguous() is free then)
+        xc = x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        ac = att.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous() if att is not None else None
+        return xc, ac
+
+
+class VITDecoderStage4Single(_DecoderBase):
+    """models/module.py:353-368: ``forward(x [B,vit_ch,h,w], att [B,nhead,h,w]) -> [B,out_ch,4h,4w]`` (added to ``conv31``)."""
+
+    def __init__(self, args):
+        super().__init__()
+        ch, vit_ch = args["out_ch"], args["vit_ch"]
+        assert args["att_fusion"] is True
+        self.attn = AttentionFusionSimple(vit_ch, ch * 4, args["nhead"])
+        self.decoder = nn.Sequential(nn.ConvTranspose2d(ch * 4, ch * 2, 4, stride=2, padding=1), nn.BatchNorm2d(ch * 2), nn.GELU(),
+                                     nn.ConvTranspose2d(ch * 2, ch, 4, stride=2, padding=1), nn.BatchNorm2d(ch), nn.GELU())
+        self._cache = None
+
+    def _ups(self):
+        d = self.decoder
+        return [("u1", d[0], d[1]), ("u2", d[3], d[4])]
+
+    def _forward_train(self, x, att):
+        """models/module.py:365-368 + :459-466 with batch statistics, every op an autograd-tracked HIP kernel (fp32 NCHW like the FPN's training
+        path): the fusion through ``_attn_train``, the two ``ConvTranspose2d`` through ``ConvT2dFn``, BatchNorm + GELU through ``BnActFn``."""
+        d = self.decoder
+        y = self._attn_train(self.attn, x.to(torch.float32).contiguous(), att.to(torch.float32).contiguous())
         for conv, bn in ((d[0], d[1]), (d[3], d[4])):
-            y = BiasFn.apply(ConvT2dFn.apply(y, conv.weight, conv.stride[0], conv.padding[0]), conv.bias)
-            y = BnActFn.apply(y, bn.weight, bn.bias, None, bn, ACT_GELU_BN)
+            y = self._bn_gelu_train(self._convT_train(y, conv), bn)
         return y
 
     def forward(self, x, att):
@@ -668,33 +779,139 @@ class VITDecoderStage4Single(nn.Module):
             return self._forward_train(x, att)
         p = self._prepared()
         with torch.no_grad():
+            B, _, h, w = x.shape
+            xc, ac = self._channels_last_inputs(x, att)
+            y = (self._attn_packed if p["packed"] else self._attn_plain)(p, xc, ac)
+            _, t = self._up_layer(p, (y, B, h, w), "u1", raw=False, act=True)
+            return self._final(p, t, "u2").permute(0, 3, 1, 2)      # logical NCHW (channel-last memory); `conv31 + vit_out` broadcasts layouts
+
+
+class VITDecoderStage4(_DecoderBase):
+    """models/module.py:305-350 (``multi_scale=True``): ``forward(x [B,vit_ch,h,w], att [B,nhead,h,w]) -> (out1 [B,ch,4h,4w], out2 [B,ch/2,8h,8w],
+    out3 [B,ch/4,16h,16w])``, the three transformer maps ``FPNDecoderV2`` concatenates.  Default: the chained form (``decoder2`` / ``decoder3`` start
+    with the BatchNorm + GELU of the previous, un-normalised output); ``multi_scale_decoder=True``: three independent heads on the fused map."""
+
+    def __init__(self, args):
+        super().__init__()
+        ch, vit_ch = args["out_ch"], args["vit_ch"]
+        self.multi_scale_decoder = args.get("multi_scale_decoder", False)
+        assert args["att_fusion"] is True
+        self.attn = AttentionFusionSimple(vit_ch, ch * 4, args["nhead"])
+        T, BN, G = (lambda i, o: nn.ConvTranspose2d(i, o, 4, stride=2, padding=1)), nn.BatchNorm2d, nn.GELU
+        self.decoder1 = nn.Sequential(T(ch * 4, ch * 2), BN(ch * 2), G(), T(ch * 2, ch))
+        if self.multi_scale_decoder:
+            self.decoder2 = nn.Sequential(T(ch * 4, ch * 2), BN(ch * 2), G(), T(ch * 2, ch), BN(ch), G(), T(ch, ch // 2))
+            self.decoder3 = nn.Sequential(T(ch * 4, ch * 2), BN(ch * 2), G(), T(ch * 2, ch), BN(ch), G(), T(ch, ch // 2), BN(ch // 2), G(),
+                                          T(ch // 2, ch // 4))
+        else:
+            self.decoder2 = nn.Sequential(BN(ch), G(), T(ch, ch // 2))
+            self.decoder3 = nn.Sequential(BN(ch // 2), G(), T(ch // 2, ch // 4))
+        self._cache = None
+
+    def _chains(self):
+        """Per head ``[(name, conv, bn behind it or None)]``; in the chained form one chain runs through the three decoders."""
+        d1, d2, d3 = self.decoder1, self.decoder2, self.decoder3
+        if self.multi_scale_decoder:
+            heads = []
+            for k, d in ((1, d1), (2, d2), (3, d3)):
+                convs = [i for i, m in enumerate(d) if isinstance(m, nn.ConvTranspose2d)]
+                heads.append([("d%d_%d" % (k, i), d[i], d[i + 1] if i + 1 < len(d) else None) for i in convs])
+            return heads
+        return [[("d1_0", d1[0], d1[1]), ("d1_3", d1[3], d2[0]), ("d2_2", d2[2], d3[0]), ("d3_2", d3[2], None)]]
+
+    def _ups(self):
+        return [layer for chain in self._chains() for layer in chain]
+
+    def _forward_train(self, x, att):
+        """models/module.py:339-350 with batch statistics; every op an autograd-tracked HIP kernel, fp32 NCHW."""
+        y = self._attn_train(self.attn, x.to(torch.float32).contiguous(), att.to(torch.float32).contiguous())
+        outs = []
+        for chain in self._chains():
+            t = y
+            for i, (_, conv, bn) in enumerate(chain):
+                t = self._convT_train(t, conv)
+                if not self.multi_scale_decoder and i >= 1:
+                    outs.append(t)                            # out1, out2, out3 leave un-normalised
+                if bn is not None:
+                    t = self._bn_gelu_train(t, bn)
+            if self.multi_scale_decoder:
+                outs.append(t)
+        return tuple(outs)
+
+    def forward(self, x, att):
+        if self.training:
+            return self._forward_train(x, att)
+        p = self._prepared()
+        with torch.no_grad():
+            B, _, h, w = x.shape
+            xc, ac = self._channels_last_inputs(x, att)
+            y = (self._attn_packed if p["packed"] else self._attn_plain)(p, xc, ac)
+            outs = []
+            for chain in self._chains():
+                t = (y, B, h, w)
+                for i, (name, _, bn) in enumerate(chain):
+                    is_out = (i >= 1) if not self.multi_scale_decoder else (i == len(chain) - 1)
+                    raw, t = self._up_layer(p, t, name, raw=is_out, act=bn is not None)
+                    if is_out:
+                        outs.append(raw)
+            return tuple(o.permute(0, 3, 1, 2) for o in outs)
+
+
+class VITDecoderStage4NoAtt(_DecoderBase):
+    """models/module.py:371-386 (``att_fusion=False``): a 3x3 convolution ``vit_ch -> 4 ch`` + BatchNorm + GELU (implicit GEMM, ``a_mode=1``) in
+    place of the attention fusion, then ``VITDecoderStage4Single``'s two-step decoder.  ``forward(x, att=None) -> [B,out_ch,4h,4w]``."""
+
+    def __init__(self, args):
+        super().__init__()
+        ch, vit_ch = args["out_ch"], args["vit_ch"]
+        self.down_sample = nn.Sequential(nn.Conv2d(vit_ch, ch * 4, kernel_size=3, padding=1), nn.BatchNorm2d(ch * 4), nn.GELU())
+        self.decoder = nn.Sequential(nn.ConvTranspose2d(ch * 4, ch * 2, 4, stride=2, padding=1), nn.BatchNorm2d(ch * 2), nn.GELU(),
+                                     nn.ConvTranspose2d(ch * 2, ch, 4, stride=2, padding=1), nn.BatchNorm2d(ch), nn.GELU())
+        self._cache = None
+
+    def _ups(self):
+        d = self.decoder
+        return [("u1", d[0], d[1]), ("u2", d[3], d[4])]
+
+    def _packed_ok(self) -> bool:
+        return self.down_sample[0].in_channels % 8 == 0 and super()._packed_ok()
+
+    def _extra_prepare(self, prep):
+        ds = self.down_sample
+        prep.update(wd=_conv3_matrix(ds[0].weight, ds[0].in_channels), fd=_fold(ds[0], ds[1]))
+
+    def _forward_train(self, x):
+        from .fpn import BiasFn, Conv2dFn
+        ds, d = self.down_sample, self.decoder
+        y = BiasFn.apply(Conv2dFn.apply(x.to(torch.float32).contiguous(), ds[0].weight, 1, 1), ds[0].bias)
+        y = self._bn_gelu_train(y, ds[1])
+        for conv, bn in ((d[0], d[1]), (d[3], d[4])):
+            y = self._bn_gelu_train(self._convT_train(y, conv), bn)
+        return y
+
+    def forward(self, x, att=None):
+        if self.training:
+            return self._forward_train(x)
+        p = self._prepared()
+        with torch.no_grad():
             B, C, h, w = x.shape
-            # channel-last views ([B, vit_ch, h, w] made from tokens is a permuted view of [B, h*w, vit_ch]: contiguous() is free then)
-            xc = x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
-            ac = att.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
-            nh = ac.shape[-1]
-            if "wl_p" in p:
-                return self._forward_packed(p, xc, ac)
-            cat = torch.zeros(B, h, w, p["cp"], device=x.device, dtype=torch.float32)
-            cat[..., :C] = xc
-            cat[..., C:C + nh] = ac
-            x1 = torch.empty(B, h * w, C, device=x.device, dtype=torch.float32)
-            ops.gemm_x3(cat, p["wl"], x1, h * w, C, 9 * p["cp"], 0, 9 * p["cp"], C, nb1=B, sA=(h * w * p["cp"], 0), sC=(h * w * C, 0), a_mode=1, H=h, W=w,
-                        Cp=p["cp"], scale=p["fl"][0], shift=p["fl"][1], act=2)
-            xr = (xc * ac.mean(dim=-1, keepdim=True)).contiguous()
-            x12 = torch.empty_like(x1)
-            ops.gemm_x3(xr, p["wr"], x12, h * w, C, 9 * C, 0, 9 * C, C, nb1=B, sA=(h * w * C, 0), sC=(h * w * C, 0), a_mode=1, H=h, W=w, Cp=C,
-                        scale=p["fr"][0], shift=p["fr"][1], act=2, mul=x1)
-            co = p["wp"].shape[0]
+            if C % 8:
+                raise _lib.MvsHipError("VITDecoderStage4NoAtt: vit_ch must be a multiple of 8 (got %d)" % C)
+            xc, _ = self._channels_last_inputs(x, None)
+            co = p["wd"].shape[0]
             y = torch.empty(B, h, w, co, device=x.device, dtype=torch.float32)
-            ops.gemm_x3(x12, p["wp"], y, B * h * w, co, C, C, C, co, shift=p["bp"])
-            y = self._up(y, p["w1"], p["f1"], 1)
-            y = self._up(y, p["w2"], p["f2"], 1)
-            return y.permute(0, 3, 1, 2)                      # logical NCHW (channel-last memory); `conv31 + vit_out` broadcasts layouts
+            ops.gemm_x3(xc, p["wd"], y, h * w, co, 9 * C, 0, 9 * C, co, nb1=B, sA=(h * w * C, 0), sC=(h * w * co, 0), a_mode=1, H=h, W=w, Cp=C,
+                        scale=p["fd"][0], shift=p["fd"][1], act=1)
+            if p["packed"]:
+                M = B * h * w
+                y = ops.x3p_pack(y.view(M, co), (M + 128) // 128 * 128)
+            _, t = self._up_layer(p, (y, B, h, w), "u1", raw=False, act=True)
+            return self._final(p, t, "u2").permute(0, 3, 1, 2)
 
 
-def vit_branch(vit: VisionTransformer, dec: VITDecoderStage4Single, img: torch.Tensor, rescale: float = 0.5):
-    """One view of mvsformer_model.py:243-262 up to ``vit_out``: bicubic resize, ViT with the last block's attention, reshapes, decoder."""
+def vit_branch(vit: VisionTransformer, dec: Optional[_DecoderBase], img: torch.Tensor, rescale: float = 0.5):
+    """One view of mvsformer_model.py:243-262 up to ``vit_out``: bicubic resize, ViT with the last block's attention, reshapes, decoder - any of
+    ``VITDecoderStage4Single`` / ``VITDecoderStage4NoAtt`` (one map) or ``VITDecoderStage4`` (``vit_out`` is then the tuple of its three maps)."""
     B, _, H, W = img.shape
     vh, vw = int(H * rescale), int(W * rescale)
     x = ops.bicubic_resize(img.detach().to(torch.float32).contiguous(), vh, vw, H / vh, W / vw)

@@ -47,7 +47,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scan", required=True)
     ap.add_argument("--checkpoint", required=True)
-    ap.add_argument("--config", default=None, help="the reference's config json (arch.args); default: MVSFormer-P")
+    ap.add_argument("--config", default=None, help="the reference's config json (arch.args); default: MVSFormer-P, with multi_scale / att_fusion from the checkpoint's own config")
     ap.add_argument("--num_view", type=int, default=5)
     ap.add_argument("--numdepth", type=int, default=192)
     ap.add_argument("--interval_scale", type=float, default=1.06)
@@ -66,9 +66,20 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("infer_scan.py runs the MI355X path: no GPU")
     dev = torch.device("cuda:0")
-    args = json.load(open(a.config))["arch"]["args"] if a.config else DEFAULT_ARGS
-    net = m.DINOMVSNet(args)
+    args = json.load(open(a.config))["arch"]["args"] if a.config else dict(DEFAULT_ARGS, vit_args=dict(DEFAULT_ARGS["vit_args"]))
     sd = torch.load(a.checkpoint, map_location="cpu")
+    if not a.config:
+        # the reference's trainer stores its config in the checkpoint: the two flags that change the model's modules come from there
+        try:
+            ck = sd["config"]["arch"]["args"]
+        except (KeyError, TypeError, IndexError):
+            ck = None
+        if ck is not None:
+            args["multi_scale"] = bool(ck.get("multi_scale", False))
+            for k in ("att_fusion", "multi_scale_decoder"):
+                if k in ck.get("vit_args", {}):
+                    args["vit_args"][k] = ck["vit_args"][k]
+    net = m.DINOMVSNet(args)
     sd = sd.get("state_dict", sd)
     net.load_state_dict({k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}, strict=True)
     net = net.to(dev).eval()
