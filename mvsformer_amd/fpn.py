@@ -23,6 +23,8 @@ bilinear x2 upsampling + lateral add and its adjoint in ``csrc/fpn_train.hip``. 
 from __future__ import annotations
 
 
+from typing import NamedTuple, Optional
+
 import torch
 import torch.nn as nn
 
@@ -101,6 +103,42 @@ class Swish(nn.Module):
         raise _lib.MvsHipError("Swish is a structural placeholder of FPNDecoder: call the decoder")
 
 
+class FpnSwitches(NamedTuple):
+    """The environment switches the FPN's eval routes depend on, read once per forward (:func:`fpn_switches`) and part of the cache keys."""
+    x3: str = "1"                 # MVS_FPN_X3: "0" | "strip" | anything else
+    v2_tail: bool = True          # MVS_FPN_V2_TAIL
+
+
+def fpn_switches() -> FpnSwitches:
+    return FpnSwitches(sw.text("MVS_FPN_X3"), sw.flag("MVS_FPN_V2_TAIL"))
+
+
+def encoder_route(cin: int, cout: int, k: int, stride: int, x3_ok: bool, x3s_ok: bool, fs: FpnSwitches) -> str:
+    """Kernel of an ``FPNEncoder`` layer in eval: ``"x3"`` (csrc/conv2d_x3.hip: conv00 / conv01, channel-last between them), ``"x3s"``
+    (csrc/conv2d_x3s.hip: the layers below full resolution) or ``"fp32"`` (csrc/conv2d.hip).  ``x3_ok`` / ``x3s_ok``: what
+    ``ops.conv2d_x3_supported`` / ``ops.conv2d_x3s_supported`` answer for ``(cin, cout, k, stride)``."""
+    if fs.x3 != "0" and x3_ok:
+        return "x3"
+    if fs.x3 != "0" and x3s_ok:
+        return "x3s"
+    return "fp32"
+
+
+def decoder_route(level: int, fs: FpnSwitches):
+    """Kernel of ``FPNDecoder`` level ``level`` (1, 2; 3 = full resolution) in eval and whether the level hands its intra map over channel-last:
+    ``"fpn_cp"`` (csrc/fpn_cp.hip, default) | ``"fpn_x3"`` (csrc/fpn_x3.hip, the strip kernel) for level 3, ``"fpn_lvl_x3"`` (csrc/fpn_lvl_x3.hip)
+    for levels 1-2, ``"fpn"`` (csrc/fpn.hip) for any level with ``MVS_FPN_X3=0``.  Channel-last: level 2 only, when level 3 takes ``fpn_cp``."""
+    if level == 3 and fs.x3 != "0":
+        return ("fpn_x3" if fs.x3 == "strip" else "fpn_cp"), False
+    nhwc = level == 2 and decoder_route(3, fs)[0] == "fpn_cp"
+    return ("fpn_lvl_x3" if fs.x3 != "0" else "fpn"), nhwc
+
+
+def v2_tail_route(tail_chs: bool, fs: FpnSwitches) -> str:
+    """``FPNDecoderV2``'s full-resolution tail: ``"fused"`` (csrc/fpn_v2_tail.hip: built for ``feat_chs[:2] == [8, 16]``) or ``"gemm"``."""
+    return "fused" if tail_chs and fs.v2_tail else "gemm"
+
+
 def _channels_last(t: torch.Tensor) -> torch.Tensor:
     """``[N,C,H,W]`` (logical) -> a contiguous ``[N,H,W,C]`` tensor: free when the producer already wrote channel-last memory (the level kernels'
     ``intra`` with ``intra_nhwc``, the encoder's ``conv01`` companion, any ``permute`` view of an NHWC buffer), one copy otherwise."""
@@ -134,17 +172,19 @@ class FPNDecoder(nn.Module):
         shift = bn.bias.detach().double() + (conv.bias.detach().double() - bn.running_mean.double()) * scale
         return scale.float().contiguous(), shift.float().contiguous()
 
-    def _prepared(self):
-        key = _versions(self)
+    def _prepared(self, fs: Optional[FpnSwitches] = None):
+        fs = fs or fpn_switches()
+        key = (_versions(self), fs.x3)
         if self._cache is None or self._cache[0] != key:
             levels = []
             for k in (1, 2, 3):
                 inner, seq = getattr(self, "inner%d" % k), getattr(self, "out%d" % k)
                 scale, shift = self._fold(seq)
+                route = decoder_route(k, fs)[0]
                 x3 = None
-                if k == 3 and sw.text("MVS_FPN_X3") != "0":      # the full-resolution level in split form (csrc/fpn_cp.hip, fpn_x3.hip)
+                if route in ("fpn_cp", "fpn_x3"):                # the full-resolution level in split form (both forms are prepared together)
                     x3 = ops.fpn_level_x3_prepare(seq[0].weight.detach().contiguous(), inner.weight.detach(), inner.bias.detach(), scale, shift)
-                elif sw.text("MVS_FPN_X3") != "0":               # levels 1-2: the 3x3 convolution in split form (csrc/fpn_lvl_x3.hip)
+                elif route == "fpn_lvl_x3":                      # levels 1-2: the 3x3 convolution in split form
                     x3 = ops.fpn_level_x3s_prepare(seq[0].weight.detach().contiguous(), scale)
                 levels.append((inner.weight.detach().reshape(ops.FPN_CH // 2, 2, -1).permute(0, 2, 1).contiguous(), inner.bias.detach().contiguous(),
                                ops.fpn_pack_weights(seq[0].weight.detach().contiguous()), scale, shift, x3))
@@ -167,21 +207,19 @@ class FPNDecoder(nn.Module):
         if self.training:
             return self._forward_train(conv01, conv11, conv21, conv31)
         with torch.no_grad():
-            (w0, s0, h0), levels = self._prepared()
+            fs = fpn_switches()
+            (w0, s0, h0), levels = self._prepared(fs)
             intra = conv31.float().contiguous()
             outs = [ops.fpn_out0(intra, w0, s0, h0)]
             for i, lateral in enumerate((conv21, conv11, conv01)):
                 w_in, b_in, packed, scale, shift, x3 = levels[i]
-                if i == 2 and x3 is not None:                # MVS_FPN_X3: 1 (default) = csrc/fpn_cp.hip, strip = csrc/fpn_x3.hip, 0 = csrc/fpn.hip
-                    prepared, shift_x, border, prepared_cp = x3
-                    if sw.text("MVS_FPN_X3") == "strip":
-                        out = ops.fpn_level_x3(intra, lateral.float().contiguous(), prepared, shift_x, border)
-                    else:
-                        out = ops.fpn_level_cp(_channels_last(intra), _channels_last(lateral), prepared_cp, shift_x, border)
+                route, nhwc = decoder_route(i + 1, fs)
+                if route == "fpn_x3":
+                    out = ops.fpn_level_x3(intra, lateral.float().contiguous(), x3[0], x3[1], x3[2])
+                elif route == "fpn_cp":
+                    out = ops.fpn_level_cp(_channels_last(intra), _channels_last(lateral), x3[3], x3[1], x3[2])
                 else:
-                    # the level below the full-resolution one hands its intra map over channel-last when csrc/fpn_cp.hip will read it
-                    nhwc = i == 1 and levels[2][5] is not None and sw.text("MVS_FPN_X3") != "strip"
-                    if x3 is not None:
+                    if route == "fpn_lvl_x3":
                         intra, out = ops.fpn_level_x3s(intra, lateral.float().contiguous(), w_in, b_in, x3, shift, want_intra=True, intra_nhwc=nhwc)
                     else:
                         intra, out = ops.fpn_level(intra, lateral.float().contiguous(), w_in, b_in, packed, scale, shift, want_intra=(i < 2), intra_nhwc=nhwc)
@@ -218,9 +256,10 @@ class FPNDecoderV2(nn.Module):
         self._tail_chs = c[:2] == [8, 16]                     # what csrc/fpn_v2_tail.hip is built for (every shipped config)
         self._cache = None
 
-    def _prepared(self):
+    def _prepared(self, fs: Optional[FpnSwitches] = None):
         from .vit import _conv3_matrix, _convT_matrices, _f, _fold
-        key = _versions(self)
+        fs = fs or fpn_switches()
+        key = (_versions(self), fs.v2_tail)
         if self._cache is None or self._cache[0] != key:
             prep = {}
             for k in (1, 2, 3, 4):
@@ -229,7 +268,7 @@ class FPNDecoderV2(nn.Module):
             for k in (1, 2, 3):
                 seq = getattr(self, "upsample%d" % k)
                 prep["up%d" % k] = (_convT_matrices(seq[0].weight), _fold(seq[0], seq[1]))
-            if self._tail_chs and sw.flag("MVS_FPN_V2_TAIL"):       # the full-resolution tail as one kernel (csrc/fpn_v2_tail.hip)
+            if v2_tail_route(self._tail_chs, fs) == "fused":      # the full-resolution tail as one kernel (csrc/fpn_v2_tail.hip)
                 prep["tail"] = ops.fpn_v2_tail_prepare(_f(self.upsample3[0].weight), prep["up3"][1], _f(self.out4[0].weight), prep["out4"][1])
             _publish_cache()
             self._cache = (key, prep)
@@ -270,7 +309,8 @@ class FPNDecoderV2(nn.Module):
         if self.training:
             return self._forward_train(conv01, conv11, conv21, conv31, vit1, vit2, vit3)
         from .vit import VITDecoderStage4Single
-        p = self._prepared()
+        fs = fpn_switches()
+        p, tail = self._prepared(fs), v2_tail_route(self._tail_chs, fs)
 
         def cl(t):                                            # logical NCHW -> channel-last memory (free when it already is)
             return t.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
@@ -281,7 +321,7 @@ class FPNDecoderV2(nn.Module):
             for k, (skip, vit) in enumerate(((conv21, vit2), (conv11, vit3), (conv01, None)), start=1):
                 out = self._conv3(x, *p["out%d" % k])
                 outs.append(out)
-                if vit is None and "tail" in p:               # MVS_FPN_V2_TAIL (default): upsample3 + conv01 + out4 fused, the up map never written
+                if vit is None and tail == "fused":           # MVS_FPN_V2_TAIL (default): upsample3 + conv01 + out4 fused, the up map never written
                     outs.append(ops.fpn_v2_tail(out, cl(skip), *p["tail"]))
                     break
                 up = VITDecoderStage4Single._up(out, p["up%d" % k][0], p["up%d" % k][1], ACT_RELU_GEMM)      # [B,2h,2w,C/2]
@@ -339,8 +379,9 @@ class FPNEncoder(nn.Module):
         self.conv31 = Conv2d(c[3], c[3], 3, 1, padding=1, norm_type=norm_type)
         self._cache = None
 
-    def _prepared(self):
-        key = _versions(self)
+    def _prepared(self, fs: Optional[FpnSwitches] = None):
+        fs = fs or fpn_switches()
+        key = (_versions(self), fs.x3)
         if self._cache is None or self._cache[0] != key:
             layers = []
             for name, k, stride in self.LAYERS:
@@ -348,12 +389,14 @@ class FPNEncoder(nn.Module):
                 scale = m.bn.weight.detach().double() / torch.sqrt(m.bn.running_var.double() + m.bn.eps)
                 shift = m.bn.bias.detach().double() - m.bn.running_mean.double() * scale
                 wt = m.conv.weight.detach().contiguous()
-                x3 = None                                    # conv00 / conv01: the split form (csrc/conv2d_x3.hip)
-                if sw.text("MVS_FPN_X3") != "0" and ops.conv2d_x3_supported(wt.shape[1], wt.shape[0], k, stride):
+                cout, cin = wt.shape[:2]
+                route = encoder_route(cin, cout, k, stride, ops.conv2d_x3_supported(cin, cout, k, stride), ops.conv2d_x3s_supported(cin, cout, k, stride), fs)
+                x3 = None
+                if route == "x3":
                     x3 = ops.conv2d_x3_prepare(wt, scale.float().contiguous())
-                elif sw.text("MVS_FPN_X3") != "0" and ops.conv2d_x3s_supported(wt.shape[1], wt.shape[0], k, stride):
-                    x3 = ops.conv2d_x3s_prepare(wt, scale.float().contiguous(), stride)      # the layers below full resolution (csrc/conv2d_x3s.hip)
-                layers.append((ops.conv2d_pack_weights(wt), scale.float().contiguous(), shift.float().contiguous(), m.conv.out_channels, k, stride, x3))
+                elif route == "x3s":
+                    x3 = ops.conv2d_x3s_prepare(wt, scale.float().contiguous(), stride)
+                layers.append((route, ops.conv2d_pack_weights(wt), scale.float().contiguous(), shift.float().contiguous(), m.conv.out_channels, k, stride, x3))
             _publish_cache()
             self._cache = (key, layers)
         return self._cache[1]
@@ -372,19 +415,19 @@ class FPNEncoder(nn.Module):
         with torch.no_grad():
             x = x.float().contiguous()
             outs = {}
-            for (name, _, _), (packed, scale, shift, cout, k, stride, x3) in zip(self.LAYERS, self._prepared()):
-                if x3 is not None and name == "conv00":     # conv00 -> conv01 channel-last: 16-byte stores / loads instead of scattered dwords
+            for (name, _, _), (route, packed, scale, shift, cout, k, stride, x3) in zip(self.LAYERS, self._prepared(fpn_switches())):
+                if route == "x3" and name == "conv00":      # conv00 -> conv01 channel-last: 16-byte stores / loads instead of scattered dwords
                     x00 = ops.conv2d_x3_bn_lrelu(x, x3, shift, cout, k, 0.1, out="nhwc")
                     outs[name] = x00.permute(0, 3, 1, 2)
                     continue
-                if x3 is not None and name == "conv01":     # + the channel-last companion the decoder's last level stages with 16-byte loads
+                if route == "x3":                           # conv01 + the channel-last companion the decoder's last level stages with 16-byte loads
                     if conv01_channels_last:
                         cl = ops.conv2d_x3_bn_lrelu(x00, x3, shift, cout, k, 0.1, x_nhwc=True, out="nhwc")
                         x = cl.permute(0, 3, 1, 2)
                     else:
                         x, cl = ops.conv2d_x3_bn_lrelu(x00, x3, shift, cout, k, 0.1, x_nhwc=True, out="both")
                     x._mvs_nhwc = (cl, x._version)
-                elif x3 is not None:                        # (downsample1 reads conv01's channel-last companion)
+                elif route == "x3s":                        # (downsample1 reads conv01's channel-last companion)
                     cl = getattr(x, "_mvs_nhwc", None) if name == "downsample1" else None
                     if cl is not None and cl[1] == x._version:
                         x = ops.conv2d_x3s_bn_lrelu(cl[0], x3, shift, cout, k, stride, 0.1, x_nhwc=True)

@@ -231,13 +231,37 @@ def to_channels_last_multi(feats: List[torch.Tensor]) -> List[torch.Tensor]:
     return outs
 
 
-def cv_entropy(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None) -> torch.Tensor:
-    """``feat`` is channel-last ``[B,V,H,W,C]`` (see :func:`to_channels_last`)."""
+def _cv_dense_dims(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor):
+    """The checks of a sweep A over dense channel-last ``feat [B,V,H,W,C]`` -> ``(B, V, C, D, H, W)``."""
     _chk(feat, "features"), _chk(rt, "rt"), _chk(depth, "depth_values")
     B, V, H, W, C = feat.shape
     D = depth.shape[1]
     if depth.shape != (B, D, H, W):
         raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, D, H, W), tuple(depth.shape)))
+    return B, V, C, D, H, W
+
+
+def _cv_volume(B: int, G: int, D: int, H: int, W: int, device, want_sim_depth: bool):
+    """The outputs of a sweep B: ``volume [B,G,D,H,W]`` and ``sim_depth [B,H,W]`` (or None)."""
+    return (torch.empty(B, G, D, H, W, device=device, dtype=torch.float32),
+            torch.empty(B, H, W, device=device, dtype=torch.float32) if want_sim_depth else None)
+
+
+def cv_store_bytes_of(B: int, V: int, C: int, G: int, D: int, H: int, W: int) -> int:
+    """Bytes of the per-view correlation store of the stored-correlation sweeps over ``H`` rows (<= 0: not built for this shape - C must be 32 or 64)."""
+    return int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, H, W))
+
+
+def _cv_corr_out(B: int, V: int, rows: int, W: int, nbytes: int, store: Optional[torch.Tensor], device):
+    """The outputs of a sweep A' over ``rows`` reference rows: entropy ``[B,V-1,rows,W]`` and the store (``store`` itself where it holds ``nbytes``)."""
+    if store is None or store.numel() * 4 < nbytes:
+        store = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+    return torch.empty(B, V - 1, rows, W, device=device, dtype=torch.float32), store
+
+
+def cv_entropy(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None) -> torch.Tensor:
+    """``feat`` is channel-last ``[B,V,H,W,C]`` (see :func:`to_channels_last`)."""
+    B, V, C, D, H, W = _cv_dense_dims(feat, rt, depth)
     ent = torch.empty(B, V - 1, H, W, device=feat.device, dtype=torch.float32)
     # algorithmic bytes of a sweep over ALL source views: features once + hypotheses once (SURVEY.md §8d); the entropy
     # maps themselves are <1 %
@@ -317,8 +341,7 @@ def cv_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, weig
     _chk(feat, "features"), _chk(rt, "rt"), _chk(depth, "depth_values"), _chk(weight, "vis_weight")
     B, V, H, W, C = feat.shape
     D = depth.shape[1]
-    vol = torch.empty(B, G, D, H, W, device=feat.device, dtype=torch.float32)
-    sim = torch.empty(B, H, W, device=feat.device, dtype=torch.float32) if want_sim_depth else None
+    vol, sim = _cv_volume(B, G, D, H, W, feat.device, want_sim_depth)
     tag = ("cv_aggregate_kernel<%d,%s>" % (C // 4, "true" if want_sim_depth else "false"), "bytes",
            4.0 * B * H * W * (V * C + D + G * D))          # 4*H*W*(V*C + D + G*D)
     if want_bf16:
@@ -332,24 +355,18 @@ def cv_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, weig
 
 
 def cv_store_bytes(feat: torch.Tensor, D: int, G: int) -> int:
-    """Bytes of the per-view correlation store of the stored-correlation sweeps for channel-last ``feat [B,V,H,W,C]`` (-1: not built
-    for this shape - C must be 32 or 64)."""
+    """:func:`cv_store_bytes_of` channel-last ``feat [B,V,H,W,C]``."""
     B, V, H, W, C = feat.shape
-    return int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, H, W))
+    return cv_store_bytes_of(B, V, C, G, D, H, W)
 
 
 def cv_corr(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None):
     """Sweep A', coarse stages: entropy ``[B,V-1,H,W]`` as :func:`cv_entropy` plus the per-view correlation store for :func:`cv_merge`."""
-    _chk(feat, "features"), _chk(rt, "rt"), _chk(depth, "depth_values")
-    B, V, H, W, C = feat.shape
-    D = depth.shape[1]
-    if depth.shape != (B, D, H, W):
-        raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, D, H, W), tuple(depth.shape)))
-    nbytes = cv_store_bytes(feat, D, G)
+    B, V, C, D, H, W = _cv_dense_dims(feat, rt, depth)
+    nbytes = cv_store_bytes_of(B, V, C, G, D, H, W)
     if nbytes <= 0:
         raise _lib.MvsHipError("stored-correlation sweeps are built for C = 32 | 64, G = 8 (got C=%d, G=%d)" % (C, G))
-    ent = torch.empty(B, V - 1, H, W, device=feat.device, dtype=torch.float32)
-    store = torch.empty(nbytes // 4, device=feat.device, dtype=torch.float32)
+    ent, store = _cv_corr_out(B, V, H, W, nbytes, None, feat.device)
     tag = ("cv_corr_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
     _call("mvs_cv_corr_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _ptr(store), _cv_flags(exact), _stream())
     return ent, store
@@ -359,10 +376,9 @@ def cv_merge(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, V: 
     """Sweep B' over the store of :func:`cv_corr`: ``volume [B,G,D,H,W]`` and the similarity arg-max depth."""
     _chk(store, "correlation store"), _chk(depth, "depth_values"), _chk(weight, "vis_weight")
     B, D, H, W = depth.shape
-    if weight.shape != (B, V - 1, H, W) or store.numel() * 4 != int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, H, W)):
+    if weight.shape != (B, V - 1, H, W) or store.numel() * 4 != cv_store_bytes_of(B, V, C, G, D, H, W):
         raise _lib.MvsHipError("cv_merge: weight %s / store size do not match the shape" % (tuple(weight.shape),))
-    vol = torch.empty(B, G, D, H, W, device=depth.device, dtype=torch.float32)
-    sim = torch.empty(B, H, W, device=depth.device, dtype=torch.float32) if want_sim_depth else None
+    vol, sim = _cv_volume(B, G, D, H, W, depth.device, want_sim_depth)
     tag = ("cv_merge_kernel<%d>" % (256 // C), "bytes", 4.0 * B * H * W * (G * D))     # the rest of SURVEY 8d's bytes is credited to sweep A'
     _call("mvs_cv_merge_fwd", tag, _ptr(store), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W, _ptr(vol), _ptr(sim), _stream())
     return vol, sim
@@ -371,17 +387,11 @@ def cv_merge(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, V: 
 def cv_corr_rows(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, y0: int, rows: int, store: Optional[torch.Tensor] = None,
                  exact: Optional[bool] = None):
     """Sweep A' on the band of reference rows ``[y0, y0 + rows)``: band-local entropy ``[B,V-1,rows,W]`` + store (``store``: a buffer to reuse)."""
-    _chk(feat, "features"), _chk(rt, "rt"), _chk(depth, "depth_values")
-    B, V, H, W, C = feat.shape
-    D = depth.shape[1]
-    if depth.shape != (B, D, H, W):
-        raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, D, H, W), tuple(depth.shape)))
-    nbytes = int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, rows, W))
+    B, V, C, D, H, W = _cv_dense_dims(feat, rt, depth)
+    nbytes = cv_store_bytes_of(B, V, C, G, D, rows, W)
     if nbytes <= 0:
         raise _lib.MvsHipError("stored-correlation sweeps are not built for C=%d, G=%d, D=%d" % (C, G, D))
-    if store is None or store.numel() * 4 < nbytes:
-        store = torch.empty(nbytes // 4, device=feat.device, dtype=torch.float32)
-    ent = torch.empty(B, V - 1, rows, W, device=feat.device, dtype=torch.float32)
+    ent, store = _cv_corr_out(B, V, rows, W, nbytes, store, feat.device)
     tag = ("cv_corr_kernel<%d>" % (C // 4), "bytes", 4.0 * B * rows * W * (V * C + D))
     _call("mvs_cv_corr_rows_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, int(y0), int(rows), _ptr(ent), _ptr(store),
           _cv_flags(exact), _stream())
@@ -395,7 +405,7 @@ def cv_merge_rows(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor
     _chk(store, "correlation store"), _chk(depth, "depth_values"), _chk(weight, "vis_weight"), _chk(volume, "volume"), _opt(sim_depth, "sim_depth")
     B, D, H, W = depth.shape
     rows = weight.shape[2]
-    if weight.shape != (B, V - 1, rows, W) or volume.shape != (B, G, D, H, W) or store.numel() * 4 < int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, rows, W)):
+    if weight.shape != (B, V - 1, rows, W) or volume.shape != (B, G, D, H, W) or store.numel() * 4 < cv_store_bytes_of(B, V, C, G, D, rows, W):
         raise _lib.MvsHipError("cv_merge_rows: weight %s / volume %s / store size do not match the shape" % (tuple(weight.shape), tuple(volume.shape)))
     tag = ("cv_merge_kernel<%d>" % (256 // C), "bytes", 4.0 * B * nrows * W * (G * D))
     _call("mvs_cv_merge_rows_fwd", tag, _ptr(store), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W, int(y0), int(rows), int(r_lo), int(nrows),
@@ -424,7 +434,7 @@ def _view_table(view_idx, who: str):
     return (ctypes.c_int * len(flat))(*flat), len(rows), len(rows[0])
 
 
-def _chk_bank(bank: torch.Tensor, view_idx, depth: torch.Tensor, who: str):
+def _chk_bank(bank: torch.Tensor, view_idx, depth: torch.Tensor, who: str, rt: Optional[torch.Tensor] = None):
     _chk(bank, "feature bank")
     if bank.dim() != 4:
         raise _lib.MvsHipError("%s: the bank must be channel-last [N,H,W,C], got %s" % (who, tuple(bank.shape)))
@@ -433,6 +443,8 @@ def _chk_bank(bank: torch.Tensor, view_idx, depth: torch.Tensor, who: str):
     D = depth.shape[1] if depth.dim() == 4 else -1
     if depth.shape != (B, D, H, W):
         raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, "D", H, W), tuple(depth.shape)))
+    if rt is not None and rt.shape != (B, V - 1, 12):
+        raise _lib.MvsHipError("rt must be [B,V-1,12]=%s, got %s" % ((B, V - 1, 12), tuple(rt.shape)))
     return table, B, V, N, H, W, C, D
 
 
@@ -440,9 +452,7 @@ def cv_entropy_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torc
     """:func:`cv_entropy` over a bank ``[N,H,W,C]``: view ``v`` of sample ``b`` is ``bank[view_idx[b][v]]``.  Bit-identical to the dense op on
     the gathered views."""
     _chk(rt, "rt"), _chk(depth, "depth_values")
-    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_entropy_views")
-    if rt.shape != (B, V - 1, 12):
-        raise _lib.MvsHipError("rt must be [B,V-1,12]=%s, got %s" % ((B, V - 1, 12), tuple(rt.shape)))
+    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_entropy_views", rt)
     ent = torch.empty(B, V - 1, H, W, device=bank.device, dtype=torch.float32)
     tag = ("cv_entropy_views_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
     _call("mvs_cv_entropy_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _cv_flags(exact), _stream())
@@ -456,8 +466,7 @@ def cv_aggregate_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: to
     table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_aggregate_views")
     if rt.shape != (B, V - 1, 12) or weight.shape != (B, V - 1, H, W):
         raise _lib.MvsHipError("cv_aggregate_views: rt %s / weight %s do not match B=%d V=%d H=%d W=%d" % (tuple(rt.shape), tuple(weight.shape), B, V, H, W))
-    vol = torch.empty(B, G, D, H, W, device=bank.device, dtype=torch.float32)
-    sim = torch.empty(B, H, W, device=bank.device, dtype=torch.float32) if want_sim_depth else None
+    vol, sim = _cv_volume(B, G, D, H, W, bank.device, want_sim_depth)
     tag = ("cv_aggregate_views_kernel<%d,%s>" % (C // 4, "true" if want_sim_depth else "false"), "bytes", 4.0 * B * H * W * (V * C + D + G * D))
     _call("mvs_cv_aggregate_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W, _ptr(vol), _ptr(sim),
           _cv_flags(exact), _stream())
@@ -469,20 +478,16 @@ def cv_corr_rows_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: to
     """:func:`cv_corr_rows` over a bank (see :func:`cv_entropy_views`); ``y0 = 0, rows = H`` is :func:`cv_corr`.  The store is read by
     :func:`cv_merge` / :func:`cv_merge_rows`, which never see features."""
     _chk(rt, "rt"), _chk(depth, "depth_values")
-    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_corr_rows_views")
-    if rt.shape != (B, V - 1, 12):
-        raise _lib.MvsHipError("rt must be [B,V-1,12]=%s, got %s" % ((B, V - 1, 12), tuple(rt.shape)))
+    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_corr_rows_views", rt)
     y0, rows = int(y0), int(rows)
     if y0 < 0 or rows < 1 or y0 + rows > H:
         raise _lib.MvsHipError("cv_corr_rows_views: rows [%d, %d) outside the image (H = %d)" % (y0, y0 + rows, H))
-    nbytes = int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, rows, W))
+    nbytes = cv_store_bytes_of(B, V, C, G, D, rows, W)
     if nbytes <= 0:
         raise _lib.MvsHipError("stored-correlation sweeps are not built for C=%d, G=%d, D=%d" % (C, G, D))
-    if store is None or store.numel() * 4 < nbytes:
-        store = torch.empty(nbytes // 4, device=bank.device, dtype=torch.float32)
-    else:
+    if store is not None and store.numel() * 4 >= nbytes:
         _chk(store, "correlation store")
-    ent = torch.empty(B, V - 1, rows, W, device=bank.device, dtype=torch.float32)
+    ent, store = _cv_corr_out(B, V, rows, W, nbytes, store, bank.device)
     tag = ("cv_corr_views_kernel<%d>" % (C // 4), "bytes", 4.0 * B * rows * W * (V * C + D))
     _call("mvs_cv_corr_rows_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, y0, rows, _ptr(ent), _ptr(store),
           _cv_flags(exact), _stream())
@@ -492,7 +497,7 @@ def cv_corr_rows_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: to
 def cv_bank_store_bytes(bank: torch.Tensor, B: int, V: int, D: int, G: int) -> int:
     """:func:`cv_store_bytes` for ``B`` samples of ``V`` views taken from a bank ``[N,H,W,C]``."""
     _, H, W, C = bank.shape
-    return int(_lib.load().mvs_cv_corr_store_bytes(B, V, C, G, D, H, W))
+    return cv_store_bytes_of(B, V, C, G, D, H, W)
 
 
 def cv_tiled_supported(feat: torch.Tensor) -> bool:
@@ -524,8 +529,7 @@ def cv_tiled_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor
     D = depth.shape[1]
     if weight.shape != (B, V - 1, H, W):
         raise _lib.MvsHipError("vis_weight must be %s, got %s" % ((B, V - 1, H, W), tuple(weight.shape)))
-    vol = torch.empty(B, G, D, H, W, device=feat.device, dtype=torch.float32)
-    sim = torch.empty(B, H, W, device=feat.device, dtype=torch.float32) if want_sim_depth else None
+    vol, sim = _cv_volume(B, G, D, H, W, feat.device, want_sim_depth)
     ws = None
     if want_sim_depth:
         nbytes = _lib.load().mvs_cv_tiled_workspace_bytes(B, V, C, D, H, W)

@@ -7,8 +7,7 @@ Every switch the package reads has a row in :data:`TABLE` (the README's switch t
 * ``int`` / ``float``: ``int(value)`` / ``float(value)``        * ``str``: the text, one of ``values`` where those are given
 
 ``read`` says when the package looks: ``call`` (every call that reaches the site), ``pack`` (when a layer's cached weights are rebuilt; the
-regularizer's and the visibility CNN's caches carry these values in their keys, so there a change rebuilds on the next forward - the FPN's and
-the ViT's caches do not) or ``import``.  The variables that
+caches carry these values in their keys, so a change rebuilds on the next forward) or ``import``.  The variables that
 ``libmvs_hip.so`` reads itself (``mvs::env_int`` / ``mvs::env_str``) are not in this table.
 """
 from __future__ import annotations

@@ -103,7 +103,8 @@ class VisionTransformer(nn.Module):
         return self._pos_cache["pos"]
 
     def _prepared(self):
-        key = _versions(self)
+        packed_ok = self._packed_ok()
+        key = (_versions(self), packed_ok)                   # MVS_VIT_PACKED as the operands were packed under it
         if self._cache is None or self._cache[0] != key:
             pw = _f(self.patch_embed.proj.weight).reshape(self.embed_dim, -1)
             blocks = []
@@ -113,7 +114,7 @@ class VisionTransformer(nn.Module):
                                                     b.mlp.fc2.weight, b.mlp.fc2.bias)))
             # the linear layers' weights split once into (h, m, l) bf16 MFMA fragments (csrc/vit_packed.hip): no block of any GEMM splits them again
             packed = None
-            if self._packed_ok():
+            if packed_ok:
                 packed = [tuple(ops.x3p_pack(w) for w in (b[2], b[4], b[8], b[10])) for b in blocks]
             _publish_cache()
             self._cache = (key, pw, _f(self.patch_embed.proj.bias), blocks, _f(self.norm.weight), _f(self.norm.bias), _f(self.cls_token), packed)
@@ -124,12 +125,12 @@ class VisionTransformer(nn.Module):
         C, NH = self.embed_dim, self.num_heads
         return C == NH * 64 and C % 128 == 0 and C <= 512 and sw.flag("MVS_VIT_PACKED")
 
-    def _run_packed(self, x: torch.Tensor, want_cls: bool):
+    def _run_packed(self, x: torch.Tensor, want_cls: bool, prep):
         """The 12 blocks on pre-split operands: LayerNorm -> packed, qkv GEMM -> packed Q / K / V^T per head, flash attention -> packed,
         projection (+ residual) -> fp32 tokens, LayerNorm -> packed, fc1 (+ GELU) -> packed, fc2 (+ residual) -> fp32 tokens.  Token rows are
         laid out [B][Np] with Np = N rounded up to 32 (padding rows stay finite and are masked as keys).  ``want_cls``: also the CLS query's
         attention row of the last block, ``[B, heads, N]`` - the only part of the attention matrix the model reads (mvsformer_model.py:257)."""
-        pw, pb, blocks, nw, nb, cls, packed = self._prepared()
+        pw, pb, blocks, nw, nb, cls, packed = prep
         x = x.detach().to(torch.float32)
         B, nc, h, w = x.shape
         P, C, NH = self.patch_size, self.embed_dim, self.num_heads
@@ -171,9 +172,10 @@ class VisionTransformer(nn.Module):
                 raise _lib.MvsHipError("VisionTransformer.forward: training mode is built for forward_with_last_att / forward_with_cls_att, what "
                                        "DINOMVSNet calls (mvsformer_model.py:216-220); the plain forward is eval only")
             return self._run_train(x, want_att)
-        if want_att is not True and self._packed_ok():
-            return self._run_packed(x, want_att == "cls")
-        pw, pb, blocks, nw, nb, cls = self._prepared()[:6]
+        prep = self._prepared()
+        if want_att is not True and prep[6] is not None:     # the pre-split operands exist: MVS_VIT_PACKED and a ViT they are built for
+            return self._run_packed(x, want_att == "cls", prep)
+        pw, pb, blocks, nw, nb, cls = prep[:6]
         x = x.detach().to(torch.float32)
         B, nc, h, w = x.shape
         P, C, NH = self.patch_size, self.embed_dim, self.num_heads
@@ -599,9 +601,9 @@ class _DecoderBase(nn.Module):
         return all(c % 32 == 0 for c in chans) and all(c % 4 == 0 for c in outs) and sw.flag("MVS_VIT_PACKED")
 
     def _prepared(self):
-        key = _versions(self)
+        packed = self._packed_ok()
+        key = (_versions(self), packed)                      # MVS_VIT_PACKED as the operands were packed under it
         if self._cache is None or self._cache[0] != key:
-            packed = self._packed_ok()
             prep = dict(packed=packed)
             a = getattr(self, "attn", None)
             if a is not None:

@@ -109,8 +109,7 @@ def test_decoder_v2_switch_routes_agree(dev, monkeypatch, N, h, w):
     vits = [torch.randn(N, c[3 - i], h << i, w << i, generator=g).to(dev) for i in range(3)]
     outs = {}
     for v in ("1", "0"):
-        monkeypatch.setenv("MVS_FPN_V2_TAIL", v)
-        dec._cache = None                                    # the switch is read when the weights are packed
+        monkeypatch.setenv("MVS_FPN_V2_TAIL", v)             # (part of the cache key: the next forward packs again)
         outs[v] = [o.clone() for o in dec(*convs, *vits)]
         assert ("tail" in dec._cache[1]) == (v == "1")
     torch.cuda.synchronize()

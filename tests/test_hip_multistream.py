@@ -18,14 +18,6 @@ VARIANTS = {"default": {}, "conv_wino": {"MVS_CONV_WINO": "1", "MVS_CONV_X3": "s
 KEYS = ("refined_depth", "photometric_confidence")
 
 
-def _reset_caches(net):
-    for mod in net.modules():
-        if hasattr(mod, "_cache"):
-            mod._cache = None
-        if hasattr(mod, "_vis_cache"):
-            mod._vis_cache = None
-
-
 def _stage_outputs(o):
     out = {k: o[k] for k in KEYS}
     for i in range(1, 5):
@@ -45,7 +37,6 @@ def run_variant(env, n_runs, dev, H=1152, W=1536):
         net = m.CascadeMVS().eval()
         m.randomize_bn_(net, seed=1)
         net = net.to(dev)
-        _reset_caches(net)
         feats, proj, dv, _ = synth.make_inputs(5, H, W, seed=0, device=dev)
         tmp = [5.0, 5.0, 5.0, 1.0]
         ref = _stage_outputs(net(feats, proj, dv, tmp=tmp))

@@ -742,10 +742,6 @@ def test_stage_vs_oracle_mixed_kernel_paths(dev, C, ndepth, H, W, V, B):
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         try:
-            for mod in net.modules():                                   # the switches are read when the caches are built
-                if hasattr(mod, "_cache"):
-                    mod._cache = None
-            net._vis_cache = None
             got = net(feat.to(dev), proj.to(dev), hyp.to(dev), tmp=5.0)
         finally:
             for k, v in old.items():

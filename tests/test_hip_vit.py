@@ -231,8 +231,7 @@ def test_vit_packed_path_matches_split_on_the_fly_path(dev, monkeypatch):
     img = torch.randn(2, 3, 80, 112, device=dev)
     tok, att = net.forward_with_cls_att(img)
     full_tok, full_att = net.forward_with_last_att(img)      # the whole attention matrix: the materialized path
-    monkeypatch.setenv("MVS_VIT_PACKED", "0")
-    net._cache = None
+    monkeypatch.setenv("MVS_VIT_PACKED", "0")                # (part of the cache key: the next forward prepares again)
     tok0, att0 = net.forward_with_cls_att(img)
     assert tok.shape == tok0.shape == (2, 36, 384) and att.shape == att0.shape == (2, 6, 36)
     assert _rel(tok, tok0.cpu()) < 2e-5 and _rel(att, att0.cpu()) < 2e-5

@@ -1,5 +1,7 @@
-"""Which kernel an eval-mode regularizer layer takes (mvsformer_amd.module.conv_route / deconv_route / tail_route: pure functions, no GPU, no
-library) and the MVS_* switch table (mvsformer_amd.switches) with its README rendering."""
+"""Which kernel an eval-mode layer takes - the regularizer's (mvsformer_amd.module.conv_route / deconv_route / tail_route), the FPN's
+(mvsformer_amd.fpn.encoder_route / decoder_route / v2_tail_route) and a stage's sweeps (mvsformer_amd.stagenet.sweep_plan, the visibility mode):
+pure functions, no GPU, no library - and the MVS_* switch table (mvsformer_amd.switches) with its README rendering."""
+import ast
 import itertools
 import os
 import re
@@ -92,6 +94,113 @@ def test_conv_x3_off_leaves_no_split_form():
         assert deconv_route(cin, cout, sd, shape, forms, off, True) == "fp32"
         assert tail_route(cin, cout, sd, shape, off) in ("tail_fp32", "unfused")
     assert tail_route(16, 8, 1, (4, 32, 80), off) == "tail_fp32"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ FPN
+FPN_CH = {"conv00": (3, 8), "conv01": (8, 8), "downsample1": (8, 16), "conv10": (16, 16), "conv11": (16, 16), "downsample2": (16, 32),
+          "conv20": (32, 32), "conv21": (32, 32), "downsample3": (32, 64), "conv30": (64, 64), "conv31": (64, 64)}
+
+
+def _fpn_switches(monkeypatch, x3):
+    from mvsformer_amd.fpn import fpn_switches
+    monkeypatch.delenv("MVS_FPN_X3", raising=False) if x3 is None else monkeypatch.setenv("MVS_FPN_X3", x3)
+    return fpn_switches()
+
+
+@pytest.mark.parametrize("x3,x3_ok,x3s_ok,want", [
+    (None, True, False, "x3"), (None, True, True, "x3"), (None, False, True, "x3s"), (None, False, False, "fp32"),
+    ("strip", True, False, "x3"), ("strip", True, True, "x3"), ("strip", False, True, "x3s"), ("strip", False, False, "fp32"),
+    ("0", True, False, "fp32"), ("0", True, True, "fp32"), ("0", False, True, "fp32"), ("0", False, False, "fp32"),
+])
+def test_encoder_route(monkeypatch, x3, x3_ok, x3s_ok, want):
+    from mvsformer_amd.fpn import FPNEncoder, encoder_route
+    fs = _fpn_switches(monkeypatch, x3)
+    assert [name for name, _, _ in FPNEncoder.LAYERS] == list(FPN_CH)
+    for name, k, stride in FPNEncoder.LAYERS:
+        assert encoder_route(*FPN_CH[name], k, stride, x3_ok, x3s_ok, fs) == want, name
+
+
+@pytest.mark.parametrize("x3,want", [
+    (None, [("fpn_lvl_x3", False), ("fpn_lvl_x3", True), ("fpn_cp", False)]),      # level 2 hands over channel-last: fpn_cp reads it
+    ("strip", [("fpn_lvl_x3", False), ("fpn_lvl_x3", False), ("fpn_x3", False)]),
+    ("0", [("fpn", False), ("fpn", False), ("fpn", False)]),
+])
+def test_decoder_route(monkeypatch, x3, want):
+    from mvsformer_amd.fpn import decoder_route
+    fs = _fpn_switches(monkeypatch, x3)
+    assert [decoder_route(level, fs) for level in (1, 2, 3)] == want
+
+
+@pytest.mark.parametrize("tail_chs,switch,want", [(True, None, "fused"), (True, "1", "fused"), (True, "0", "gemm"), (False, None, "gemm"),
+                                                  (False, "0", "gemm")])
+def test_v2_tail_route(monkeypatch, tail_chs, switch, want):
+    from mvsformer_amd.fpn import fpn_switches, v2_tail_route
+    monkeypatch.delenv("MVS_FPN_V2_TAIL", raising=False) if switch is None else monkeypatch.setenv("MVS_FPN_V2_TAIL", switch)
+    assert fpn_switches().v2_tail is (switch != "0")
+    assert v2_tail_route(tail_chs, fpn_switches()) == want
+
+
+# --------------------------------------------------------------------------------------------------------------------------- sweeps
+MB = 2 ** 20
+# the store sizes ``ops.cv_store_bytes`` gives at config 2 (pinned with the library in test_abi.py): stage 1 = 5 views of 144x192, C 64, D 32: 121.5 MiB
+# (the "127 MB"); stage 2 = 288x384, C 32, D 16: 243 MiB (the "254 MB")
+S1, S2 = 127401984, 254803968
+
+
+@pytest.mark.parametrize("nbytes,H,limit_mb,bands,want", [
+    (S1, 144, 160.0, 1, 1),                                                 # 127 MB: one store for the whole image
+    (S2, 288, 160.0, 1, 0),                                                 # 254 MB: recompute (banding is opt-in)
+    (-1, 576, 160.0, 1, 0),                                                 # C = 16: not built for the shape
+    (S2, 288, 160.0, 4, 2),                                                 # two bands of 144 + 7 rows: 133 MB each
+    (S1, 144, 160.0, 4, 1),
+    (S2, 288, 70.0, 4, 4),                                                  # 72 + 7 rows: 69.7 MB
+    (S1, 144, 70.0, 4, 2),
+    (S2, 288, 400.0, 4, 1),
+    (S1, 144, 0.0, 4, 0),                                                   # limit 0: the stored-correlation sweeps are off
+    (160 * MB, 144, 160.0, 1, 1),                                           # exactly the limit
+    (160 * MB + 1, 144, 160.0, 1, 0),
+])
+def test_sweep_plan(nbytes, H, limit_mb, bands, want):
+    from mvsformer_amd.stagenet import TILED, StageSwitches, sweep_plan
+    ss = StageSwitches(store_max_mb=limit_mb, store_bands=bands)
+    assert (S1 / MB, S2 / MB) == (121.5, 243.0)
+    for tiled_ok in (False, True):
+        assert sweep_plan(nbytes, H, tiled_ok, ss) == want                  # MVS_CV_TILED unset: what the features allow does not matter
+        assert sweep_plan(nbytes, H, tiled_ok, ss._replace(tiled=True)) == (TILED if tiled_ok else want)
+    assert TILED not in (0, 1, 2, 3, 4)
+
+
+def test_stage_switches_defaults_are_the_documented_ones(monkeypatch):
+    from mvsformer_amd.stagenet import StageSwitches, stage_switches
+    for name in ("MVS_CV_TILED", "MVS_CV_STORE_MAX_MB", "MVS_CV_STORE_BANDS", "MVS_VIS", "MVS_VIS_WINO"):
+        monkeypatch.delenv(name, raising=False)
+    assert stage_switches() == StageSwitches() == (False, 160.0, 1, "x3")
+    monkeypatch.setenv("MVS_CV_TILED", "1"), monkeypatch.setenv("MVS_CV_STORE_MAX_MB", "70"), monkeypatch.setenv("MVS_CV_STORE_BANDS", "4")
+    assert stage_switches() == (True, 70.0, 4, "x3")
+
+
+@pytest.mark.parametrize("vis,wino,want", [(None, None, "x3"), (None, "0", "valu"), ("x3", None, "x3"), ("x3", "0", "x3"), ("wino", None, "wino"),
+                                           ("wino", "0", "wino"), ("valu", None, "valu"), ("valu", "0", "valu")])
+def test_visibility_mode(monkeypatch, vis, wino, want):
+    from mvsformer_amd.stagenet import stage_switches
+    for name, value in (("MVS_VIS", vis), ("MVS_VIS_WINO", wino)):
+        monkeypatch.delenv(name, raising=False) if value is None else monkeypatch.setenv(name, value)
+    assert stage_switches().vis == want
+
+
+def test_eval_forwards_read_no_switch_themselves():
+    """In fpn.py and stagenet.py the switch-tuple readers are the only functions that call the switch reader: no ``forward`` / ``forward_bank`` (or
+    anything else, the eval body ``StageNet._eval`` included) holds a ``sw.`` call."""
+    for name, readers in (("fpn.py", {"fpn_switches"}), ("stagenet.py", {"stage_switches"})):
+        src = open(os.path.join(REPO, "mvsformer_amd", name), encoding="utf-8").read()
+        assert re.search(r"^from \. import .*\bswitches as sw\b", src, re.M), name
+        seen, forwards = set(), 0
+        for fn in ast.walk(ast.parse(src)):
+            if isinstance(fn, ast.FunctionDef):
+                forwards += fn.name in ("forward", "forward_bank")
+                if any(isinstance(n, ast.Name) and n.id == "sw" for n in ast.walk(fn)):
+                    seen.add(fn.name)
+        assert seen == readers and forwards >= 2, (name, seen)
 
 
 # --------------------------------------------------------------------------------------------------------------------------- switch table

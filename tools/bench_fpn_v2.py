@@ -84,7 +84,6 @@ def main():
     vits = [torch.randn(N, c[3 - i], (H >> 3) << i, (W >> 3) << i, device=dev) for i in range(3)]
     for v in ("1", "0"):
         os.environ["MVS_FPN_V2_TAIL"] = v
-        dec._cache = None
         res["b_decoder_v2_tail=%s" % v] = regions(lambda: dec(*convs, *vits), a.regions, max(2, a.iters // 2))
     os.environ.pop("MVS_FPN_V2_TAIL")
     del convs, vits, c01, dec
