@@ -46,7 +46,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 47
+#define MVS_ABI_VERSION 48
 
 typedef void* mvs_stream_t;
 
@@ -484,6 +484,36 @@ int mvs_prob1_fwd(const float* x, const float* w, const float* bias, int B, int 
 int mvs_init_inverse_range(const float* depth_range, int N, int B, int D, int H, int W, float* hyp, mvs_stream_t stream);
 int mvs_schedule_inverse_range(const float* prev_depth, const float* prev_hyp, int Dp, float split_itv,
                                int B, int D, int H, int W, float* hyp, mvs_stream_t stream);
+/* The linear-depth pair (inverse_depth=False), models/module.py:622-630 and 687-699; index 0 = near (hypotheses ASCEND with d).
+ *   init:     hyp[b,d,:,:] = min + float(d) * (max - min)/(D-1), min = depth_range[b,0], max = depth_range[b,N-1]; the product and the sum
+ *             each rounded to fp32, the reference's operation order
+ *   schedule: prev_depth [B,H/2,W/2] (integer halves: odd H, W allowed), depth_interval [B] DEVICE pointer, step = ratio * depth_interval[b];
+ *             at low resolution lo = max(depth - D/2*step, 0.01), hi = depth + D/2*step, sample d = lo + float(d) * (hi - lo)/(D-1), then
+ *             the align_corners=True upsampling to H x W (the depth axis keeps its size: bilinear in H and W) */
+int mvs_init_range(const float* depth_range, int N, int B, int D, int H, int W, float* hyp, mvs_stream_t stream);
+int mvs_schedule_range(const float* prev_depth, const float* depth_interval, float ratio, int B, int D, int H, int W, float* hyp,
+                       mvs_stream_t stream);
+
+/* Training heads of depth_type 'mixup_ce' and of the regression types (models/mvsformer_model.py:126-136 and 137-146), one launch
+ * forward and one backward each, fp32, deterministic (no atomics), any D >= 2 (D = 1: MVS_EINVAL).  pre, depth_values, prob_volume,
+ * dprob, dpre [B,D,H,W]; depth, conf, ddepth [B,H,W].
+ *   reg fwd:    prob_volume = softmax_d(pre), depth = sum_d prob*depth_values, conf = max_d prob (conf may be NULL: the windowed
+ *               confidence of the larger depth counts is mvs_conf_regression on prob_volume)
+ *   reg bwd:    g_d = dprob_d + ddepth*depth_values_d (dprob / ddepth may be NULL = zero), dpre_d = prob_d * (g_d - sum_k prob_k g_k);
+ *               evaluated with depth_values relative to plane 0 (a constant in g cancels exactly)
+ *   mixup fwd:  prob_volume; pair [B,H,W] (int32) = the first maximum of prob[d] + prob[d+1] as mvs_mixup_head finds it, conf = that sum,
+ *               depth = the pair's hypotheses mixed by the pair probabilities renormalised with +1e-7
+ *   mixup bwd:  ddepth reaches prob[pair] and prob[pair+1] only: with s = p_l + p_r + 1e-7, d(depth)/d(p_l) = (h_l - depth)/s and
+ *               likewise for p_r (evaluated as (1e-7 h_l - (h_r - h_l) p_r)/s^2 and (1e-7 h_r + (h_r - h_l) p_l)/s^2: the same values
+ *               without the cancellation against the rounded depth); plus dprob, then through the softmax as above */
+int mvs_reg_head_fwd(const float* pre, const float* depth_values, int B, int D, int H, int W, float* prob_volume, float* depth,
+                     float* conf, mvs_stream_t stream);
+int mvs_reg_head_bwd(const float* prob_volume, const float* depth_values, const float* dprob, const float* ddepth, int B, int D,
+                     int H, int W, float* dpre, mvs_stream_t stream);
+int mvs_mixup_train_fwd(const float* pre, const float* depth_values, int B, int D, int H, int W, float* prob_volume, float* depth,
+                        float* conf, int* pair, mvs_stream_t stream);
+int mvs_mixup_train_bwd(const float* prob_volume, const float* depth_values, const int* pair, const float* dprob, const float* ddepth,
+                        int B, int D, int H, int W, float* dpre, mvs_stream_t stream);
 
 /* Nearest-neighbour upsample + accumulate of the per-stage confidences (mvsformer_model.py:297-301):
  *   acc [B,Hf,Wf] += nearest(conf [B,H,W]) * weight */

@@ -2,7 +2,7 @@
 
 Hand-written HIP kernels behind a C ABI (``include/mvs_hip.h`` -> ``libmvs_hip.so``) re-exposed with the
 reference's own Python interface: ``StageNet`` (alias ``DepthNet``), ``CostRegNet``, ``CostRegNet3D``,
-``homo_warping_3D_with_mask`` (alias ``homo_warping``), ``depth_regression``, the inverse-depth schedulers, and
+``homo_warping_3D_with_mask`` (alias ``homo_warping``), ``depth_regression``, the inverse- and linear-depth schedulers, and
 ``install()`` to rebind them inside an unmodified reference checkout.  ``synth`` (pure torch) builds the
 synthetic DTU-shaped inputs used by the tests and ``bench.py``.
 
@@ -12,7 +12,7 @@ from . import synth  # noqa: F401
 
 __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "CascadeMVS", "homo_warping_3D_with_mask",
            "homo_warping_3D", "homo_warping", "depth_regression", "conf_regression", "init_inverse_range",
-           "schedule_inverse_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
+           "schedule_inverse_range", "init_range", "schedule_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
            "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference"]
 
 
@@ -21,7 +21,7 @@ def __getattr__(name):
         from . import stagenet
         return getattr(stagenet, name)
     if name in ("CostRegNet", "CostRegNet3D", "Conv3d", "Deconv3d", "ConvBnReLU", "depth_regression", "conf_regression",
-                "init_inverse_range", "schedule_inverse_range"):
+                "init_inverse_range", "schedule_inverse_range", "init_range", "schedule_range"):
         from . import module
         return getattr(module, name)
     if name in ("homo_warping_3D_with_mask", "homo_warping_3D", "homo_warping", "diff_homo_warping_3D_with_mask"):

@@ -20,7 +20,7 @@ from . import switches as sw
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = sw.text("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 47
+ABI_VERSION = 48
 
 from ctypes import c_double  # noqa: E402
 
@@ -209,6 +209,12 @@ SIGNATURES = {
     "mvs_pointcloud_scatter": (I, [P, P, P, I, I, I, I, P, P, I, P, L, P, P, P, P]),
     "mvs_init_inverse_range": (I, [P, I, I, I, I, I, P, P]),
     "mvs_schedule_inverse_range": (I, [P, P, I, F, I, I, I, I, P, P]),
+    "mvs_init_range": (I, [P, I, I, I, I, I, P, P]),
+    "mvs_schedule_range": (I, [P, P, F, I, I, I, I, P, P]),
+    "mvs_reg_head_fwd": (I, [P, P, I, I, I, I, P, P, P, P]),
+    "mvs_reg_head_bwd": (I, [P, P, P, P, I, I, I, I, P, P]),
+    "mvs_mixup_train_fwd": (I, [P, P, I, I, I, I, P, P, P, P, P]),
+    "mvs_mixup_train_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P]),
     "mvs_conf_accumulate": (I, [P, I, I, I, P, I, I, F, P]),
     "mvs_conf_stack": (I, [P, P, P, P, I, I, P, P]),
     "mvs_conv2d_packed_floats": (L, [I, I, I]),

@@ -25,7 +25,9 @@ _RULES = [
     (r"^conv3d_kernel", ["conv3d_fwd.hip", "conv_common.h", "common.h", "prims.h", PUB]),
     (r"^(deconv3d_kernel|prob3)", ["conv3d.hip", "conv_common.h", "common.h", "prims.h", PUB]),
     (r"^pack_deconv_s1", ["deconv3d_s1.hip", "conv_common.h", "common.h", "prims.h", PUB]),
-    (r"^(head_|prob1_kernel|mvs_prob1_fwd|init_inverse|schedule_inverse|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|mvs_conf)", ["head.hip", "common.h", PUB]),
+    (r"^(reg_head|mixup_train|mvs_reg_head|mvs_mixup_train)", ["head_train.hip", "common.h", PUB]),
+    (r"^(head_|prob1_kernel|mvs_prob1_fwd|init_inverse|schedule_inverse|init_range|schedule_range|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|"
+     r"mvs_init_range|mvs_schedule_range|mvs_conf)", ["head.hip", "common.h", PUB]),
     (r"^(proj_|mvs_proj)", ["proj.hip", "common.h", PUB]),
     (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
     (r"^(fpn_v2_tail|mvs_fpn_v2_tail)", ["fpn_v2_tail.hip", "conv_common.h", "common.h", "prims.h", PUB]),

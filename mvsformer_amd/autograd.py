@@ -287,6 +287,56 @@ class HeadFn(torch.autograd.Function):
         return ops.softmax_bwd(prob, dprob.contiguous()), None, None
 
 
+def _head_grad(g):
+    """An upstream gradient of a head node as the kernels take it: None (nothing depends on that output) stays None."""
+    return None if g is None else g.contiguous()
+
+
+class RegHeadFn(torch.autograd.Function):
+    """Regression head (mvsformer_model.py:111,137-146): softmax over depth, ``depth = sum_d prob * hyp``, confidence = the windowed
+    probability mass of ``conf_regression`` (``window`` = its n; 0: max probability).  ``prob`` and ``depth`` are differentiable, one
+    launch each way; the confidence is not."""
+
+    @staticmethod
+    def forward(ctx, pre, hyp, window):
+        pre = pre.contiguous()
+        prob, depth, conf = ops.reg_head_fwd(pre, hyp, want_conf=not window)
+        if window:
+            conf = ops.conf_regression(prob, int(window))
+        ctx.save_for_backward(prob, hyp)
+        ctx.mark_non_differentiable(conf)
+        ctx.set_materialize_grads(False)
+        return prob, depth, conf
+
+    @staticmethod
+    def backward(ctx, dprob, ddepth, _dc):
+        prob, hyp = ctx.saved_tensors
+        if dprob is None and ddepth is None:
+            return None, None, None
+        return ops.reg_head_bwd(prob, hyp, _head_grad(dprob), _head_grad(ddepth)), None, None
+
+
+class MixupHeadFn(torch.autograd.Function):
+    """'mixup_ce' head (mvsformer_model.py:111,126-136): softmax over depth, the adjacent hypothesis pair with the largest probability sum,
+    ``depth`` = the pair's hypotheses mixed by its renormalised probabilities, confidence = that sum (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, pre, hyp):
+        pre = pre.contiguous()
+        prob, depth, conf, pair = ops.mixup_train_fwd(pre, hyp)
+        ctx.save_for_backward(prob, hyp, pair)
+        ctx.mark_non_differentiable(conf)
+        ctx.set_materialize_grads(False)
+        return prob, depth, conf
+
+    @staticmethod
+    def backward(ctx, dprob, ddepth, _dc):
+        prob, hyp, pair = ctx.saved_tensors
+        if dprob is None and ddepth is None:
+            return None, None
+        return ops.mixup_train_bwd(prob, hyp, pair, _head_grad(dprob), _head_grad(ddepth)), None
+
+
 # ---------------------------------------------------------------------------------------------------------
 class _EmbedConv2dWeightFn(torch.autograd.Function):
     """``[Cout,Cin,3,3]`` -> ``[Cout,cin_pad,3,3,3]`` with the 2-D kernel in the centre depth tap, zeros elsewhere: one fill + one strided

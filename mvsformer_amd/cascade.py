@@ -1,7 +1,9 @@
 """The coarse-to-fine loop the reference's top models run around ``StageNet`` — restated from
 ``DINOMVSNet.forward`` / ``TwinMVSNet.forward`` (models/mvsformer_model.py:273-306 / 410-449) for callers that
 start from precomputed per-stage feature maps (the bench, the tests, inference sharding).  Feature extraction
-(FPN + ViT) is outside the path and not part of this package.
+(FPN + ViT) is outside the path and not part of this package.  ``args["inverse_depth"]`` picks the hypothesis schedulers as
+the reference does (mvsformer_model.py:283-294): ``True`` samples uniformly in inverse depth (``init_inverse_range`` /
+``schedule_inverse_range``), ``False`` uniformly in depth (``init_range`` / ``schedule_range``, the CasMVSNet recipe).
 """
 from __future__ import annotations
 
@@ -11,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, switches as sw
-from .module import init_inverse_range, schedule_inverse_range
+from .module import init_inverse_range, init_range, schedule_inverse_range
 from .stagenet import StageNet
 
 DEFAULT_ARGS = dict(base_ch=8, fusion_type="cnn", depth_type="ce", model_th=8, inverse_depth=True,
@@ -27,8 +29,7 @@ class CascadeMVS(nn.Module):
         self.args = dict(DEFAULT_ARGS, **(args or {}))
         self.ndepths = list(self.args["ndepths"])
         self.depth_interals_ratio = list(self.args["depth_interals_ratio"])
-        if not self.args.get("inverse_depth", False):
-            raise NotImplementedError("only inverse_depth=True (every shipped reference config) is built")
+        self.inverse_depth = bool(self.args.get("inverse_depth", False))
         self.fusions = nn.ModuleList([StageNet(self.args, self.ndepths[i], i) for i in range(len(self.ndepths))])
 
     def forward(self, features: Dict[str, torch.Tensor], proj_matrices: Dict[str, torch.Tensor], depth_values: torch.Tensor,
@@ -56,6 +57,20 @@ class CascadeMVS(nn.Module):
                 st._routed_by_cascade = False
                 st.train_pack().unroute()                       # the routed weights belong to this forward's graph only
 
+    def _hypotheses(self, i, depth_values, prev, device, H, W):
+        """Stage ``i``'s hypotheses ``[B,D,H,W]`` (mvsformer_model.py:283-294): uniform in inverse depth (descending with d) or, with
+        ``inverse_depth=False``, in depth (ascending), around the previous stage's detached depth from stage 2 on."""
+        if i == 0:
+            init = init_inverse_range if self.inverse_depth else init_range
+            return init(depth_values, self.ndepths[0], device, torch.float32, H, W)
+        depth = prev["depth"].detach()
+        if self.inverse_depth:
+            return schedule_inverse_range(depth, prev["depth_values"].detach(), self.ndepths[i], self.depth_interals_ratio[i], H, W)
+        # depth_interals_ratio[i] * depth_interval: the interval stays on the device (no host read inside a captured step)
+        dv = depth_values.detach().to(torch.float32)
+        return ops.schedule_range(depth.to(torch.float32).contiguous(), (dv[:, 1] - dv[:, 0]).contiguous(), self.ndepths[i],
+                                  self.depth_interals_ratio[i], H, W)
+
     def _forward(self, features, proj_matrices, depth_values, tmp):
         n = len(self.ndepths)
         last = features["stage%d" % n]
@@ -71,11 +86,7 @@ class CascadeMVS(nn.Module):
         for i in range(n):
             f = features["stage%d" % (i + 1)]
             H, W = f.shape[-2:]
-            if i == 0:
-                hyp = init_inverse_range(depth_values, self.ndepths[0], f.device, torch.float32, H, W)
-            else:
-                hyp = schedule_inverse_range(stage_out["depth"].detach(), stage_out["depth_values"].detach(), self.ndepths[i],
-                                             self.depth_interals_ratio[i], H, W)
+            hyp = self._hypotheses(i, depth_values, stage_out, f.device, H, W)
             stage_out = self.fusions[i](f, proj_matrices["stage%d" % (i + 1)], hyp, tmp=tmp)
             # nearest-upsampled confidences averaged over the stages (mvsformer_model.py:297-301,305)
             ops.conf_accumulate(stage_out["photometric_confidence"].detach().contiguous(), prob_maps, 1.0 / n)
@@ -103,10 +114,7 @@ class CascadeMVS(nn.Module):
             for i in range(n):
                 bank = banks["stage%d" % (i + 1)]
                 H, W = bank.shape[1:3]
-                if i == 0:
-                    hyp = init_inverse_range(depth_values, self.ndepths[0], bank.device, torch.float32, H, W)
-                else:
-                    hyp = schedule_inverse_range(stage_out["depth"], stage_out["depth_values"], self.ndepths[i], self.depth_interals_ratio[i], H, W)
+                hyp = self._hypotheses(i, depth_values, stage_out, bank.device, H, W)
                 stage_out = self.fusions[i].forward_bank(bank, rows, proj_matrices["stage%d" % (i + 1)], hyp, tmp=tmp)
                 ops.conf_accumulate(stage_out["photometric_confidence"].contiguous(), prob_maps, 1.0 / n)
                 outputs["stage%d" % (i + 1)] = stage_out

@@ -1,5 +1,5 @@
 // Per-pixel depth-axis sweeps around the regularizer: the softmax head (models/mvsformer_model.py:110-125 with
-// depth_regression, models/module.py:597-603), the inverse-depth hypothesis schedulers (module.py:633-653) and
+// depth_regression, models/module.py:597-603), the hypothesis schedulers (inverse depth module.py:633-653, linear :622-630,687-699) and
 // the confidence accumulation of the cascade loop (mvsformer_model.py:297-301).  All pure bandwidth: one lane
 // per pixel along W, every [B,D,H,W] plane access is a coalesced 256-B row segment per wavefront.
 #include "common.h"
@@ -119,32 +119,61 @@ __global__ void init_inverse_kernel(const float* __restrict__ range, int N, int 
     hyp[((size_t)(b * D + d) * H + y) * W + x] = 1.0f / inv;
 }
 
+// module.py:622-630: min + d * (max - min)/(D-1), min = range[:,0], max = range[:,-1] (the product, then the sum, each rounded to fp32)
+__global__ void init_range_kernel(const float* __restrict__ range, int N, int D, int H, int W, float* __restrict__ hyp) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    const int b = blockIdx.z / D, d = blockIdx.z % D;
+    if (x >= W || y >= H) return;
+    const float dmin = range[(size_t)b * N], dmax = range[(size_t)b * N + N - 1];
+    const float itv = (dmax - dmin) / (float)(D - 1);
+    const float step = (float)d * itv;
+    hyp[((size_t)(b * D + d) * H + y) * W + x] = dmin + step;
+}
+
+// F.interpolate(align_corners=True) from the previous stage's [H/2, W/2] map to pixel (x, y) of [H, W] (H, W >= 2; odd sizes round the
+// half down): the four low-resolution neighbours (y0|y1, x0|x1) and their weights.  The schedulers' depth axis has equal input and
+// output size, so its interpolation weight is exactly 0 and the trilinear upsampling is this bilinear one per plane.
+struct Up2 {
+    int Hl, Wl, ys[4], xs[4];
+    float ly0, ly1, lx0, lx1;
+    __device__ __forceinline__ Up2(int x, int y, int H, int W) {
+        Hl = H / 2, Wl = W / 2;
+        const float sy = (H > 1) ? (float)(Hl - 1) / (float)(H - 1) : 0.0f;
+        const float sx = (W > 1) ? (float)(Wl - 1) / (float)(W - 1) : 0.0f;
+        const float fy = sy * (float)y, fx = sx * (float)x;
+        const int y0 = (int)fy, x0 = (int)fx;
+        const int y1 = y0 + ((y0 < Hl - 1) ? 1 : 0), x1 = x0 + ((x0 < Wl - 1) ? 1 : 0);
+        ly1 = fy - (float)y0, lx1 = fx - (float)x0;
+        ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
+        ys[0] = y0, ys[1] = y0, ys[2] = y1, ys[3] = y1;
+        xs[0] = x0, xs[1] = x1, xs[2] = x0, xs[3] = x1;
+    }
+    __device__ __forceinline__ size_t at(int k) const { return (size_t)ys[k] * Wl + xs[k]; }
+    // v[k]: the sample at neighbour k
+    __device__ __forceinline__ float mix(float v0, float v1, float v2, float v3) const {
+        const float top = lx0 * v0 + lx1 * v1;
+        const float bot = lx0 * v2 + lx1 * v3;
+        return ly0 * top + ly1 * bot;
+    }
+};
+
 // module.py:642-653.  The low-resolution inverse-depth samples are generated on the fly from the previous
-// stage's depth map and its hypothesis planes 1 and 2, then trilinearly upsampled (align_corners=True; the
-// depth axis has equal input and output size, so its interpolation weight is exactly 0) and inverted.
+// stage's depth map and its hypothesis planes 1 and 2, then trilinearly upsampled (align_corners=True) and inverted.
 __global__ void schedule_inverse_kernel(const float* __restrict__ prev_depth, const float* __restrict__ prev_hyp, int Dp,
                                         float split_itv, int D, int H, int W, float* __restrict__ hyp) {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     const int b = blockIdx.z;
     if (x >= W || y >= H) return;
-    const int Hl = H / 2, Wl = W / 2;
-    const float sy = (H > 1) ? (float)(Hl - 1) / (float)(H - 1) : 0.0f;
-    const float sx = (W > 1) ? (float)(Wl - 1) / (float)(W - 1) : 0.0f;
-    const float fy = sy * (float)y, fx = sx * (float)x;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + ((y0 < Hl - 1) ? 1 : 0), x1 = x0 + ((x0 < Wl - 1) ? 1 : 0);
-    const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
-    const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-    const size_t lplane = (size_t)Hl * Wl;
+    const Up2 up(x, y, H, W);
+    const size_t lplane = (size_t)up.Hl * up.Wl;
     const float* pd = prev_depth + (size_t)b * lplane;
     const float* h1 = prev_hyp + ((size_t)b * Dp + 1) * lplane;
     const float* h2 = prev_hyp + ((size_t)b * Dp + 2) * lplane;
     // the four low-resolution neighbours' (inv_max, inv_min - inv_max): the 12 divisions happen once per pixel, not per plane
     float lo[4], span[4];
-    const int ys[4] = {y0, y0, y1, y1}, xs[4] = {x0, x1, x0, x1};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const size_t o = (size_t)ys[k] * Wl + xs[k];
+        const size_t o = up.at(k);
         const float last = 1.0f / h2[o] - 1.0f / h1[o];
         const float inv_d = 1.0f / pd[o];
         const float inv_min = inv_d + split_itv * last;
@@ -155,10 +184,35 @@ __global__ void schedule_inverse_kernel(const float* __restrict__ prev_depth, co
     float* out = hyp + (size_t)b * D * plane + (size_t)y * W + x;
     for (int d = 0; d < D; ++d) {
         const float itv = (float)d / (float)(D - 1);
-        const float top = lx0 * (lo[0] + span[0] * itv) + lx1 * (lo[1] + span[1] * itv);
-        const float bot = lx0 * (lo[2] + span[2] * itv) + lx1 * (lo[3] + span[3] * itv);
-        const float inv = ly0 * top + ly1 * bot;
+        const float inv = up.mix(lo[0] + span[0] * itv, lo[1] + span[1] * itv, lo[2] + span[2] * itv, lo[3] + span[3] * itv);
         out[(size_t)d * plane] = 1.0f / inv;
+    }
+}
+
+// module.py:687-699.  The low-resolution samples lo + d * (hi - lo)/(D-1) with lo = max(depth - D/2 * step, 0.01), hi = depth + D/2 * step
+// (clamped BEFORE the interpolation, as the reference does) from the previous stage's depth map, then upsampled like the inverse pair.
+// step = ratio * interval[b]: the interval is read on the device, so no host value enters a captured step.
+__global__ void schedule_range_kernel(const float* __restrict__ prev_depth, const float* __restrict__ interval, float ratio, int D, int H, int W,
+                                      float* __restrict__ hyp) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    const int b = blockIdx.z;
+    if (x >= W || y >= H) return;
+    const Up2 up(x, y, H, W);
+    const float* pd = prev_depth + (size_t)b * up.Hl * up.Wl;
+    const float step = ratio * interval[b];
+    const float half = ((float)D / 2.0f) * step;             // ndepth / 2 is a Python float: 2.5 for D = 5
+    float lo[4], itv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float dep = pd[up.at(k)];
+        lo[k] = fmaxf(dep - half, 0.01f);
+        itv[k] = ((dep + half) - lo[k]) / (float)(D - 1);
+    }
+    const size_t plane = (size_t)H * W;
+    float* out = hyp + (size_t)b * D * plane + (size_t)y * W + x;
+    for (int d = 0; d < D; ++d) {
+        const float fd = (float)d;
+        out[(size_t)d * plane] = up.mix(lo[0] + fd * itv[0], lo[1] + fd * itv[1], lo[2] + fd * itv[2], lo[3] + fd * itv[3]);
     }
 }
 
@@ -345,6 +399,23 @@ extern "C" int mvs_schedule_inverse_range(const float* prev_depth, const float* 
     dim3 grid(mvs::ceil_div(W, 64), mvs::ceil_div(H, 4), B), block(64, 4);
     hipLaunchKernelGGL(schedule_inverse_kernel, grid, block, 0, MVS_STREAM(stream), prev_depth, prev_hyp, Dp, split_itv, D, H, W, hyp);
     return mvs::finish_launch("mvs_schedule_inverse_range");
+}
+
+extern "C" int mvs_init_range(const float* depth_range, int N, int B, int D, int H, int W, float* hyp, mvs_stream_t stream) {
+    MVS_REQUIRE(depth_range && hyp, "mvs_init_range: null pointer");
+    MVS_REQUIRE(N >= 1 && B >= 1 && D >= 2 && H >= 1 && W >= 1 && (int64_t)B * D <= 65535, "mvs_init_range: bad shape");
+    dim3 grid(mvs::ceil_div(W, 64), mvs::ceil_div(H, 4), B * D), block(64, 4);
+    hipLaunchKernelGGL(init_range_kernel, grid, block, 0, MVS_STREAM(stream), depth_range, N, D, H, W, hyp);
+    return mvs::finish_launch("mvs_init_range");
+}
+
+extern "C" int mvs_schedule_range(const float* prev_depth, const float* depth_interval, float ratio, int B, int D, int H, int W, float* hyp,
+                                  mvs_stream_t stream) {
+    MVS_REQUIRE(prev_depth && depth_interval && hyp, "mvs_schedule_range: null pointer");
+    MVS_REQUIRE(B >= 1 && D >= 2 && H >= 2 && W >= 2 && B <= 65535, "mvs_schedule_range: bad shape B=%d D=%d H=%d W=%d", B, D, H, W);
+    dim3 grid(mvs::ceil_div(W, 64), mvs::ceil_div(H, 4), B), block(64, 4);
+    hipLaunchKernelGGL(schedule_range_kernel, grid, block, 0, MVS_STREAM(stream), prev_depth, depth_interval, ratio, D, H, W, hyp);
+    return mvs::finish_launch("mvs_schedule_range");
 }
 
 extern "C" int mvs_conf_accumulate(const float* conf, int B, int H, int W, float* acc, int Hf, int Wf, float weight,

@@ -26,6 +26,8 @@ _SYMBOLS = {
     "conf_regression": _m.conf_regression,
     "init_inverse_range": _m.init_inverse_range,
     "schedule_inverse_range": _m.schedule_inverse_range,
+    "init_range": _m.init_range,
+    "schedule_range": _m.schedule_range,
     "homo_warping_3D_with_mask": _w.homo_warping_3D_with_mask,
 }
 # the rows before the path: rebound on request (eval and training mode are both built; the ViT itself is frozen / eval-only)

@@ -524,7 +524,7 @@ class CostRegNet3D(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# heads and schedulers (reference models/module.py:597-619, 633-653)
+# heads and schedulers (reference models/module.py:597-619, 622-653, 687-699)
 # ---------------------------------------------------------------------------------------------------------
 def depth_regression(p, depth_values):
     """``sum_d p * depth_values``; ``depth_values`` is ``[B,D,H,W]`` or ``[B,D]`` (reference module.py:597-603)."""
@@ -542,6 +542,17 @@ def init_inverse_range(cur_depth, ndepths, device, dtype, H, W):
     """Reference signature (module.py:633); ``device``/``dtype`` are accepted for compatibility, output is fp32 on
     ``cur_depth``'s device."""
     return ops.init_inverse_range(cur_depth.to(torch.float32).contiguous(), ndepths, H, W)
+
+
+def init_range(cur_depth, ndepths, device, dtype, H, W):
+    """Reference signature (module.py:622); ``device``/``dtype`` are accepted for compatibility, output is fp32 on
+    ``cur_depth``'s device."""
+    return ops.init_range(cur_depth.to(torch.float32).contiguous(), ndepths, H, W)
+
+
+def schedule_range(cur_depth, ndepth, depth_inteval_pixel, H, W):
+    """Reference signature (module.py:687): ``depth_inteval_pixel [B]`` is the stage's ratio times the depth interval already."""
+    return ops.schedule_range(cur_depth.to(torch.float32).contiguous(), depth_inteval_pixel.to(torch.float32).contiguous(), ndepth, 1.0, H, W)
 
 
 def schedule_inverse_range(depth, depth_hypo, ndepths, split_itv, H, W):

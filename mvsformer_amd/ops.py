@@ -871,6 +871,85 @@ def schedule_inverse_range(prev_depth: torch.Tensor, prev_hyp: torch.Tensor, nde
     return hyp
 
 
+def init_range(depth_range: torch.Tensor, ndepths: int, H: int, W: int) -> torch.Tensor:
+    """Linear-depth hypotheses of stage 1 (reference module.py:622-630): ``[B,ndepths,H,W]`` ascending from ``depth_range[:,0]`` to ``[:,-1]``."""
+    _chk(depth_range, "depth_values")
+    B, N = depth_range.shape
+    hyp = torch.empty(B, ndepths, H, W, device=depth_range.device, dtype=torch.float32)
+    _call("mvs_init_range", None, _ptr(depth_range), N, B, ndepths, H, W, _ptr(hyp), _stream())
+    return hyp
+
+
+def schedule_range(prev_depth: torch.Tensor, depth_interval: torch.Tensor, ndepths: int, ratio: float, H: int, W: int) -> torch.Tensor:
+    """Linear-depth hypotheses of a later stage (reference module.py:687-699) around ``prev_depth [B,H//2,W//2]``, ``ndepths`` samples
+    ``ratio * depth_interval[b]`` apart; ``depth_interval [B]`` stays on the device."""
+    _chk(prev_depth, "depth"), _chk(depth_interval, "depth_interval")
+    if prev_depth.dim() != 3 or depth_interval.shape != (prev_depth.shape[0],) or tuple(prev_depth.shape[1:]) != (H // 2, W // 2):
+        raise _lib.MvsHipError("schedule_range: previous stage %s / interval %s is not half of (%d,%d) with one interval per sample" % (
+            tuple(prev_depth.shape), tuple(depth_interval.shape), H, W))
+    B = prev_depth.shape[0]
+    hyp = torch.empty(B, ndepths, H, W, device=prev_depth.device, dtype=torch.float32)
+    _call("mvs_schedule_range", None, _ptr(prev_depth), _ptr(depth_interval), float(ratio), B, ndepths, H, W, _ptr(hyp), _stream())
+    return hyp
+
+
+def _head_train_args(pre_or_prob: torch.Tensor, depth_values: torch.Tensor, what: str):
+    _chk(pre_or_prob, what), _chk(depth_values, "depth_values")
+    if pre_or_prob.dim() != 4 or pre_or_prob.shape != depth_values.shape:
+        raise _lib.MvsHipError("%s %s / depth_values %s must both be [B,D,H,W]" % (what, tuple(pre_or_prob.shape), tuple(depth_values.shape)))
+    return pre_or_prob.shape
+
+
+def _head_train_grads(prob: torch.Tensor, dprob: Optional[torch.Tensor], ddepth: Optional[torch.Tensor]):
+    _opt(dprob, "dprob"), _opt(ddepth, "ddepth")
+    B, D, H, W = prob.shape
+    if (dprob is not None and dprob.shape != prob.shape) or (ddepth is not None and tuple(ddepth.shape) != (B, H, W)):
+        raise _lib.MvsHipError("head backward: dprob / ddepth do not match prob_volume %s" % (tuple(prob.shape),))
+
+
+def reg_head_fwd(pre: torch.Tensor, depth_values: torch.Tensor, want_conf: bool = True):
+    """Regression training head (reference mvsformer_model.py:111,138) -> (prob_volume, depth, max-probability confidence or None)."""
+    B, D, H, W = _head_train_args(pre, depth_values, "prob_volume_pre")
+    prob = torch.empty_like(pre)
+    depth = torch.empty(B, H, W, device=pre.device, dtype=torch.float32)
+    conf = torch.empty(B, H, W, device=pre.device, dtype=torch.float32) if want_conf else None
+    _call("mvs_reg_head_fwd", None, _ptr(pre), _ptr(depth_values), B, D, H, W, _ptr(prob), _ptr(depth), _ptr(conf), _stream())
+    return prob, depth, conf
+
+
+def reg_head_bwd(prob: torch.Tensor, depth_values: torch.Tensor, dprob: Optional[torch.Tensor], ddepth: Optional[torch.Tensor]) -> torch.Tensor:
+    """d(loss)/d(prob_volume_pre) of :func:`reg_head_fwd` from d/d(prob_volume) and d/d(depth) (either may be None)."""
+    B, D, H, W = _head_train_args(prob, depth_values, "prob_volume")
+    _head_train_grads(prob, dprob, ddepth)
+    dpre = torch.empty_like(prob)
+    _call("mvs_reg_head_bwd", None, _ptr(prob), _ptr(depth_values), _ptr(dprob), _ptr(ddepth), B, D, H, W, _ptr(dpre), _stream())
+    return dpre
+
+
+def mixup_train_fwd(pre: torch.Tensor, depth_values: torch.Tensor):
+    """'mixup_ce' training head (reference mvsformer_model.py:111,126-136) -> (prob_volume, depth, confidence, winning pair index int32 [B,H,W])."""
+    B, D, H, W = _head_train_args(pre, depth_values, "prob_volume_pre")
+    prob = torch.empty_like(pre)
+    depth = torch.empty(B, H, W, device=pre.device, dtype=torch.float32)
+    conf = torch.empty(B, H, W, device=pre.device, dtype=torch.float32)
+    pair = torch.empty(B, H, W, device=pre.device, dtype=torch.int32)
+    _call("mvs_mixup_train_fwd", None, _ptr(pre), _ptr(depth_values), B, D, H, W, _ptr(prob), _ptr(depth), _ptr(conf), _ptr(pair), _stream())
+    return prob, depth, conf, pair
+
+
+def mixup_train_bwd(prob: torch.Tensor, depth_values: torch.Tensor, pair: torch.Tensor, dprob: Optional[torch.Tensor],
+                    ddepth: Optional[torch.Tensor]) -> torch.Tensor:
+    """d(loss)/d(prob_volume_pre) of :func:`mixup_train_fwd`; ``pair`` is the index it saved."""
+    B, D, H, W = _head_train_args(prob, depth_values, "prob_volume")
+    _head_train_grads(prob, dprob, ddepth)
+    _chk(pair, "pair", torch.int32)
+    if tuple(pair.shape) != (B, H, W):
+        raise _lib.MvsHipError("mixup_train_bwd: pair %s is not [B,H,W] of prob_volume %s" % (tuple(pair.shape), tuple(prob.shape)))
+    dpre = torch.empty_like(prob)
+    _call("mvs_mixup_train_bwd", None, _ptr(prob), _ptr(depth_values), _ptr(pair), _ptr(dprob), _ptr(ddepth), B, D, H, W, _ptr(dpre), _stream())
+    return dpre
+
+
 def conf_accumulate(conf: torch.Tensor, acc: torch.Tensor, weight: float = 1.0) -> None:
     _chk(conf, "photometric_confidence"), _chk(acc, "prob_maps")
     B, H, W = conf.shape

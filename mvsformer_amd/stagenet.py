@@ -15,6 +15,10 @@ correlation in sweep B (``mvs_cv_entropy_fwd`` / ``mvs_cv_aggregate_fwd``) becau
 Infinity Cache.  ``MVS_CV_TILED=1`` opts into the LDS-tiled sweeps of cost_volume_tiled.hip (they lose on the noisy
 hypotheses a random-weight cascade predicts).
 
+Training mode runs the same steps under :mod:`mvsformer_amd.autograd`; every ``depth_type``'s head is a HIP kernel there too (``HeadFn``
+for 'ce' / 'was', ``MixupHeadFn`` for 'mixup_ce', ``RegHeadFn`` for the regression head - csrc/head_train.hip).  The hypotheses a stage is
+given may ascend (linear depth) or descend (inverse depth) with d: nothing here depends on their order.
+
 ``DepthNet`` is the name BASELINE.json uses for the same thing.
 """
 from __future__ import annotations
@@ -267,20 +271,10 @@ class StageNet(nn.Module):
         depth_type = self.args["depth_type"]
         if depth_type in ("ce", "was"):
             prob, depth, conf = ag.HeadFn.apply(pre, hyp, float(tmp))
-        else:
-            # The mixup / regression heads are a few elementwise ops on [B,D,H,W]; in training they run as torch ops on the HIP
-            # regularizer's logits so that depth and prob_volume are differentiable (mvsformer_model.py:126-146).
-            prob = torch.softmax(pre, dim=1)
-            if depth_type == "mixup_ce":
-                left, right = prob[:, :-1], prob[:, 1:]
-                conf, idx = torch.max(left + right, dim=1)
-                norm = left + right + 1e-7
-                mix = hyp[:, :-1] * (left / norm) + hyp[:, 1:] * (right / norm)
-                depth = torch.gather(mix, 1, idx.unsqueeze(1)).squeeze(1)
-            else:
-                depth = torch.sum(prob * hyp, dim=1)
-                n = self._conf_window()
-                conf = ops.conf_regression(prob.detach().contiguous(), n) if n else prob.max(1)[0]
+        elif depth_type == "mixup_ce":                          # mvsformer_model.py:126-136, differentiable in prob_volume and depth
+            prob, depth, conf = ag.MixupHeadFn.apply(pre, hyp)
+        else:                                                   # regression head, mvsformer_model.py:137-146 (tmp unused)
+            prob, depth, conf = ag.RegHeadFn.apply(pre, hyp, self._conf_window())
         return {"depth": depth, "prob_volume": prob, "photometric_confidence": conf.detach(), "depth_values": depth_values,
                 "prob_volume_pre": pre}
 

@@ -69,13 +69,15 @@ def main():
     args = json.load(open(a.config))["arch"]["args"] if a.config else dict(DEFAULT_ARGS, vit_args=dict(DEFAULT_ARGS["vit_args"]))
     sd = torch.load(a.checkpoint, map_location="cpu")
     if not a.config:
-        # the reference's trainer stores its config in the checkpoint: the two flags that change the model's modules come from there
+        # the reference's trainer stores its config in the checkpoint: the flags that change the model's modules and its hypothesis
+        # sampling come from there (absent ones as the reference's own constructor reads them, mvsformer_model.py:169-170)
         try:
             ck = sd["config"]["arch"]["args"]
         except (KeyError, TypeError, IndexError):
             ck = None
         if ck is not None:
             args["multi_scale"] = bool(ck.get("multi_scale", False))
+            args["inverse_depth"] = bool(ck.get("inverse_depth", False))
             for k in ("att_fusion", "multi_scale_decoder"):
                 if k in ck.get("vit_args", {}):
                     args["vit_args"][k] = ck["vit_args"][k]
