@@ -46,7 +46,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 48
+#define MVS_ABI_VERSION 49
 
 typedef void* mvs_stream_t;
 
@@ -773,6 +773,31 @@ int mvs_was_loss_fwd(const float* prob_volume, const float* depth_values, const 
                      int ot_iter, float ot_eps, float weight, float* grad_unscaled, float* acc, float* loss, mvs_stream_t stream);
 int mvs_ce_loss_bwd_scale(const float* grad_unscaled, float* grad, int64_t numel, const float* acc, const float* grad_out, float weight,
                           mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Depth metrics of a batch (csrc/metrics.hip): Thres_metrics / AbsDepthError_metrics of the reference's utils.py:148-182 for every image,
+ * every threshold and the batch in one pass over the three maps, and the DictAverageMeter update (utils.py:119-145) behind it; no host
+ * synchronisation, no float atomics, bit-reproducible.
+ *   depth_est, depth_gt [B][HW] fp32; mask [B][HW] fp32 (valid where > 0.5) or, mask_is_byte != 0, one byte per pixel (valid where != 0).
+ *   The three maps are dense but need no alignment beyond their element's: the kernel reads 16 bytes per lane where all three allow it.
+ *   thresholds [B][K] fp32 (0 <= K <= 8; may be NULL when K = 0).  use_band != 0: the abs error is taken over band_lo <= e <= band_hi only.
+ *   A value at an invalid pixel is never used (selected, not multiplied); e = |est - gt| is formed in fp32.
+ * acc: mvs_depth_metrics_acc_floats(B, HW) floats of scratch, 8-byte aligned (one row per block of MVS_DEPTH_METRICS_BLOCK_PIXELS pixels).
+ * counts [B][2+K] int32: valid pixels n, valid pixels inside the band (n itself without a band), then per threshold the valid pixels
+ *        with e > threshold (strict, fp32; a NaN error is neither above a threshold nor inside a band).
+ * per_image [B][1+K] fp32: mean of e over the valid (band) pixels - the fp32 values added in double, divided once, rounded once; 0 for an empty
+ *        band (or an empty mask with a band), NaN for an empty mask without one - then the K ratios count / n (NaN when n = 0).
+ * batch [1+K] fp32: the means of per_image over the B images (added in double in image order).
+ * meter_sums (may be NULL) [1+K] double += batch, meter_count (may be NULL) [1] double += meter_n, at the end of the same stream-ordered work.
+ * HW <= 2^31 - 1, B <= 65535.
+ * ------------------------------------------------------------------------------------------------------- */
+#define MVS_DEPTH_METRICS_BLOCK_PIXELS 1024
+#define MVS_DEPTH_METRICS_MAX_K 8
+int mvs_depth_metrics_block_pixels(void);
+int64_t mvs_depth_metrics_acc_floats(int B, int64_t HW);
+int mvs_depth_metrics(const float* depth_est, const float* depth_gt, const void* mask, int mask_is_byte, const float* thresholds, int B, int K,
+                      int64_t HW, int use_band, float band_lo, float band_hi, float* acc, int32_t* counts, float* per_image, float* batch,
+                      double* meter_sums, double* meter_count, double meter_n, mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * the DINO ViT-small feature branch of MVSFormer-P (csrc/vit.hip; models/vision_transformer.py:104-154,194-214,324-451,

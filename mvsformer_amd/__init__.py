@@ -2,7 +2,8 @@
 
 Hand-written HIP kernels behind a C ABI (``include/mvs_hip.h`` -> ``libmvs_hip.so``) re-exposed with the
 reference's own Python interface: ``StageNet`` (alias ``DepthNet``), ``CostRegNet``, ``CostRegNet3D``,
-``homo_warping_3D_with_mask`` (alias ``homo_warping``), ``depth_regression``, the inverse- and linear-depth schedulers, and
+``homo_warping_3D_with_mask`` (alias ``homo_warping``), ``depth_regression``, the inverse- and linear-depth schedulers, the depth metrics of ``utils.py``
+(``Thres_metrics``, ``AbsDepthError_metrics``, ``metrics.DeviceAverageMeter``, ``metrics.valid_epoch``), and
 ``install()`` to rebind them inside an unmodified reference checkout.  ``synth`` (pure torch) builds the
 synthetic DTU-shaped inputs used by the tests and ``bench.py``.
 
@@ -13,7 +14,8 @@ from . import synth  # noqa: F401
 __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "CascadeMVS", "homo_warping_3D_with_mask",
            "homo_warping_3D", "homo_warping", "depth_regression", "conf_regression", "init_inverse_range",
            "schedule_inverse_range", "init_range", "schedule_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
-           "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference"]
+           "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference",
+           "metrics", "Thres_metrics", "AbsDepthError_metrics", "depth_metrics", "DeviceAverageMeter", "valid_epoch"]
 
 
 def __getattr__(name):
@@ -51,6 +53,12 @@ def __getattr__(name):
     if name == "SceneInference":
         from . import scene
         return scene.SceneInference
+    if name == "metrics":
+        import importlib
+        return importlib.import_module(".metrics", __name__)
+    if name in ("Thres_metrics", "AbsDepthError_metrics", "depth_metrics", "DeviceAverageMeter", "valid_epoch"):
+        from . import metrics
+        return getattr(metrics, name)
     if name == "install":
         from .install import install
         return install

@@ -20,7 +20,7 @@ from . import switches as sw
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = sw.text("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 from ctypes import c_double  # noqa: E402
 
@@ -160,6 +160,9 @@ SIGNATURES = {
     "mvs_was_loss_fwd": (I, [P, P, P, P, I, I, L, I, F, F, P, P, P, P]),
     "mvs_ce_loss_bwd_scale": (I, [P, P, L, P, P, F, P]),
     "mvs_ce_loss_acc_floats": (L, [I, L]),
+    "mvs_depth_metrics_block_pixels": (I, []),
+    "mvs_depth_metrics_acc_floats": (L, [I, L]),
+    "mvs_depth_metrics": (I, [P, P, P, I, P, I, I, L, I, F, F, P, P, P, P, P, P, Dbl, P]),
     "mvs_bf16_embed_ch0": (I, [P, P, L, P]),
     "mvs_gemm_x3": (I, [P, P, P, I, I, I, I, I, I, I, I, L, L, L, L, L, L, I, I, I, I, I, F, P, P, I, P, P, P]),
     "mvs_attention_x3": (I, [P, P, P, I, I, I, I, I, F, P]),

@@ -38,12 +38,24 @@ _FEATURE_SYMBOLS = {"FPNDecoder": _f.FPNDecoder, "FPNDecoderV2": _f.FPNDecoderV2
 _VIT_MODULE, _VIT_FACTORIES = "models.vision_transformer", {"vit_small": _v.vit_small}
 
 
-def install(model_module: str = "models.mvsformer_model", also=("models.module", "models.warping"), features: bool = False) -> dict:
+# utils.py:119-182, rebound on request (install(metrics=True)): the metrics run as one HIP call each, the meter keeps its sums on the device
+_METRICS_MODULE = "utils"
+
+
+def _metric_symbols() -> dict:
+    from . import metrics as _mt
+    return {"Thres_metrics": _mt.Thres_metrics, "AbsDepthError_metrics": _mt.AbsDepthError_metrics, "DictAverageMeter": _mt.DeviceAverageMeter}
+
+
+def install(model_module: str = "models.mvsformer_model", also=("models.module", "models.warping"), features: bool = False,
+            metrics: bool = False) -> dict:
     """Rebind the hot-path names inside the reference's modules.  Returns ``{module: [names rebound]}``.
     ``features=True`` also rebinds ``FPNEncoder`` / ``FPNDecoder`` / ``FPNDecoderV2``, the three ViT decoders (``VITDecoderStage4Single`` /
     ``VITDecoderStage4`` / ``VITDecoderStage4NoAtt``), the ``vit_small`` factory of ``models.vision_transformer`` (the DINO branch of MVSFormer-P)
     and ``DINOMVSNet`` itself, which takes ``multi_scale`` and ``att_fusion`` as the reference's class does.  The FPN and the ViT decoder run in eval AND
-    training mode; the ViT is eval-only (MVSFormer-P freezes it, ``"fix": true``; a model that fine-tunes the ViT must keep the reference's)."""
+    training mode; the ViT is eval-only (MVSFormer-P freezes it, ``"fix": true``; a model that fine-tunes the ViT must keep the reference's).
+    ``metrics=True`` also rebinds ``Thres_metrics``, ``AbsDepthError_metrics`` and ``DictAverageMeter`` in the reference's ``utils`` module
+    (``mvsformer_amd.metrics``; a module that did ``from utils import *`` before the call keeps the names it already bound)."""
     done = {}
     symbols = dict(_SYMBOLS, **(_FEATURE_SYMBOLS if features else {}))
     for name in (model_module,) + tuple(also):
@@ -61,6 +73,17 @@ def install(model_module: str = "models.mvsformer_model", also=("models.module",
                 setattr(mod, sym, getattr(_w, sym))
                 hit.append(sym)
         done[name] = hit
+    if metrics:                                              # off by default: nothing of `utils` is touched without it
+        try:
+            umod = importlib.import_module(_METRICS_MODULE)
+            hit = []
+            for sym, obj in _metric_symbols().items():
+                if hasattr(umod, sym):
+                    setattr(umod, sym, obj)
+                    hit.append(sym)
+            done[_METRICS_MODULE] = hit
+        except ImportError:
+            pass
     if features:
         try:                                                 # the whole model too: its forward uses the CLS-row attention path (forward_with_cls_att)
             from .mvsformer_model import DINOMVSNet

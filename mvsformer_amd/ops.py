@@ -1438,6 +1438,52 @@ def ce_loss_bwd_scale(grad, acc, gout, weight: float) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------- depth metrics (utils.py:119-182)
+DEPTH_METRICS_BLOCK_PIXELS = 1024                            # MVS_DEPTH_METRICS_BLOCK_PIXELS: pixels one block of the first launch covers
+DEPTH_METRICS_MAX_K = 8                                      # MVS_DEPTH_METRICS_MAX_K
+
+
+def depth_metrics(depth_est, depth_gt, mask, thresholds=None, band=None, meter_sums=None, meter_count=None, meter_n: float = 1.0):
+    """``depth_est``, ``depth_gt`` ``[B,H,W]`` fp32, ``mask`` ``[B,H,W]`` fp32 (valid where > 0.5) or bool / uint8 (valid where non-zero),
+    ``thresholds`` ``[B,K]`` fp32 or None, ``band`` ``(lo, hi)`` or None -> ``(counts [B,2+K] int32, per_image [B,1+K], batch [1+K])``:
+    valid / in-band / above-threshold pixel counts, the mean abs error and the K ratios per image, and their batch means.  ``meter_sums``
+    ``[1+K]`` / ``meter_count`` ``[1]`` (fp64, updated in place after the batch means, on the same stream).  No host synchronisation."""
+    _chk(depth_est, "depth_est"), _chk(depth_gt, "depth_gt")
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.float32, torch.bool, torch.uint8):
+        raise _lib.MvsHipError("mask must be a float32, bool or uint8 tensor, got %s" % getattr(mask, "dtype", type(mask)))
+    byte = mask.dtype != torch.float32
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)                        # same bytes: True is stored as 1
+    _chk(mask, "mask", mask.dtype)
+    if depth_est.dim() != 3 or depth_gt.shape != depth_est.shape or mask.shape != depth_est.shape:
+        raise _lib.MvsHipError("depth_metrics: shapes %s %s %s" % (tuple(depth_est.shape), tuple(depth_gt.shape), tuple(mask.shape)))
+    B, H, W = depth_est.shape
+    K = 0
+    if thresholds is not None:
+        _chk(thresholds, "thresholds")
+        if thresholds.dim() != 2 or thresholds.shape[0] != B:
+            raise _lib.MvsHipError("depth_metrics: thresholds must be [B,K] = [%d,K], got %s" % (B, tuple(thresholds.shape)))
+        K = thresholds.shape[1]
+    if meter_sums is not None:
+        _chk(meter_sums, "meter_sums", torch.float64), _chk(meter_count, "meter_count", torch.float64)
+        if meter_sums.numel() != 1 + K or meter_count.numel() != 1:
+            raise _lib.MvsHipError("depth_metrics: the meter holds %d sums, the call produces %d" % (meter_sums.numel(), 1 + K))
+    dev = depth_est.device
+    nacc = _lib.load().mvs_depth_metrics_acc_floats(B, H * W)
+    if nacc < 0:
+        raise _lib.MvsHipError("depth_metrics: bad shape %s" % (tuple(depth_est.shape),))
+    acc = torch.empty(nacc, device=dev, dtype=torch.float32)
+    counts = torch.empty(B, 2 + K, device=dev, dtype=torch.int32)
+    per_image = torch.empty(B, 1 + K, device=dev, dtype=torch.float32)
+    batch = torch.empty(1 + K, device=dev, dtype=torch.float32)
+    lo, hi = (float(band[0]), float(band[1])) if band is not None else (0.0, 0.0)
+    algo = float(B * H * W) * (8 + (1 if byte else 4))
+    _call("mvs_depth_metrics", ("depth_metrics", "bytes", algo), _ptr(depth_est), _ptr(depth_gt), _ptr(mask), int(byte), _ptr(thresholds if K else None),
+          B, K, H * W, int(band is not None), lo, hi, _ptr(acc), _ptr(counts), _ptr(per_image), _ptr(batch), _ptr(meter_sums), _ptr(meter_count),
+          float(meter_n), _stream())
+    return counts, per_image, batch
+
+
 def bf16_embed_ch0(x: torch.Tensor) -> torch.Tensor:
     """fp32 ``[...]`` -> bf16 ``[..., 8]`` with the value in channel 0, zeros elsewhere (one launch instead of a fill and a strided copy)."""
     _chk(x, "x")

@@ -137,6 +137,7 @@ class SceneInference:
         self.stats: Dict[str, object] = {}
         self.timing = False                                  # True: run() brackets extraction and cascade with HIP events (timings())
         self._events: Dict[str, list] = {"extract": [], "cascade": []}
+        self.depth_meter = None                              # run(gt=...): the metrics.DeviceAverageMeter of the last run
 
     # ------------------------------------------------------------------------------------------------ inputs
     def _gpu(self, t, name: str) -> torch.Tensor:
@@ -226,11 +227,16 @@ class SceneInference:
             self.stats["extract_passes"] += 1
 
     # ------------------------------------------------------------------------------------------------ run
-    def run(self, tmp=2.0, fusion=None, save_to: Optional[str] = None) -> Dict[int, Dict[str, torch.Tensor]]:
+    def run(self, tmp=2.0, fusion=None, save_to: Optional[str] = None, gt=None, meter=None) -> Dict[int, Dict[str, torch.Tensor]]:
         """Depth and confidence of every reference view of the pairs, in their order.  -> ``{ref_id: {"depth": [H,W], "confidence":
         [4,H,W] (or [H,W] with combine_conf), "cam": [2,4,4]}}`` as device tensors.  ``fusion``: a ``fusion.SceneFusion`` that gets every
         finished view (with its de-normalised uint8 image) and the pairs - ``fusion.fuse()`` is then images -> point cloud with no file in
-        between.  ``save_to``: a scan folder that gets the files the reference writes (``data_io.save_depth_outputs``, ``save_image``)."""
+        between.  ``save_to``: a scan folder that gets the files the reference writes (``data_io.save_depth_outputs``, ``save_image``).
+        ``gt``: ground truth per reference view, ``{ref_id: (depth [H,W], mask [H,W])}`` device tensors at output resolution (a mapping or a
+        callable ``ref_id -> (depth, mask)``; mask fp32 valid where > 0.5, or bool).  Every view's depth map then goes into a
+        ``metrics.DeviceAverageMeter`` (``meter``, or a fresh one) with test.py:310-320's seven entries - ``abs_depth_error`` and
+        ``thres{1,2,4,8,14,20}mm_error`` at multiples of ``depth_interval / 2.65`` - by one launch sequence per view and no host
+        synchronisation; the meter is ``self.depth_meter`` afterwards (``.mean()`` -> ``metrics.write_depth_metric_txt``)."""
         if not self.pairs or not self.images:
             raise ValueError("SceneInference.run: add_image() and set_pairs() first")
         if self.model.training:
@@ -266,6 +272,11 @@ class SceneInference:
             confs = torch.empty((nrefs, h, w) if self.combine_conf else (nrefs, 4, h, w), device=self.device, dtype=torch.float32)
             out: Dict[int, Dict[str, torch.Tensor]] = {}
             self._events = {"extract": [], "cascade": []}
+            self.depth_meter = None
+            if gt is not None:
+                from . import metrics as _metrics
+                names = [_metrics.ABS_KEY] + _metrics.threshold_names(_metrics.TEST_MULTIPLIERS)
+                self.depth_meter = meter if meter is not None else _metrics.DeviceAverageMeter(names, self.device)
             for i, st in enumerate(steps):
                 if st["extract"]:
                     done = self._mark("extract")
@@ -281,6 +292,13 @@ class SceneInference:
                 else:
                     ops.conf_stack([o["stage%d" % (k + 1)]["photometric_confidence"] for k in range(nstage)], confs[i])
                 done()
+                if gt is not None:
+                    gt_depth, gt_mask = gt(st["ref"]) if callable(gt) else gt[st["ref"]]
+                    if tuple(gt_depth.shape) != (h, w) or tuple(gt_mask.shape) != (h, w):
+                        raise MvsHipError("view %d: ground truth is %s / %s, the depth map %dx%d (resize it beforehand)"
+                                          % (st["ref"], tuple(gt_depth.shape), tuple(gt_mask.shape), h, w))
+                    _metrics.depth_metrics(depths[i:i + 1], gt_depth.unsqueeze(0), gt_mask.unsqueeze(0), depth_interval=dv[:, 1] - dv[:, 0],
+                                           multipliers=_metrics.TEST_MULTIPLIERS, meter=self.depth_meter)
                 out[st["ref"]] = {"depth": depths[i], "confidence": confs[i], "cam": self.cams[st["ref"]]}
             if fusion is not None or save_to is not None:
                 imgs8 = {v: self.image_uint8(v) for v in distinct}

@@ -3,12 +3,15 @@
 
     python tools/infer_scan.py --scan SCAN_FOLDER --checkpoint model_best.pth [--config config.json] [--num_view 5] [--numdepth 192]
         [--interval_scale 1.06] [--tmp 5,5,5,1] [--out OUT_FOLDER] [--ply cloud.ply] [--prob_threshold 0.5,0.5,0.5,0.5] [--method pcd]
+        [--gt_depth DIR --gt_mask DIR]
 
 ``SCAN_FOLDER`` holds ``images/%08d.jpg|png``, ``cams/%08d_cam.txt`` and ``pair.txt`` (the layout ``general_eval.py`` reads).  ``--out`` gets
 the files the reference's ``save_depth`` writes (``depth_est/``, ``confidence/``, ``cams/``, ``images/``: ``tools/fuse_scan.py`` and the
 reference's own filter step consume them); ``--ply`` fuses the scan on the device with no file in between.  Images are used as they are:
 their size must be a multiple of 64 (resize / crop beforehand - datasets are out of scope here), and the intrinsics in the camera files
-must belong to that size.  Needs the GPU.
+must belong to that size.  ``--gt_depth`` / ``--gt_mask`` (with ``--out``): ground truth per reference view, ``DIR/%08d.pfm`` and
+``DIR/%08d.png`` (or DTU's ``depth_map_%04d.pfm`` / ``depth_visual_%04d.png``; a mask pixel is valid above 10, as the reference's loader
+reads it), already at the images' size - ``OUT_FOLDER/depth_metric.txt`` then holds test.py's seven accuracy entries.  Needs the GPU.
 """
 import argparse
 import json
@@ -21,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mvsformer_amd as m  # noqa: E402
-from mvsformer_amd import data_io  # noqa: E402
+from mvsformer_amd import data_io, metrics  # noqa: E402
 from mvsformer_amd.scene import IMAGENET_MEAN, IMAGENET_STD  # noqa: E402
 
 DEFAULT_ARGS = dict(fix=True, depth_type="ce", fusion_type="cnn", inverse_depth=True, attn_temp=2.0, base_ch=8, ndepths=[32, 16, 8, 4], feat_chs=[8, 16, 32, 64],
@@ -43,6 +46,19 @@ def depth_values(cam_file, numdepth, interval_scale):
     return np.arange(depth_min, interval * (numdepth - 0.5) + depth_min, interval, dtype=np.float32)
 
 
+def load_gt(depth_dir, mask_dir, vid, dev):
+    """-> ``(depth [H,W] fp32, mask [H,W] bool)`` of view ``vid`` on ``dev``."""
+    def first(folder, patterns):
+        for pat in patterns:
+            path = os.path.join(folder, pat.format(vid))
+            if os.path.exists(path):
+                return path
+        raise SystemExit("no ground truth for view %d in %s (%s)" % (vid, folder, " or ".join(p.format(vid) for p in patterns)))
+    depth, _ = data_io.read_pfm(first(depth_dir, ("{:0>8}.pfm", "depth_map_{:0>4}.pfm")))
+    mask = data_io.read_img(first(mask_dir, ("{:0>8}.png", "depth_visual_{:0>4}.png")))[..., 0] > 10
+    return torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(dev), torch.from_numpy(np.ascontiguousarray(mask)).to(dev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scan", required=True)
@@ -60,9 +76,13 @@ def main():
     ap.add_argument("--capacity_views", type=int, default=None)
     ap.add_argument("--max_bank_mb", type=float, default=16384.0)
     ap.add_argument("--extract_batch", type=int, default=4)
+    ap.add_argument("--gt_depth", default=None, help="folder of ground-truth depth maps (PFM) at the images' size; with --gt_mask and --out: depth_metric.txt")
+    ap.add_argument("--gt_mask", default=None, help="folder of validity masks (PNG, valid above 10)")
     a = ap.parse_args()
     if not a.out and not a.ply:
         raise SystemExit("nothing to do: give --out and / or --ply")
+    if bool(a.gt_depth) != bool(a.gt_mask) or (a.gt_depth and not a.out):
+        raise SystemExit("--gt_depth and --gt_mask go together and need --out (depth_metric.txt is written there)")
     if not torch.cuda.is_available():
         raise SystemExit("infer_scan.py runs the MI355X path: no GPU")
     dev = torch.device("cuda:0")
@@ -108,11 +128,17 @@ def main():
     si.set_pairs(pairs, num_views=a.num_view)
     th = [float(x) for x in a.prob_threshold.split(",")]
     fusion = m.SceneFusion(a.method, th, combine_conf=a.combine_conf, device="cuda:0") if a.ply else None
+    gt = {r: load_gt(a.gt_depth, a.gt_mask, r, dev) for r, _ in pairs} if a.gt_depth else None
     t1 = time.perf_counter()
-    si.run(tmp=[float(x) for x in a.tmp.split(",")], fusion=fusion, save_to=a.out)
+    si.run(tmp=[float(x) for x in a.tmp.split(",")], fusion=fusion, save_to=a.out, gt=gt)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     res = dict(views=len(ids), samples=len(pairs), seconds=dict(load=t1 - t0, infer=t2 - t1), bank=si.stats)
+    if gt is not None:
+        means = si.depth_meter.mean()                        # the scan's one device-to-host copy of the metrics
+        os.makedirs(a.out, exist_ok=True)
+        metrics.write_depth_metric_txt(os.path.join(a.out, "depth_metric.txt"), means)
+        res.update(depth_metrics=means)
     if fusion is not None:
         out = fusion.fuse(want=("records",))
         data_io.write_ply_records(a.ply, out["records"], out["n_points"])
