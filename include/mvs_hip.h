@@ -46,7 +46,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 49
+#define MVS_ABI_VERSION 50
 
 typedef void* mvs_stream_t;
 
@@ -798,6 +798,61 @@ int64_t mvs_depth_metrics_acc_floats(int B, int64_t HW);
 int mvs_depth_metrics(const float* depth_est, const float* depth_gt, const void* mask, int mask_is_byte, const float* thresholds, int B, int K,
                       int64_t HW, int use_band, float band_lo, float band_hi, float* acc, int32_t* counts, float* per_image, float* batch,
                       double* meter_sums, double* meter_count, double meter_n, mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Point-cloud evaluation (csrc/cloud_eval.hip): capped exact nearest-neighbour distances between two clouds over a uniform grid, voxel
+ * thinning, and the score reduction behind DTU's accuracy / completeness and Tanks-and-Temples' precision / recall / F-score.  Clouds are
+ * dense fp32 [N][3] in DEVICE memory; every size is 64-bit (1 <= N <= 2^36; an empty cloud needs no call).  No float atomics: two runs
+ * give the same bits.
+ *
+ * The grid of a cloud: cell coordinate = floorf((x - origin) / cell) per axis (two IEEE fp32 operations, in this order), origin = the
+ * per-axis minimum over the finite points, key = x | y << 21 | z << 42 (x fastest).  `grid` is a device record of
+ * MVS_CLOUD_GRID_RECORD_BYTES bytes, 8-byte aligned, written by the first two calls and read by the others.
+ *   mvs_cloud_bounds      min / max per axis over the finite points into the record AND, after waiting for the stream, into
+ *                         bounds_host[6] (min xyz, max xyz; zeros when no point is finite) and *n_nonfinite_host.
+ *   mvs_cloud_grid_keys   keys [N] int64 for `cell` and those bounds (as mvs_cloud_bounds returned them); a non-finite point gets the largest
+ *                         key, so it sorts behind every cell and is not indexed.  MVS_EINVAL, before any launch, when cell <= 0 or is not
+ *                         finite, or when an axis spans MVS_CLOUD_MAX_AXIS_CELLS (2^21) cells or more.
+ *   ... the caller sorts the keys with a STABLE sort and keeps the permutation perm [N] (sorted position -> original index) ...
+ *   mvs_cloud_grid_build  from the sorted keys: the table of occupied cells cell_keys [N], cell_start [N + 1] (entries [0, cells) are used,
+ *                         cell_start[cells] = number of indexed points; the number of cells stays in the record), and sorted_pts [N][3]
+ *                         (may be NULL) = the points in cell order.  workspace: mvs_cloud_grid_workspace_bytes(N), 8-byte aligned.
+ *   mvs_cloud_query_keys  keys [M] that ORDER queries by their (clamped) cell in an existing grid; sort them and pass the permutation as
+ *                         query_perm, so that neighbouring lanes walk the same cells (NULL: caller's order).
+ *   mvs_cloud_nn_query    dist [M] fp32, idx [M] int64 in the caller's order: the Euclidean distance ((dx*dx + dy*dy) + dz*dz in fp32,
+ *                         then sqrtf) to the nearest indexed point and its ORIGINAL index if that distance is < max_dist, else max_dist
+ *                         and -1.  Exact: the minimum a brute-force scan of the same fp32 arithmetic finds; equidistant targets resolve
+ *                         to the lowest original index.  `cell` repeats the grid's; max_dist / cell <= MVS_CLOUD_MAX_SHELLS.
+ *   mvs_cloud_voxel_downsample_count / _write   thinning = a grid with cell = voxel: _count waits for the stream and returns the number
+ *                         of occupied voxels in *count_host; _write: out [count][3] = per voxel, in ascending key order, the mean of
+ *                         attr [N][3] (the points themselves, or colours) over the voxel's points, added in double in original order.
+ *   mvs_cloud_score       over dist [M] (M >= 0): record (MVS_CLOUD_SCORE_RECORD_BYTES, 8-byte aligned, device) = int64 n = M, int64
+ *                         number of distances < max_dist, int64[8] number < taus_host[k] (HOST array, K <= MVS_CLOUD_SCORE_MAX_K, each
+ *                         <= max_dist or MVS_EINVAL), double sum of the distances < max_dist, double mean = sum / count (NaN for an
+ *                         empty set), 32 bytes reserved.  Counts: 64-bit integer atomics; sum: per-block doubles added in a fixed order
+ *                         by a second launch.  workspace: mvs_cloud_score_workspace_bytes(M), 8-byte aligned.
+ * ------------------------------------------------------------------------------------------------------- */
+#define MVS_CLOUD_GRID_RECORD_BYTES 128
+#define MVS_CLOUD_SCORE_RECORD_BYTES 128
+#define MVS_CLOUD_MAX_AXIS_CELLS 2097152
+#define MVS_CLOUD_MAX_SHELLS 32
+#define MVS_CLOUD_SCORE_MAX_K 8
+int mvs_cloud_bounds(const float* pts, int64_t N, void* grid, float* bounds_host, int64_t* n_nonfinite_host, mvs_stream_t stream);
+int mvs_cloud_grid_keys(const float* pts, int64_t N, float cell, const float* bounds_host, int64_t n_nonfinite, void* grid, int64_t* keys,
+                        mvs_stream_t stream);
+int64_t mvs_cloud_grid_workspace_bytes(int64_t N);
+int mvs_cloud_grid_build(const float* pts, int64_t N, const int64_t* sorted_keys, const int64_t* perm, void* grid, void* workspace,
+                         float* sorted_pts, int64_t* cell_keys, int64_t* cell_start, mvs_stream_t stream);
+int mvs_cloud_query_keys(const float* queries, int64_t M, const void* grid, int64_t* keys, mvs_stream_t stream);
+int mvs_cloud_nn_query(const float* queries, int64_t M, const int64_t* query_perm, const void* grid, float cell, const float* sorted_pts,
+                       const int64_t* perm, const int64_t* cell_keys, const int64_t* cell_start, int64_t N, float max_dist, float* dist,
+                       int64_t* idx, mvs_stream_t stream);
+int mvs_cloud_voxel_downsample_count(const void* grid, int64_t* count_host, mvs_stream_t stream);
+int mvs_cloud_voxel_downsample_write(const float* attr, int64_t N, const int64_t* perm, const void* grid, const int64_t* cell_start,
+                                     int64_t count, float* out, mvs_stream_t stream);
+int64_t mvs_cloud_score_workspace_bytes(int64_t M);
+int mvs_cloud_score(const float* dist, int64_t M, float max_dist, const float* taus_host, int K, void* workspace, void* record,
+                    mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * the DINO ViT-small feature branch of MVSFormer-P (csrc/vit.hip; models/vision_transformer.py:104-154,194-214,324-451,

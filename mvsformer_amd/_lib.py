@@ -20,7 +20,7 @@ from . import switches as sw
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = sw.text("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 49
+ABI_VERSION = 50
 
 from ctypes import c_double  # noqa: E402
 
@@ -163,6 +163,16 @@ SIGNATURES = {
     "mvs_depth_metrics_block_pixels": (I, []),
     "mvs_depth_metrics_acc_floats": (L, [I, L]),
     "mvs_depth_metrics": (I, [P, P, P, I, P, I, I, L, I, F, F, P, P, P, P, P, P, Dbl, P]),
+    "mvs_cloud_bounds": (I, [P, L, P, P, P, P]),
+    "mvs_cloud_grid_keys": (I, [P, L, F, P, L, P, P, P]),
+    "mvs_cloud_grid_workspace_bytes": (L, [L]),
+    "mvs_cloud_grid_build": (I, [P, L, P, P, P, P, P, P, P, P]),
+    "mvs_cloud_query_keys": (I, [P, L, P, P, P]),
+    "mvs_cloud_nn_query": (I, [P, L, P, P, F, P, P, P, P, L, F, P, P, P]),
+    "mvs_cloud_voxel_downsample_count": (I, [P, P, P]),
+    "mvs_cloud_voxel_downsample_write": (I, [P, L, P, P, P, L, P, P]),
+    "mvs_cloud_score_workspace_bytes": (L, [L]),
+    "mvs_cloud_score": (I, [P, L, F, P, I, P, P, P]),
     "mvs_bf16_embed_ch0": (I, [P, P, L, P]),
     "mvs_gemm_x3": (I, [P, P, P, I, I, I, I, I, I, I, I, L, L, L, L, L, L, I, I, I, I, I, F, P, P, I, P, P, P]),
     "mvs_attention_x3": (I, [P, P, P, I, I, I, I, I, F, P]),

@@ -1,0 +1,229 @@
+"""Point-cloud evaluation on the device: DTU's accuracy / completeness / overall and Tanks-and-Temples' precision / recall / F-score between
+a reconstructed cloud and a ground-truth cloud (csrc/cloud_eval.hip).  The reference leaves this step to the DTU MATLAB code and the T&T
+site; here the clouds stay where ``SceneFusion.fuse(on_device=True)`` left them.
+
+* :func:`nn_distance`: exact nearest-neighbour distances, capped at ``max_dist``, over a uniform grid of the target.
+* :func:`voxel_downsample`: one point per occupied voxel, the centroid of the voxel's points (the Open3D / T&T rule).  DTU's own 0.2 mm
+  thinning is a greedy pass over a random shuffle and is not reproduced: scores after thinning are comparable to the MATLAB numbers, not
+  equal to them; the distances themselves are exact.
+* :func:`evaluate`: both directions, the means and the shares under every threshold, read back in ONE 256-byte record at the end.
+* :func:`in_box`, :func:`in_volume`, :func:`above_plane`: DTU's bounding-box, observation-mask and above-plane filters as boolean masks
+  (elementwise torch code).
+
+Host reads: the scores are one record.  Before that each grid build reads its 32-byte bounds record (``mvs_cloud_grid_keys`` refuses a grid
+of 2^21 cells or more per axis on the host, and the default cell size is derived from the bounds), and a thinning reads its voxel count
+to size its output.  The key sort is ``torch.sort(stable=True)``; everything else is the HIP path, and a CPU tensor is refused.
+
+The default cell (``cell=None``): ``cbrt(V / N)`` with ``V`` the target's bounding-box volume over the axes that have an extent (the square
+or the length itself for a flat or a straight cloud) and ``N`` its finite points - about one point per cell of a filled box, a handful per
+occupied cell of a surface - then raised to ``max_dist / 16`` (at most 16 shells are walked before the cap ends the search) and to
+``extent / 2^20`` (the grid indexes fewer than 2^21 cells per axis).
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import MvsHipError
+
+MAX_DEFAULT_SHELLS = 16
+
+
+def _cloud(t, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise MvsHipError("%s must be a GPU tensor: the MI355X HIP path is the only implementation (no CPU fallback)" % name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise MvsHipError("%s must be [N,3], got %s" % (name, tuple(t.shape)))
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _positive(v, name: str) -> float:
+    v = float(v)
+    if not math.isfinite(v) or v <= 0.0:
+        raise MvsHipError("%s=%r must be positive and finite" % (name, v))
+    return v
+
+
+def default_cell(bounds: Sequence[float], n_finite: int, max_dist: float) -> float:
+    """The rule of the module docstring on the host: ``bounds`` = (min xyz, max xyz)."""
+    ext = [float(bounds[3 + a]) - float(bounds[a]) for a in range(3)]
+    pos = [e for e in ext if e > 0.0]
+    cell = (math.prod(pos) / max(1, n_finite)) ** (1.0 / len(pos)) if pos else max_dist
+    cell = max(cell, max_dist / MAX_DEFAULT_SHELLS, max(ext) / float(1 << 20))
+    return float(np.float32(cell) * np.float32(1.0 + 2.0 ** -20))          # rounded to fp32, never below the two floors
+
+
+class _Index:
+    """The grid of one target cloud: what ``mvs_cloud_grid_build`` left on the device."""
+
+    def __init__(self, pts: torch.Tensor, cell: Optional[float], max_dist: Optional[float], want_sorted: bool = True):
+        self.pts, self.n = pts, pts.shape[0]
+        self.grid, self.bounds, self.n_bad = ops.cloud_bounds(pts)
+        self.n_valid = self.n - self.n_bad
+        self.cell = default_cell(self.bounds, self.n_valid, max_dist) if cell is None else cell
+        keys = ops.cloud_grid_keys(pts, self.cell, self.grid, self.bounds, self.n_bad)
+        skeys, self.perm = torch.sort(keys, stable=True)                   # plumbing: the one step of the index that is not HIP
+        self.sorted_pts, self.cell_keys, self.cell_start = ops.cloud_grid_build(pts, skeys, self.perm, self.grid, want_sorted)
+
+    def query(self, src: torch.Tensor, max_dist: float):
+        qperm = torch.sort(ops.cloud_query_keys(src, self.grid), stable=True)[1]
+        return ops.cloud_nn_query(src, qperm, self.grid, self.cell, self.sorted_pts, self.perm, self.cell_keys, self.cell_start, max_dist)
+
+
+def _capped(m: int, max_dist: float, device):
+    return (torch.full((m,), max_dist, dtype=torch.float32, device=device), torch.full((m,), -1, dtype=torch.int64, device=device))
+
+
+def _nn(src: torch.Tensor, dst: torch.Tensor, max_dist: float, cell: Optional[float]):
+    if src.shape[0] == 0 or dst.shape[0] == 0:
+        return _capped(src.shape[0], max_dist, src.device)                 # nothing to launch
+    index = _Index(dst, cell, max_dist)
+    if index.n_valid == 0:
+        return _capped(src.shape[0], max_dist, src.device)
+    return index.query(src, max_dist)
+
+
+@torch.no_grad()
+def nn_distance(src, dst, max_dist: float, cell: Optional[float] = None):
+    """For every point of ``src [M,3]`` the Euclidean distance to the nearest point of ``dst [N,3]`` and that point's index:
+    ``(dist float32 [M], idx int64 [M])``; where no target is closer than ``max_dist`` (strictly), ``max_dist`` and ``-1``.  Exact - the
+    minimum a brute-force scan finds in fp32; equidistant targets resolve to the lowest index.  Non-finite targets are not indexed, a
+    non-finite query comes back capped.  ``cell``: the grid's cell edge (default: see the module docstring); ``max_dist / cell <= 32``."""
+    src, dst = _cloud(src, "src"), _cloud(dst, "dst")
+    max_dist = _positive(max_dist, "max_dist")
+    cell = None if cell is None else _positive(cell, "cell")
+    if cell is not None and max_dist / cell > ops.CLOUD_MAX_SHELLS:
+        raise MvsHipError("max_dist / cell = %g: at most %d shells are walked" % (max_dist / cell, ops.CLOUD_MAX_SHELLS))
+    with torch.cuda.device(src.device):
+        return _nn(src, dst, max_dist, cell)
+
+
+def _thin(xyz: torch.Tensor, voxel: float, attrs: Sequence[torch.Tensor] = ()):
+    """-> ``[centroids] + [mean of each attr]`` per occupied voxel, ascending key order."""
+    empty = [torch.empty(0, 3, dtype=torch.float32, device=xyz.device) for _ in range(1 + len(attrs))]
+    if xyz.shape[0] == 0:
+        return empty
+    index = _Index(xyz, voxel, None, want_sorted=False)
+    count = ops.cloud_voxel_count(index.grid) if index.n_valid else 0
+    if count == 0:
+        return empty
+    return [ops.cloud_voxel_write(a, index.perm, index.grid, index.cell_start, count) for a in [xyz] + list(attrs)]
+
+
+@torch.no_grad()
+def voxel_downsample(xyz, voxel: float, rgb=None):
+    """One point per occupied voxel of edge ``voxel`` (cells counted from the cloud's per-axis minimum): the centroid of the voxel's points,
+    accumulated in fp64 in original order - bit-identical from run to run.  Output order: ascending cell key (x fastest).  ``rgb [N,3]``
+    (uint8 or float32) is averaged the same way and returned in its own dtype (uint8: rounded to nearest): ``xyz`` or ``(xyz, rgb)``.
+    Non-finite points are dropped."""
+    xyz = _cloud(xyz, "xyz")
+    voxel = _positive(voxel, "voxel")
+    if rgb is None:
+        with torch.cuda.device(xyz.device):
+            return _thin(xyz, voxel)[0]
+    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda or rgb.shape != xyz.shape:
+        raise MvsHipError("rgb must be a GPU tensor of xyz's shape %s" % (tuple(xyz.shape),))
+    with torch.cuda.device(xyz.device):
+        out, col = _thin(xyz, voxel, [rgb.detach().to(torch.float32).contiguous()])
+    if rgb.dtype == torch.uint8:
+        col = (col + 0.5).floor().clamp_(0, 255).to(torch.uint8)
+    return out, col
+
+
+def _valid(xyz: torch.Tensor, mask) -> torch.Tensor:
+    ok = torch.isfinite(xyz).all(dim=1)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.device != xyz.device or mask.shape != (xyz.shape[0],):
+            raise MvsHipError("a mask must be a boolean tensor [%d] on the cloud's device" % xyz.shape[0])
+        ok = ok & mask.to(torch.bool)
+    return ok
+
+
+@torch.no_grad()
+def evaluate(pred_xyz, gt_xyz, max_dist: float, taus: Sequence[float] = (), voxel: Optional[float] = None, pred_mask=None, gt_mask=None,
+             cell: Optional[float] = None) -> Dict[str, object]:
+    """Scores of ``pred_xyz [M,3]`` against ``gt_xyz [N,3]`` (device tensors; ``SceneFusion.fuse(on_device=True)['xyz']`` as it is):
+
+    * ``n_pred``, ``n_gt``: points after the masks (boolean ``[M]`` / ``[N]``; non-finite points are dropped too) and the thinning
+      (``voxel``: :func:`voxel_downsample` of both clouds first);
+    * ``accuracy``: the mean of the pred -> gt distances that are ``< max_dist`` (DTU: ``d[d < max_dist].mean()``), ``completeness``: the
+      same for gt -> pred, ``overall``: their mean; ``pred_below_max`` / ``gt_below_max``: how many distances those means are over;
+    * per ``tau`` (``taus``, each ``<= max_dist``; lists in that order): ``precision`` = the share of pred points closer than ``tau`` to the
+      ground truth, ``recall`` = the same for gt points, ``fscore = 2PR / (P + R)`` (0 when ``P + R == 0``), and the counts
+      ``pred_below_tau`` / ``gt_below_tau``.
+
+    A mean or a share over an empty set is ``nan``.  Masked-out points never leave the device: they are turned into non-finite points,
+    which the index skips and the score does not count."""
+    pred, gt = _cloud(pred_xyz, "pred_xyz"), _cloud(gt_xyz, "gt_xyz")
+    if pred.device != gt.device:
+        raise MvsHipError("pred_xyz is on %s, gt_xyz on %s" % (pred.device, gt.device))
+    max_dist = _positive(max_dist, "max_dist")
+    taus = [float(t) for t in taus]
+    if len(taus) > ops.CLOUD_SCORE_MAX_K:
+        raise MvsHipError("%d thresholds, at most %d are built" % (len(taus), ops.CLOUD_SCORE_MAX_K))
+    for t in taus:
+        if not t <= max_dist:
+            raise MvsHipError("tau=%r exceeds max_dist=%r" % (t, max_dist))
+    cell = None if cell is None else _positive(cell, "cell")
+    if cell is not None and max_dist / cell > ops.CLOUD_MAX_SHELLS:
+        raise MvsHipError("max_dist / cell = %g: at most %d shells are walked" % (max_dist / cell, ops.CLOUD_MAX_SHELLS))
+    voxel = None if voxel is None else _positive(voxel, "voxel")
+    nan = float("nan")
+    with torch.cuda.device(pred.device):
+        clouds = []
+        for xyz, mask in ((pred, pred_mask), (gt, gt_mask)):
+            ok = _valid(xyz, mask)
+            xyz = torch.where(ok[:, None], xyz, torch.full((), nan, dtype=torch.float32, device=xyz.device))
+            if voxel is not None:
+                xyz = _thin(xyz, voxel)[0]
+                ok = torch.ones(xyz.shape[0], dtype=torch.bool, device=xyz.device)
+            clouds.append((xyz, ok))
+        rec = torch.zeros(2, ops.CLOUD_SCORE_RECORD_BYTES // 8, dtype=torch.int64, device=pred.device)
+        for i, ((src, ok), (dst, _)) in enumerate((clouds, clouds[::-1])):
+            dist = _nn(src, dst, max_dist, cell)[0]
+            dist = torch.where(ok, dist, torch.full((), nan, dtype=torch.float32, device=dist.device))      # a dropped point scores nothing
+            ops.cloud_score(dist, max_dist, taus, rec[i])
+            rec[i, 12] = ok.sum()                                          # a reserved slot: the points that count
+        host = rec.cpu()                                                   # the one read of the scores
+    out: Dict[str, object] = {}
+    sides = []
+    for i in range(2):
+        r = host[i]
+        n, below = int(r[12]), int(r[1])
+        counts = [int(c) for c in r[2:2 + len(taus)]]
+        sides.append((n, below, float(r[11:12].view(torch.float64)[0]), counts, [c / n if n else nan for c in counts]))
+    (n_pred, pb, acc, pc, prec), (n_gt, gb, comp, gc, rcl) = sides
+    out.update(n_pred=n_pred, n_gt=n_gt, accuracy=acc, completeness=comp, overall=0.5 * (acc + comp), pred_below_max=pb, gt_below_max=gb,
+               taus=taus, precision=prec, recall=rcl, pred_below_tau=pc, gt_below_tau=gc,
+               fscore=[(2.0 * p * r / (p + r) if p + r > 0.0 else 0.0) if p == p and r == r else nan for p, r in zip(prec, rcl)])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ DTU's filters (elementwise torch)
+def in_box(xyz: torch.Tensor, lo, hi) -> torch.Tensor:
+    """``lo <= xyz <= hi`` on every axis -> bool ``[N]`` (DTU's bounding box ``BB``)."""
+    lo = torch.as_tensor(lo, dtype=xyz.dtype, device=xyz.device)
+    hi = torch.as_tensor(hi, dtype=xyz.dtype, device=xyz.device)
+    return ((xyz >= lo) & (xyz <= hi)).all(dim=1)
+
+
+def in_volume(xyz: torch.Tensor, occupancy: torch.Tensor, origin, res: float) -> torch.Tensor:
+    """DTU's observation mask: voxel ``round((xyz - origin) / res)`` of ``occupancy [X,Y,Z]`` (uint8 / bool) is set; a point outside the
+    volume is outside the mask -> bool ``[N]``."""
+    origin = torch.as_tensor(origin, dtype=xyz.dtype, device=xyz.device)
+    occ = occupancy.to(xyz.device)
+    q = torch.round((xyz - origin) / float(res))
+    shape = torch.tensor(occ.shape, dtype=xyz.dtype, device=xyz.device)
+    inside = ((q >= 0) & (q < shape)).all(dim=1)                            # NaN compares false
+    qi = torch.where(inside[:, None], q, torch.zeros_like(q)).long()
+    return inside & (occ[qi[:, 0], qi[:, 1], qi[:, 2]] != 0)
+
+
+def above_plane(xyz: torch.Tensor, plane4) -> torch.Tensor:
+    """``[x y z 1] . plane4 > 0`` -> bool ``[N]`` (DTU's table plane)."""
+    p = torch.as_tensor(plane4, dtype=xyz.dtype, device=xyz.device)
+    return (xyz * p[:3]).sum(dim=1) + p[3] > 0

@@ -1,0 +1,589 @@
+// Point-cloud evaluation: nearest-neighbour distances between two clouds, voxel thinning and the score reduction behind DTU's
+// accuracy / completeness and Tanks-and-Temples' precision / recall / F-score (mvsformer_amd/cloud_eval.py).
+//
+// A uniform grid over the TARGET cloud: the cell of a point is floorf((x - origin) / cell) per axis - these two fp32 operations, in this
+// order; origin = the cloud's per-axis minimum (bounds_kernel: integer atomics on order-preserving bit patterns, so min and max are
+// exact and order-free).  A cell's key is x | y << 21 | z << 42: x runs fastest, the cells of one x-row are consecutive keys and, after
+// the sort, consecutive points - one range lookup serves the whole row of a shell.
+//
+//   1. mvs_cloud_bounds:      min / max over the finite points, the number of non-finite ones; the caller reads 32 bytes.
+//   2. mvs_cloud_grid_keys:   one int64 key per point (non-finite points: the largest key, behind every cell).
+//      ... the caller sorts the keys (stable) and keeps the permutation ...
+//   3. mvs_cloud_grid_build:  heads of runs of equal keys -> count per 256-point block -> one-block scan -> scatter: the table of
+//                             occupied cells (key, first point), and the points gathered into cell order.  Stable: the permutation of
+//                             a stable sort keeps the original order inside a cell.
+//   4. mvs_cloud_nn_query:    one lane per query, queries in cell order (their own sorted keys): Chebyshev shells of cells around the
+//                             query's cell until the lower bound of everything not yet visited reaches the best distance or max_dist.
+//   5. mvs_cloud_voxel_*:     the same table with cell = voxel: one lane per occupied voxel adds its points in double in original order.
+//   6. mvs_cloud_score:       counts below max_dist and below each tau (ballot + popcount, 64-bit integer atomics), the distances below
+//                             max_dist added in double per block, the block sums added in a fixed order by a second launch.
+// No float atomics, no block waits on another block, every phase is its own launch on one stream.
+//
+// Exactness of the search.  The cell of a point is computed in fp32, so a cell is not an exact box: with u = fl(fl(x - origin) / cell)
+// and u* the real quotient, |u - u*| <= 2^-23 |u*| (two roundings).  Two points whose cells differ by s + 1 or more on an axis are
+// therefore farther apart than (s - slack) * cell with slack = 2^-22 * 1.01 * (largest |u| in play).  The walk uses that bound, shrunk by
+// another 1e-5 relative to cover the fp32 rounding of the distance itself: it never skips a point the brute-force scan would pick.
+#include "common.h"
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+namespace {
+
+constexpr int CE_THREADS = 256;
+constexpr int CE_AXIS_BITS = 21;
+constexpr long long CE_AXIS_CELLS = 1LL << CE_AXIS_BITS;                  // MVS_CLOUD_MAX_AXIS_CELLS
+constexpr long long CE_BAD_KEY = 0x7fffffffffffffffLL;                    // non-finite points: behind every cell after the sort
+constexpr long long CE_MAX_POINTS = 1LL << 36;
+constexpr int CE_MAXK = MVS_CLOUD_SCORE_MAX_K;
+
+// the device record of a grid: MVS_CLOUD_GRID_RECORD_BYTES
+struct CloudGrid {
+    uint32_t lo_bits[3], hi_bits[3];      // order-preserving patterns of the per-axis min / max over the finite points
+    float origin[3];                      // = the minimum (0 for a cloud without a finite point)
+    float cell;
+    int32_t ncell[3];                     // occupied extent in cells per axis: floorf((max - origin) / cell) + 1
+    int32_t reserved;
+    long long n_bad;                      // non-finite points
+    long long n_valid;                    // points in the index
+    long long n_cells;                    // occupied cells
+};
+static_assert(sizeof(CloudGrid) <= MVS_CLOUD_GRID_RECORD_BYTES, "CloudGrid layout");
+
+// the device record of a score: MVS_CLOUD_SCORE_RECORD_BYTES = 16 x 8 bytes
+struct CloudScore {
+    long long n;                          // distances given
+    long long n_below;                    // distances < max_dist
+    long long below_tau[CE_MAXK];         // distances < tau[k]
+    double sum;                           // sum of the distances < max_dist
+    double mean;                          // sum / n_below (NaN for an empty set)
+    long long reserved[4];
+};
+static_assert(sizeof(CloudScore) == MVS_CLOUD_SCORE_RECORD_BYTES, "CloudScore layout");
+
+struct Taus { float t[CE_MAXK]; };
+
+__device__ __forceinline__ uint32_t order_bits(float f) {                  // a < b  <=>  order_bits(a) < order_bits(b) (finite values)
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__host__ __device__ inline float from_order_bits(uint32_t b) {
+    const uint32_t u = (b & 0x80000000u) ? (b & 0x7fffffffu) : ~b;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// the cell rule: two IEEE fp32 operations and a floor (no contraction: the build sets -ffp-contract=off)
+__host__ __device__ inline float cell_coord(float x, float origin, float cell) { return floorf((x - origin) / cell); }
+
+__device__ __forceinline__ long long make_key(int cx, int cy, int cz) {
+    return (long long)cx | ((long long)cy << CE_AXIS_BITS) | ((long long)cz << (2 * CE_AXIS_BITS));
+}
+
+// ---------------------------------------------------------------------------------------------------------- bounds
+__global__ __launch_bounds__(CE_THREADS) void cloud_bounds_kernel(const float* __restrict__ pts, long long N, CloudGrid* __restrict__ g) {
+    __shared__ uint32_t slo[3][CE_THREADS / 64], shi[3][CE_THREADS / 64], sbad[CE_THREADS / 64];
+    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    uint32_t bad = 0;
+    for (long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x; i < N; i += (long long)gridDim.x * CE_THREADS) {
+        const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+        if (finite3(x, y, z)) {
+            const uint32_t b[3] = {order_bits(x), order_bits(y), order_bits(z)};
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], b[a]); hi[a] = max(hi[a], b[a]); }
+        } else {
+            ++bad;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min(lo[a], (uint32_t)__shfl_down(lo[a], o, 64));
+            hi[a] = max(hi[a], (uint32_t)__shfl_down(hi[a], o, 64));
+        }
+        bad += __shfl_down(bad, o, 64);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { slo[a][wave] = lo[a]; shi[a][wave] = hi[a]; }
+        sbad[wave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        uint32_t l = slo[a][0], h = shi[a][0];
+        for (int w = 1; w < CE_THREADS / 64; ++w) { l = min(l, slo[a][w]); h = max(h, shi[a][w]); }
+        atomicMin(&g->lo_bits[a], l);
+        atomicMax(&g->hi_bits[a], h);
+    } else if (threadIdx.x == 3) {
+        uint32_t b = 0;
+        for (int w = 0; w < CE_THREADS / 64; ++w) b += sbad[w];
+        if (b) atomicAdd(reinterpret_cast<unsigned long long*>(&g->n_bad), (unsigned long long)b);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ keys
+struct GridSetup { float origin[3]; float cell; int ncell[3]; long long n_valid; };
+
+__global__ __launch_bounds__(CE_THREADS) void cloud_keys_kernel(const float* __restrict__ pts, long long N, GridSetup s, CloudGrid* __restrict__ g,
+                                                                long long* __restrict__ keys) {
+    const long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (i == 0) {                                                           // the record the later launches read
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { g->origin[a] = s.origin[a]; g->ncell[a] = s.ncell[a]; }
+        g->cell = s.cell;
+        g->n_valid = s.n_valid;
+        g->n_cells = 0;
+    }
+    if (i >= N) return;
+    const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    long long key = CE_BAD_KEY;
+    if (finite3(x, y, z)) {
+        // origin is the minimum and ncell was sized from the maximum by the same monotone operations: 0 <= c < ncell <= 2^21; the clamp
+        // only guards a caller whose bounds do not belong to these points
+        const int cx = min(max((int)cell_coord(x, s.origin[0], s.cell), 0), s.ncell[0] - 1);
+        const int cy = min(max((int)cell_coord(y, s.origin[1], s.cell), 0), s.ncell[1] - 1);
+        const int cz = min(max((int)cell_coord(z, s.origin[2], s.cell), 0), s.ncell[2] - 1);
+        key = make_key(cx, cy, cz);
+    }
+    keys[i] = key;
+}
+
+// a query's cell in the TARGET's grid, clamped to +-2^22 per axis (a query that far out has no target within any allowed max_dist)
+__device__ __forceinline__ int query_coord(float x, float origin, float cell) {
+    const float u = cell_coord(x, origin, cell);
+    return (int)fminf(fmaxf(u, -4194304.0f), 4194304.0f);
+}
+
+// queries are only ORDERED by these keys (lanes of a wavefront then walk the same cells): clamped into the grid, non-finite ones last
+__global__ __launch_bounds__(CE_THREADS) void cloud_query_keys_kernel(const float* __restrict__ q, long long M, const CloudGrid* __restrict__ g,
+                                                                      long long* __restrict__ keys) {
+    const long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (i >= M) return;
+    const float x = q[3 * i], y = q[3 * i + 1], z = q[3 * i + 2];
+    long long key = CE_BAD_KEY;
+    if (finite3(x, y, z)) {
+        const int top = (int)CE_AXIS_CELLS - 1;
+        const int cx = min(max(query_coord(x, g->origin[0], g->cell), 0), top);
+        const int cy = min(max(query_coord(y, g->origin[1], g->cell), 0), top);
+        const int cz = min(max(query_coord(z, g->origin[2], g->cell), 0), top);
+        key = make_key(cx, cy, cz);
+    }
+    keys[i] = key;
+}
+
+// ------------------------------------------------------------------------------------------------------------ build
+// workspace: offsets int64 [nb + 1], then counts uint32 [nb], nb = ceil(N / 256)
+__device__ __forceinline__ bool is_head(const long long* __restrict__ sk, long long i, long long n_valid) {
+    return i < n_valid && (i == 0 || sk[i] != sk[i - 1]);
+}
+
+__global__ __launch_bounds__(CE_THREADS) void cloud_heads_count_kernel(const long long* __restrict__ sk, long long N, const CloudGrid* __restrict__ g,
+                                                                       uint32_t* __restrict__ counts) {
+    __shared__ uint32_t part[CE_THREADS / 64];
+    const long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    const bool h = i < N && is_head(sk, i, g->n_valid);
+    const uint32_t c = __popcll(__ballot(h));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+constexpr int CE_SCAN_THREADS = 1024, CE_SCAN_ITEMS = 8;
+
+// one block: exclusive 64-bit scan of the block counts in tiles of 8192 with a running carry; the total is the number of occupied cells
+__global__ __launch_bounds__(CE_SCAN_THREADS) void cloud_scan_kernel(const uint32_t* __restrict__ counts, long long nb, long long* __restrict__ offsets,
+                                                                     CloudGrid* __restrict__ g, long long* __restrict__ cell_start) {
+    __shared__ uint32_t wsum[CE_SCAN_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    long long carry = 0;
+    for (long long base = 0; base < nb; base += (long long)CE_SCAN_THREADS * CE_SCAN_ITEMS) {
+        const long long i0 = base + (long long)t * CE_SCAN_ITEMS;
+        uint32_t v[CE_SCAN_ITEMS], s = 0;
+#pragma unroll
+        for (int j = 0; j < CE_SCAN_ITEMS; ++j) {
+            v[j] = (i0 + j < nb) ? counts[i0 + j] : 0u;
+            s += v[j];
+        }
+        uint32_t inc = s;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        uint32_t wbase = 0, tile = 0;
+        for (int w = 0; w < CE_SCAN_THREADS / 64; ++w) {
+            const uint32_t q = wsum[w];
+            wbase += (w < wave) ? q : 0u;
+            tile += q;
+        }
+        long long run = carry + (long long)wbase + (long long)(inc - s);
+#pragma unroll
+        for (int j = 0; j < CE_SCAN_ITEMS; ++j)
+            if (i0 + j < nb) { offsets[i0 + j] = run; run += v[j]; }
+        carry += tile;
+        __syncthreads();
+    }
+    if (t == 0) {
+        offsets[nb] = carry;
+        g->n_cells = carry;
+        cell_start[carry] = g->n_valid;                                     // carry <= N: cell_start holds N + 1 entries
+    }
+}
+
+__global__ __launch_bounds__(CE_THREADS) void cloud_build_kernel(const float* __restrict__ pts, long long N, const long long* __restrict__ sk,
+                                                                 const long long* __restrict__ perm, const CloudGrid* __restrict__ g,
+                                                                 const long long* __restrict__ offsets, float* __restrict__ sorted_pts,
+                                                                 long long* __restrict__ cell_keys, long long* __restrict__ cell_start) {
+    __shared__ uint32_t wcnt[CE_THREADS / 64];
+    const long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    const long long n_valid = g->n_valid;
+    const bool h = i < N && is_head(sk, i, n_valid);
+    const unsigned long long b = __ballot(h);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) wcnt[wave] = __popcll(b);
+    __syncthreads();
+    uint32_t woff = 0;
+    for (int w = 0; w < CE_THREADS / 64; ++w) woff += (w < wave) ? wcnt[w] : 0u;
+    if (h) {
+        const long long c = offsets[blockIdx.x] + (long long)(woff + rank);
+        if (c >= 0 && c < N) { cell_keys[c] = sk[i]; cell_start[c] = i; }   // never past what the caller allocated
+    }
+    if (sorted_pts && i < N && i < n_valid) {
+        const long long src = perm[i];
+        if (src >= 0 && src < N) {
+            sorted_pts[3 * i] = pts[3 * src];
+            sorted_pts[3 * i + 1] = pts[3 * src + 1];
+            sorted_pts[3 * i + 2] = pts[3 * src + 2];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ query
+// first index in [lo, hi) whose key is >= key
+__device__ __forceinline__ long long lower_bound(const long long* __restrict__ keys, long long lo, long long hi, long long key) {
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct Best { float d2; long long idx; };
+
+// the cells x0..x1 of row (y, z): one lookup, then their points (consecutive in cell order)
+__device__ __forceinline__ void visit_row(int x0, int x1, int y, int z, const CloudGrid& g, long long n_cells, const long long* __restrict__ cell_keys,
+                                          const long long* __restrict__ cell_start, const float* __restrict__ spts,
+                                          const long long* __restrict__ perm, float qx, float qy, float qz, Best& best) {
+    if (y < 0 || y >= g.ncell[1] || z < 0 || z >= g.ncell[2]) return;
+    x0 = max(x0, 0);
+    x1 = min(x1, g.ncell[0] - 1);
+    if (x0 > x1) return;
+    const long long a = lower_bound(cell_keys, 0, n_cells, make_key(x0, y, z));
+    if (a >= n_cells) return;
+    const long long e = lower_bound(cell_keys, a, min(n_cells, a + (long long)(x1 - x0 + 1)), make_key(x1, y, z) + 1);
+    if (e <= a) return;
+    const long long j0 = cell_start[a], j1 = min(cell_start[e], g.n_valid);
+    for (long long j = j0; j < j1; ++j) {
+        const float dx = qx - spts[3 * j], dy = qy - spts[3 * j + 1], dz = qz - spts[3 * j + 2];
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 <= best.d2) {                                                // NaN never enters: the index holds finite points only
+            const long long id = perm[j];
+            if (d2 < best.d2 || id < best.idx || best.idx < 0) { best.d2 = d2; best.idx = id; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(CE_THREADS) void cloud_nn_query_kernel(const float* __restrict__ q, long long M, const long long* __restrict__ q_perm,
+                                                                    const CloudGrid* __restrict__ gp, const float* __restrict__ spts,
+                                                                    const long long* __restrict__ perm, const long long* __restrict__ cell_keys,
+                                                                    const long long* __restrict__ cell_start, float max_dist,
+                                                                    float* __restrict__ dist, long long* __restrict__ idx) {
+    const long long t = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (t >= M) return;
+    long long qi = q_perm ? q_perm[t] : t;
+    if (qi < 0 || qi >= M) return;
+    const CloudGrid g = *gp;
+    const float qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
+    Best best;
+    best.d2 = INFINITY;
+    best.idx = -1;
+    const long long n_cells = g.n_cells;
+    if (finite3(qx, qy, qz) && n_cells > 0) {
+        const int c[3] = {query_coord(qx, g.origin[0], g.cell), query_coord(qy, g.origin[1], g.cell), query_coord(qz, g.origin[2], g.cell)};
+        int s0 = 0, nmax = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            s0 = max(s0, c[a] < 0 ? -c[a] : (c[a] > g.ncell[a] - 1 ? c[a] - (g.ncell[a] - 1) : 0));        // shells below s0 hold no cell
+            nmax = max(nmax, g.ncell[a]);
+        }
+        // see the head of the file: cells differing by s + 1 on an axis <=> farther apart than (s - slack) * cell
+        const float reach = max_dist / g.cell;                              // <= MVS_CLOUD_MAX_SHELLS, checked by the host
+        const int s_cap = (int)(reach * 1.0001f) + 3;                       // before slack
+        const float slack = 2.4082e-7f * (float)(nmax + s_cap + 4);         // 2^-22 * 1.01
+        const int s_last = s_cap + (int)slack + 1;                          // past it the bound exceeds max_dist whatever the rounding
+        for (int s = s0; s <= s_last; ++s) {
+            // everything not visited yet lies in shells >= s
+            const float lbc = (float)(s - 1) - slack;
+            if (lbc > 0.0f) {
+                const float lb = lbc * g.cell * 0.99999f;
+                if (lb >= max_dist || lb * lb * 0.99999f >= best.d2) break;
+            }
+            for (int dz = -s; dz <= s; ++dz)
+                for (int dy = -s; dy <= s; ++dy) {
+                    if (max(abs(dy), abs(dz)) == s) {
+                        visit_row(c[0] - s, c[0] + s, c[1] + dy, c[2] + dz, g, n_cells, cell_keys, cell_start, spts, perm, qx, qy, qz, best);
+                    } else {                                                // an inner row: its two end cells belong to this shell
+                        visit_row(c[0] - s, c[0] - s, c[1] + dy, c[2] + dz, g, n_cells, cell_keys, cell_start, spts, perm, qx, qy, qz, best);
+                        visit_row(c[0] + s, c[0] + s, c[1] + dy, c[2] + dz, g, n_cells, cell_keys, cell_start, spts, perm, qx, qy, qz, best);
+                    }
+                }
+        }
+    }
+    const float d = sqrtf(best.d2);
+    const bool hit = best.idx >= 0 && d < max_dist;
+    dist[qi] = hit ? d : max_dist;
+    idx[qi] = hit ? best.idx : -1;
+}
+
+// ------------------------------------------------------------------------------------------------------------ voxels
+// one lane per occupied voxel: its points' attributes (through the permutation: original order inside the voxel) added in double
+__global__ __launch_bounds__(CE_THREADS) void cloud_voxel_write_kernel(const float* __restrict__ attr, long long N, const long long* __restrict__ perm,
+                                                                       const CloudGrid* __restrict__ g, const long long* __restrict__ cell_start,
+                                                                       long long n_out, float* __restrict__ out) {
+    const long long c = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (c >= n_out || c >= g->n_cells) return;
+    const long long j0 = cell_start[c], j1 = min(cell_start[c + 1], g->n_valid);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (long long j = j0; j < j1; ++j) {
+        const long long src = perm[j];
+        if (src < 0 || src >= N) continue;
+        sx += (double)attr[3 * src];
+        sy += (double)attr[3 * src + 1];
+        sz += (double)attr[3 * src + 2];
+    }
+    const double n = (double)(j1 - j0);
+    out[3 * c] = (float)(sx / n);
+    out[3 * c + 1] = (float)(sy / n);
+    out[3 * c + 2] = (float)(sz / n);
+}
+
+// ------------------------------------------------------------------------------------------------------------- score
+constexpr int CE_SCORE_PPT = 4, CE_SCORE_P = CE_THREADS * CE_SCORE_PPT;
+
+__global__ __launch_bounds__(CE_THREADS) void cloud_score_kernel(const float* __restrict__ d, long long M, float max_dist, Taus taus, int K,
+                                                                 CloudScore* __restrict__ rec, double* __restrict__ partial) {
+    __shared__ double sred[CE_THREADS / 64];
+    __shared__ uint32_t cred[CE_THREADS / 64][1 + CE_MAXK];
+    const long long p0 = (long long)blockIdx.x * CE_SCORE_P + threadIdx.x;
+    double s = 0.0;
+    uint32_t cnt[1 + CE_MAXK];
+#pragma unroll
+    for (int c = 0; c <= CE_MAXK; ++c) cnt[c] = 0;
+#pragma unroll
+    for (int j = 0; j < CE_SCORE_PPT; ++j) {
+        const long long p = p0 + (long long)j * CE_THREADS;
+        const bool in = p < M;
+        const float v = in ? d[p] : 0.0f;
+        const bool below = in && v < max_dist;                              // a NaN distance is below nothing
+        s += below ? (double)v : 0.0;
+        cnt[0] += (uint32_t)__popcll(__ballot(below));
+#pragma unroll
+        for (int k = 0; k < CE_MAXK; ++k)
+            if (k < K) cnt[1 + k] += (uint32_t)__popcll(__ballot(in && v < taus.t[k]));
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        sred[wave] = s;
+#pragma unroll
+        for (int c = 0; c <= CE_MAXK; ++c) cred[wave][c] = cnt[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+    if (threadIdx.x <= K) {
+        const uint32_t c = (cred[0][threadIdx.x] + cred[1][threadIdx.x]) + (cred[2][threadIdx.x] + cred[3][threadIdx.x]);
+        long long* dst = threadIdx.x == 0 ? &rec->n_below : &rec->below_tau[threadIdx.x - 1];
+        if (c) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)c);
+    }
+}
+
+// one block, after the launch above: the block sums in a fixed order, then the mean
+__global__ __launch_bounds__(CE_THREADS) void cloud_score_final_kernel(const double* __restrict__ partial, long long nblk, long long M,
+                                                                       CloudScore* __restrict__ rec) {
+    __shared__ double sred[CE_THREADS / 64];
+    double s = 0.0;
+    for (long long i = threadIdx.x; i < nblk; i += CE_THREADS) s += partial[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double sum = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+        rec->n = M;
+        rec->sum = sum;
+        rec->mean = sum / (double)rec->n_below;                             // 0 / 0 = NaN: the mean over an empty set
+    }
+}
+
+inline unsigned blocks_for(long long n, int per) { return (unsigned)mvs::ceil_div(n, (long long)per); }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+}  // namespace
+
+extern "C" int mvs_cloud_bounds(const float* pts, int64_t N, void* grid, float* bounds_host, int64_t* n_nonfinite_host, mvs_stream_t stream) {
+    MVS_REQUIRE(pts && grid && bounds_host && n_nonfinite_host, "mvs_cloud_bounds: null pointer");
+    MVS_REQUIRE(N >= 1 && N <= CE_MAX_POINTS, "mvs_cloud_bounds: N=%lld points, 1..2^36 are taken (an empty cloud needs no launch)", (long long)N);
+    MVS_REQUIRE(aligned8(grid), "mvs_cloud_bounds: the grid record must be 8-byte aligned");
+    hipStream_t s = MVS_STREAM(stream);
+    CloudGrid* g = reinterpret_cast<CloudGrid*>(grid);
+    if (hipMemsetAsync(g, 0, MVS_CLOUD_GRID_RECORD_BYTES, s) != hipSuccess || hipMemsetAsync(g->lo_bits, 0xff, sizeof(g->lo_bits), s) != hipSuccess)
+        return mvs::finish_launch("mvs_cloud_bounds(memset)");
+    const unsigned nb = (unsigned)std::min<long long>(mvs::ceil_div((long long)N, (long long)CE_THREADS), 4096);
+    hipLaunchKernelGGL(cloud_bounds_kernel, dim3(nb), dim3(CE_THREADS), 0, s, pts, (long long)N, g);
+    if (int rc = mvs::finish_launch("mvs_cloud_bounds")) return rc;
+    CloudGrid h;
+    if (hipMemcpyAsync(&h, g, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return mvs::finish_launch("mvs_cloud_bounds(copy)");
+    const bool none = h.n_bad >= N;
+    for (int a = 0; a < 3; ++a) {
+        bounds_host[a] = none ? 0.0f : from_order_bits(h.lo_bits[a]);
+        bounds_host[3 + a] = none ? 0.0f : from_order_bits(h.hi_bits[a]);
+    }
+    *n_nonfinite_host = h.n_bad;
+    return MVS_OK;
+}
+
+extern "C" int mvs_cloud_grid_keys(const float* pts, int64_t N, float cell, const float* bounds_host, int64_t n_nonfinite, void* grid,
+                                   int64_t* keys, mvs_stream_t stream) {
+    MVS_REQUIRE(pts && bounds_host && grid && keys, "mvs_cloud_grid_keys: null pointer");
+    MVS_REQUIRE(N >= 1 && N <= CE_MAX_POINTS && n_nonfinite >= 0 && n_nonfinite <= N, "mvs_cloud_grid_keys: N=%lld points (%lld non-finite)",
+                (long long)N, (long long)n_nonfinite);
+    MVS_REQUIRE(isfinite(cell) && cell > 0.0f, "mvs_cloud_grid_keys: cell=%g must be positive and finite", (double)cell);
+    MVS_REQUIRE(aligned8(grid) && aligned8(keys), "mvs_cloud_grid_keys: the grid record and the keys must be 8-byte aligned");
+    GridSetup gs;
+    gs.cell = cell;
+    gs.n_valid = N - n_nonfinite;
+    for (int a = 0; a < 3; ++a) {
+        const float lo = bounds_host[a], hi = bounds_host[3 + a];
+        MVS_REQUIRE(isfinite(lo) && isfinite(hi) && lo <= hi, "mvs_cloud_grid_keys: bad bounds [%g, %g] on axis %d", (double)lo, (double)hi, a);
+        const float top = cell_coord(hi, lo, cell);                         // the largest cell coordinate any point of the cloud gets
+        MVS_REQUIRE(top < (float)CE_AXIS_CELLS, "mvs_cloud_grid_keys: axis %d spans %g cells of %g, fewer than 2^21 are indexed", a,
+                    (double)top + 1.0, (double)cell);
+        gs.origin[a] = lo;
+        gs.ncell[a] = (int)top + 1;
+    }
+    hipLaunchKernelGGL(cloud_keys_kernel, dim3(blocks_for(N, CE_THREADS)), dim3(CE_THREADS), 0, MVS_STREAM(stream), pts, (long long)N, gs,
+                       reinterpret_cast<CloudGrid*>(grid), reinterpret_cast<long long*>(keys));
+    return mvs::finish_launch("mvs_cloud_grid_keys");
+}
+
+extern "C" int mvs_cloud_query_keys(const float* queries, int64_t M, const void* grid, int64_t* keys, mvs_stream_t stream) {
+    MVS_REQUIRE(queries && grid && keys, "mvs_cloud_query_keys: null pointer");
+    MVS_REQUIRE(M >= 1 && M <= CE_MAX_POINTS, "mvs_cloud_query_keys: M=%lld queries, 1..2^36 are taken", (long long)M);
+    MVS_REQUIRE(aligned8(grid) && aligned8(keys), "mvs_cloud_query_keys: the grid record and the keys must be 8-byte aligned");
+    hipLaunchKernelGGL(cloud_query_keys_kernel, dim3(blocks_for(M, CE_THREADS)), dim3(CE_THREADS), 0, MVS_STREAM(stream), queries, (long long)M,
+                       reinterpret_cast<const CloudGrid*>(grid), reinterpret_cast<long long*>(keys));
+    return mvs::finish_launch("mvs_cloud_query_keys");
+}
+
+extern "C" int64_t mvs_cloud_grid_workspace_bytes(int64_t N) {
+    if (N < 1 || N > CE_MAX_POINTS) return -1;
+    const long long nb = mvs::ceil_div((long long)N, (long long)CE_THREADS);
+    return (int64_t)((nb + 1) * 8 + nb * 4);
+}
+
+extern "C" int mvs_cloud_grid_build(const float* pts, int64_t N, const int64_t* sorted_keys, const int64_t* perm, void* grid, void* workspace,
+                                    float* sorted_pts, int64_t* cell_keys, int64_t* cell_start, mvs_stream_t stream) {
+    MVS_REQUIRE(pts && sorted_keys && perm && grid && workspace && cell_keys && cell_start, "mvs_cloud_grid_build: null pointer");
+    MVS_REQUIRE(N >= 1 && N <= CE_MAX_POINTS, "mvs_cloud_grid_build: N=%lld points, 1..2^36 are taken", (long long)N);
+    MVS_REQUIRE(aligned8(grid) && aligned8(workspace) && aligned8(sorted_keys) && aligned8(perm) && aligned8(cell_keys) && aligned8(cell_start),
+                "mvs_cloud_grid_build: 64-bit arrays must be 8-byte aligned");
+    hipStream_t s = MVS_STREAM(stream);
+    const long long nb = mvs::ceil_div((long long)N, (long long)CE_THREADS);
+    long long* offsets = reinterpret_cast<long long*>(workspace);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(offsets + nb + 1);
+    CloudGrid* g = reinterpret_cast<CloudGrid*>(grid);
+    const long long* sk = reinterpret_cast<const long long*>(sorted_keys);
+    const long long* pm = reinterpret_cast<const long long*>(perm);
+    hipLaunchKernelGGL(cloud_heads_count_kernel, dim3((unsigned)nb), dim3(CE_THREADS), 0, s, sk, (long long)N, g, counts);
+    hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(CE_SCAN_THREADS), 0, s, counts, nb, offsets, g, reinterpret_cast<long long*>(cell_start));
+    hipLaunchKernelGGL(cloud_build_kernel, dim3((unsigned)nb), dim3(CE_THREADS), 0, s, pts, (long long)N, sk, pm, g, offsets, sorted_pts,
+                       reinterpret_cast<long long*>(cell_keys), reinterpret_cast<long long*>(cell_start));
+    return mvs::finish_launch("mvs_cloud_grid_build");
+}
+
+extern "C" int mvs_cloud_nn_query(const float* queries, int64_t M, const int64_t* query_perm, const void* grid, float cell, const float* sorted_pts,
+                                  const int64_t* perm, const int64_t* cell_keys, const int64_t* cell_start, int64_t N, float max_dist, float* dist,
+                                  int64_t* idx, mvs_stream_t stream) {
+    MVS_REQUIRE(queries && grid && sorted_pts && perm && cell_keys && cell_start && dist && idx, "mvs_cloud_nn_query: null pointer");
+    MVS_REQUIRE(M >= 1 && M <= CE_MAX_POINTS && N >= 1 && N <= CE_MAX_POINTS,
+                "mvs_cloud_nn_query: M=%lld queries, N=%lld targets (an empty side needs no launch)", (long long)M, (long long)N);
+    MVS_REQUIRE(isfinite(cell) && cell > 0.0f && isfinite(max_dist) && max_dist > 0.0f, "mvs_cloud_nn_query: cell=%g and max_dist=%g must be positive and finite",
+                (double)cell, (double)max_dist);
+    MVS_REQUIRE(max_dist / cell <= (float)MVS_CLOUD_MAX_SHELLS, "mvs_cloud_nn_query: max_dist / cell = %g, at most %d shells are walked",
+                (double)(max_dist / cell), MVS_CLOUD_MAX_SHELLS);
+    MVS_REQUIRE(aligned8(grid) && aligned8(query_perm) && aligned8(perm) && aligned8(cell_keys) && aligned8(cell_start) && aligned8(idx),
+                "mvs_cloud_nn_query: 64-bit arrays must be 8-byte aligned");
+    hipLaunchKernelGGL(cloud_nn_query_kernel, dim3(blocks_for(M, CE_THREADS)), dim3(CE_THREADS), 0, MVS_STREAM(stream), queries, (long long)M,
+                       reinterpret_cast<const long long*>(query_perm), reinterpret_cast<const CloudGrid*>(grid), sorted_pts,
+                       reinterpret_cast<const long long*>(perm), reinterpret_cast<const long long*>(cell_keys),
+                       reinterpret_cast<const long long*>(cell_start), max_dist, dist, reinterpret_cast<long long*>(idx));
+    return mvs::finish_launch("mvs_cloud_nn_query");
+}
+
+extern "C" int mvs_cloud_voxel_downsample_count(const void* grid, int64_t* count_host, mvs_stream_t stream) {
+    MVS_REQUIRE(grid && count_host, "mvs_cloud_voxel_downsample_count: null pointer");
+    hipStream_t s = MVS_STREAM(stream);
+    CloudGrid h;
+    if (hipMemcpyAsync(&h, grid, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return mvs::finish_launch("mvs_cloud_voxel_downsample_count(copy)");
+    *count_host = h.n_cells;
+    return MVS_OK;
+}
+
+extern "C" int mvs_cloud_voxel_downsample_write(const float* attr, int64_t N, const int64_t* perm, const void* grid, const int64_t* cell_start,
+                                                int64_t count, float* out, mvs_stream_t stream) {
+    MVS_REQUIRE(attr && perm && grid && cell_start && out, "mvs_cloud_voxel_downsample_write: null pointer");
+    MVS_REQUIRE(N >= 1 && N <= CE_MAX_POINTS && count >= 1 && count <= N,
+                "mvs_cloud_voxel_downsample_write: N=%lld points, count=%lld voxels (an empty cloud needs no launch)", (long long)N, (long long)count);
+    MVS_REQUIRE(aligned8(grid) && aligned8(perm) && aligned8(cell_start), "mvs_cloud_voxel_downsample_write: 64-bit arrays must be 8-byte aligned");
+    hipLaunchKernelGGL(cloud_voxel_write_kernel, dim3(blocks_for(count, CE_THREADS)), dim3(CE_THREADS), 0, MVS_STREAM(stream), attr, (long long)N,
+                       reinterpret_cast<const long long*>(perm), reinterpret_cast<const CloudGrid*>(grid),
+                       reinterpret_cast<const long long*>(cell_start), (long long)count, out);
+    return mvs::finish_launch("mvs_cloud_voxel_downsample_write");
+}
+
+extern "C" int64_t mvs_cloud_score_workspace_bytes(int64_t M) {
+    if (M < 0 || M > CE_MAX_POINTS) return -1;
+    return (int64_t)(8 * std::max<long long>(1, mvs::ceil_div((long long)M, (long long)CE_SCORE_P)));
+}
+
+extern "C" int mvs_cloud_score(const float* dist, int64_t M, float max_dist, const float* taus_host, int K, void* workspace, void* record,
+                               mvs_stream_t stream) {
+    MVS_REQUIRE(record && workspace && (M == 0 || dist) && (K == 0 || taus_host), "mvs_cloud_score: null pointer");
+    MVS_REQUIRE(M >= 0 && M <= CE_MAX_POINTS, "mvs_cloud_score: M=%lld distances", (long long)M);
+    MVS_REQUIRE(K >= 0 && K <= CE_MAXK, "mvs_cloud_score: K=%d thresholds, 0..%d are built", K, CE_MAXK);
+    MVS_REQUIRE(isfinite(max_dist) && max_dist > 0.0f, "mvs_cloud_score: max_dist=%g must be positive and finite", (double)max_dist);
+    MVS_REQUIRE(aligned8(record) && aligned8(workspace), "mvs_cloud_score: the record and the workspace must be 8-byte aligned");
+    Taus taus;
+    for (int k = 0; k < CE_MAXK; ++k) taus.t[k] = 0.0f;
+    for (int k = 0; k < K; ++k) {
+        MVS_REQUIRE(taus_host[k] <= max_dist, "mvs_cloud_score: tau[%d]=%g exceeds max_dist=%g", k, (double)taus_host[k], (double)max_dist);   // NaN fails too
+        taus.t[k] = taus_host[k];
+    }
+    hipStream_t s = MVS_STREAM(stream);
+    CloudScore* rec = reinterpret_cast<CloudScore*>(record);
+    if (hipMemsetAsync(rec, 0, sizeof(CloudScore), s) != hipSuccess) return mvs::finish_launch("mvs_cloud_score(memset)");
+    const long long nblk = mvs::ceil_div((long long)M, (long long)CE_SCORE_P);
+    double* partial = reinterpret_cast<double*>(workspace);
+    if (nblk > 0) hipLaunchKernelGGL(cloud_score_kernel, dim3((unsigned)nblk), dim3(CE_THREADS), 0, s, dist, (long long)M, max_dist, taus, K, rec, partial);
+    hipLaunchKernelGGL(cloud_score_final_kernel, dim3(1), dim3(CE_THREADS), 0, s, partial, nblk, (long long)M, rec);
+    return mvs::finish_launch("mvs_cloud_score");
+}

@@ -190,12 +190,14 @@ class SceneFusion:
         self.set_pairs(scene["pairs"])
         return self
 
-    def fuse(self, want: Sequence[str] = ("records", "xyz", "rgb"), with_intermediates: bool = False) -> Dict[str, object]:
+    def fuse(self, want: Sequence[str] = ("records", "xyz", "rgb"), with_intermediates: bool = False,
+             on_device: bool = False) -> Dict[str, object]:
         """-> ``xyz [M,3]`` float32, ``rgb [M,3]`` uint8, ``records`` uint8 ``[M*15]`` (the PLY vertex body) as numpy arrays (those named
         in ``want``), ``counts_per_view {ref_id: points}``, ``stats {ref_id: {photo, geo, final}}`` (fractions of the view's pixels), and
         ``n_points``.  Points come in ``pairs`` order, row-major inside a view, as the reference concatenates them.  With
         ``with_intermediates`` also the device tensors the compaction read: ``photo_mask [Nv,H,W]`` (views in ``view_ids`` order),
-        ``geo_mask [R,H,W]`` and ``points_dense [R,3,H,W]`` (one per pair)."""
+        ``geo_mask [R,H,W]`` and ``points_dense [R,3,H,W]`` (one per pair).  ``on_device``: the arrays named in ``want`` stay device
+        tensors (no copy to the host) - ``xyz`` is then what ``cloud_eval.evaluate`` takes as ``pred_xyz``."""
         from ._lib import MvsHipError
         if not self.pairs or not self.views:
             raise ValueError("SceneFusion.fuse: add_view() and set_pairs() first")
@@ -234,7 +236,7 @@ class SceneFusion:
                                                    want=("geo_mask", "points"))
                 geo = out["geo_mask"]
             comp = ops.pointcloud_compact(table, photo.view(len(ids), *self.hw), geo, out["points"], images, want=tuple(want))
-            res: Dict[str, object] = {k: comp[k].cpu().numpy() for k in want}
+            res: Dict[str, object] = {k: comp[k] if on_device else comp[k].cpu().numpy() for k in want}
         if with_intermediates:
             res.update(photo_mask=photo.view(len(ids), *self.hw), geo_mask=geo, points_dense=out["points"], view_ids=ids)
         hw = float(self.hw[0] * self.hw[1])

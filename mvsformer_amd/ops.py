@@ -1484,6 +1484,125 @@ def depth_metrics(depth_est, depth_gt, mask, thresholds=None, band=None, meter_s
     return counts, per_image, batch
 
 
+# ------------------------------------------------------------------------------------- point-cloud evaluation (csrc/cloud_eval.hip)
+CLOUD_GRID_RECORD_BYTES = 128                                # MVS_CLOUD_GRID_RECORD_BYTES
+CLOUD_SCORE_RECORD_BYTES = 128                               # MVS_CLOUD_SCORE_RECORD_BYTES
+CLOUD_MAX_AXIS_CELLS = 1 << 21                               # MVS_CLOUD_MAX_AXIS_CELLS
+CLOUD_MAX_SHELLS = 32                                        # MVS_CLOUD_MAX_SHELLS
+CLOUD_SCORE_MAX_K = 8                                        # MVS_CLOUD_SCORE_MAX_K
+
+
+def _chk_cloud(t, name: str) -> torch.Tensor:
+    _chk(t, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise _lib.MvsHipError("%s must be [N,3], got %s" % (name, tuple(t.shape)))
+    return t
+
+
+def cloud_bounds(pts):
+    """``pts [N,3]`` (N >= 1) -> ``(grid record (device), bounds: 6 floats on the host (min xyz, max xyz over the finite points), number of
+    non-finite points)``.  One host synchronisation: 32 bytes."""
+    _chk_cloud(pts, "pts")
+    grid = torch.empty(CLOUD_GRID_RECORD_BYTES // 8, device=pts.device, dtype=torch.int64)
+    bounds, bad = (ctypes.c_float * 6)(), ctypes.c_int64(0)
+    _call("mvs_cloud_bounds", ("cloud_bounds", "bytes", 12.0 * pts.shape[0]), _ptr(pts), pts.shape[0], _ptr(grid), ctypes.addressof(bounds),
+          ctypes.addressof(bad), _stream())
+    return grid, list(bounds), int(bad.value)
+
+
+def cloud_grid_keys(pts, cell: float, grid, bounds, n_bad: int) -> torch.Tensor:
+    """The int64 cell key of every point (non-finite points: the largest key); refuses a bad ``cell`` or an axis of 2^21 cells or more
+    before launching anything."""
+    _chk_cloud(pts, "pts"), _chk(grid, "grid", torch.int64)
+    keys = torch.empty(pts.shape[0], device=pts.device, dtype=torch.int64)
+    b = (ctypes.c_float * 6)(*bounds)
+    _call("mvs_cloud_grid_keys", ("cloud_grid_keys", "bytes", 20.0 * pts.shape[0]), _ptr(pts), pts.shape[0], float(cell), ctypes.addressof(b),
+          int(n_bad), _ptr(grid), _ptr(keys), _stream())
+    return keys
+
+
+def cloud_grid_build(pts, sorted_keys, perm, grid, want_sorted: bool = True):
+    """-> ``(sorted_pts [N,3] or None, cell_keys [N], cell_start [N+1])`` from the stably sorted keys and their permutation."""
+    _chk_cloud(pts, "pts"), _chk(sorted_keys, "sorted_keys", torch.int64), _chk(perm, "perm", torch.int64), _chk(grid, "grid", torch.int64)
+    n, dev = pts.shape[0], pts.device
+    if sorted_keys.shape != (n,) or perm.shape != (n,):
+        raise _lib.MvsHipError("cloud_grid_build: %d points, keys %s, perm %s" % (n, tuple(sorted_keys.shape), tuple(perm.shape)))
+    ws = torch.empty(_lib.load().mvs_cloud_grid_workspace_bytes(n) // 8 + 1, device=dev, dtype=torch.int64)
+    spts = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_sorted else None
+    cell_keys = torch.empty(n, device=dev, dtype=torch.int64)
+    cell_start = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    _call("mvs_cloud_grid_build", ("cloud_grid_build", "bytes", (24.0 + (24.0 if want_sorted else 0.0)) * n), _ptr(pts), n, _ptr(sorted_keys),
+          _ptr(perm), _ptr(grid), _ptr(ws), _ptr(spts), _ptr(cell_keys), _ptr(cell_start), _stream())
+    return spts, cell_keys, cell_start
+
+
+def cloud_query_keys(queries, grid) -> torch.Tensor:
+    _chk_cloud(queries, "queries"), _chk(grid, "grid", torch.int64)
+    keys = torch.empty(queries.shape[0], device=queries.device, dtype=torch.int64)
+    _call("mvs_cloud_query_keys", ("cloud_query_keys", "bytes", 20.0 * queries.shape[0]), _ptr(queries), queries.shape[0], _ptr(grid), _ptr(keys),
+          _stream())
+    return keys
+
+
+def cloud_nn_query(queries, query_perm, grid, cell: float, sorted_pts, perm, cell_keys, cell_start, max_dist: float):
+    """-> ``(dist [M] float32, idx [M] int64)`` in the caller's order; ``query_perm`` (or None) is the order the lanes take the queries in."""
+    _chk_cloud(queries, "queries"), _chk_cloud(sorted_pts, "sorted_pts"), _chk(grid, "grid", torch.int64)
+    for t, name in ((perm, "perm"), (cell_keys, "cell_keys"), (cell_start, "cell_start")):
+        _chk(t, name, torch.int64)
+    m, n = queries.shape[0], sorted_pts.shape[0]
+    if query_perm is not None and _chk(query_perm, "query_perm", torch.int64).shape != (m,):
+        raise _lib.MvsHipError("cloud_nn_query: query_perm must hold %d entries" % m)
+    if perm.shape != (n,) or cell_keys.shape != (n,) or cell_start.shape != (n + 1,):
+        raise _lib.MvsHipError("cloud_nn_query: the index arrays do not belong to %d points" % n)
+    dist = torch.empty(m, device=queries.device, dtype=torch.float32)
+    idx = torch.empty(m, device=queries.device, dtype=torch.int64)
+    _call("mvs_cloud_nn_query", "cloud_nn_query", _ptr(queries), m, _ptr(query_perm), _ptr(grid), float(cell), _ptr(sorted_pts), _ptr(perm),
+          _ptr(cell_keys), _ptr(cell_start), n, float(max_dist), _ptr(dist), _ptr(idx), _stream())
+    return dist, idx
+
+
+def cloud_voxel_count(grid) -> int:
+    """The number of occupied cells of a built grid (waits for the stream: 8 bytes)."""
+    _chk(grid, "grid", torch.int64)
+    count = ctypes.c_int64(0)
+    _call("mvs_cloud_voxel_downsample_count", None, _ptr(grid), ctypes.addressof(count), _stream())
+    return int(count.value)
+
+
+def cloud_voxel_write(attr, perm, grid, cell_start, count: int) -> torch.Tensor:
+    """``attr [N,3]`` -> ``[count,3]``: its mean per occupied voxel, in ascending key order."""
+    _chk_cloud(attr, "attr"), _chk(perm, "perm", torch.int64), _chk(grid, "grid", torch.int64), _chk(cell_start, "cell_start", torch.int64)
+    n = attr.shape[0]
+    if perm.shape != (n,) or cell_start.shape != (n + 1,):
+        raise _lib.MvsHipError("cloud_voxel_write: the index arrays do not belong to %d points" % n)
+    out = torch.empty(count, 3, device=attr.device, dtype=torch.float32)
+    _call("mvs_cloud_voxel_downsample_write", ("cloud_voxel_write", "bytes", 20.0 * n + 12.0 * count), _ptr(attr), n, _ptr(perm), _ptr(grid),
+          _ptr(cell_start), int(count), _ptr(out), _stream())
+    return out
+
+
+def cloud_score(dist, max_dist: float, taus=(), record=None) -> torch.Tensor:
+    """``dist [M]`` (M >= 0) -> the device record, int64 ``[16]``: n, count < max_dist, 8 counts < tau[k], then (as float64 bits) the sum of
+    the distances < max_dist and their mean.  ``record``: a 16-entry int64 slice to write into.  No host synchronisation."""
+    _chk(dist, "dist")
+    if dist.dim() != 1:
+        raise _lib.MvsHipError("cloud_score: dist must be [M], got %s" % (tuple(dist.shape),))
+    taus = [float(t) for t in taus]
+    if len(taus) > CLOUD_SCORE_MAX_K:
+        raise _lib.MvsHipError("cloud_score: %d thresholds, at most %d are built" % (len(taus), CLOUD_SCORE_MAX_K))
+    if record is None:
+        record = torch.empty(CLOUD_SCORE_RECORD_BYTES // 8, device=dist.device, dtype=torch.int64)
+    _chk(record, "record", torch.int64)
+    if record.numel() != CLOUD_SCORE_RECORD_BYTES // 8:
+        raise _lib.MvsHipError("cloud_score: the record holds %d int64" % (CLOUD_SCORE_RECORD_BYTES // 8))
+    m = dist.shape[0]
+    ws = torch.empty(_lib.load().mvs_cloud_score_workspace_bytes(m) // 8, device=dist.device, dtype=torch.float64)
+    th = (ctypes.c_float * max(1, len(taus)))(*taus)
+    _call("mvs_cloud_score", ("cloud_score", "bytes", 4.0 * m), _ptr(dist) if m else None, m, float(max_dist), ctypes.addressof(th), len(taus),
+          _ptr(ws), _ptr(record), _stream())
+    return record
+
+
 def bf16_embed_ch0(x: torch.Tensor) -> torch.Tensor:
     """fp32 ``[...]`` -> bf16 ``[..., 8]`` with the value in channel 0, zeros elsewhere (one launch instead of a fill and a strided copy)."""
     _chk(x, "x")

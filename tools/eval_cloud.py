@@ -1,0 +1,72 @@
+#!/usr/bin/env python
+"""Score a reconstructed point cloud against a ground-truth cloud on the MI355X (needs the GPU):
+
+    python tools/eval_cloud.py --pred fused.ply --gt stl.ply --max_dist 20 --tau 1,2 [--voxel 0.2] \\
+        [--box x0,y0,z0,x1,y1,z1] [--plane a,b,c,d] --out scores.json
+
+Both files are read with ``data_io.read_ply`` (the layout ``write_ply`` / ``fuse_scan`` write).  ``--box`` keeps the points of BOTH clouds
+inside the box, ``--plane`` those with ``a x + b y + c z + d > 0`` (DTU's bounding box and table plane).  The scores are
+``mvsformer_amd.cloud_eval.evaluate``'s: accuracy / completeness / overall (DTU: means of the distances below ``--max_dist``) and, per
+``--tau``, precision / recall / F-score (Tanks and Temples).  ``--voxel`` thins both clouds to one centroid per voxel first; DTU's own
+0.2 mm thinning is a greedy pass over a random shuffle, so scores after thinning are comparable to the MATLAB numbers, not equal to them.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mvsformer_amd import cloud_eval, data_io  # noqa: E402
+
+
+def floats(text, n=None):
+    v = [float(t) for t in text.split(",") if t.strip()]
+    if n is not None and len(v) != n:
+        raise argparse.ArgumentTypeError("expected %d comma-separated numbers, got %r" % (n, text))
+    return v
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--pred", required=True)
+    ap.add_argument("--gt", required=True)
+    ap.add_argument("--max_dist", type=float, required=True)
+    ap.add_argument("--tau", type=floats, default=[])
+    ap.add_argument("--voxel", type=float, default=None)
+    ap.add_argument("--box", type=lambda t: floats(t, 6), default=None)
+    ap.add_argument("--plane", type=lambda t: floats(t, 4), default=None)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_cloud.py runs the MI355X path: no GPU")
+    dev = torch.device(a.device)
+    t0 = time.perf_counter()
+    clouds, masks = [], []
+    for path in (a.pred, a.gt):
+        xyz = torch.from_numpy(data_io.read_ply(path)[0]).to(dev)
+        mask = None
+        if a.box is not None:
+            mask = cloud_eval.in_box(xyz, a.box[:3], a.box[3:])
+        if a.plane is not None:
+            up = cloud_eval.above_plane(xyz, a.plane)
+            mask = up if mask is None else mask & up
+        clouds.append(xyz)
+        masks.append(mask)
+    t1 = time.perf_counter()
+    scores = cloud_eval.evaluate(clouds[0], clouds[1], a.max_dist, a.tau, voxel=a.voxel, pred_mask=masks[0], gt_mask=masks[1])
+    t2 = time.perf_counter()
+    scores.update(pred=a.pred, gt=a.gt, max_dist=a.max_dist, voxel=a.voxel, box=a.box, plane=a.plane, points_read=[int(c.shape[0]) for c in clouds],
+                  seconds=dict(read=t1 - t0, evaluate=t2 - t1))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(scores, f, indent=1)
+    print(json.dumps(scores))
+    return scores
+
+
+if __name__ == "__main__":
+    main()
