@@ -21,6 +21,8 @@
 #include "common.h"
 #include "prims.h"
 #include "reduce_f64.h"
+#include "bn_core.h"
+#include "bf16_conv_plan.h"
 
 namespace {
 
@@ -32,6 +34,7 @@ using mvsprim::rsrc_t;
 using mvsprim::OOB;
 using mvsprim::make_rsrc;
 using mvsprim::resolve_count;
+using namespace mvsplan;
 
 __device__ __forceinline__ bf16x8 ld8(rsrc_t r, unsigned voff) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
@@ -297,8 +300,7 @@ __global__ __launch_bounds__(256) void bf16_conv_kernel(const ConvArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float f = (float)yv[r];
-                    float g = (float)o[r];                 // the ROUNDED gradient: what the apply kernel reads
-                    if (a.bn_relu && !(fmaf(f, p4[r], p4[CT + r]) > 0.0f)) g = 0.0f;
+                    const float g = mvsbn::masked_grad((float)o[r], f, &p4[r], &p4[CT + r], a.bn_relu);      // the ROUNDED gradient: what the apply kernel reads
                     ssum[nt][r] += g;
                     ssq[nt][r] = fmaf(g, (f - p4[2 * CT + r]) * p4[3 * CT + r], ssq[nt][r]);
                 }
@@ -681,8 +683,7 @@ __global__ __launch_bounds__(256) void bf16_bn_reduce_kernel(const __bf16* __res
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float f = (float)xv[e];
-                float g = (float)gv[e];
-                if (relu && !(fmaf(f, sc[e], sh[e]) > 0.0f)) g = 0.0f;
+                const float g = mvsbn::masked_grad((float)gv[e], f, &sc[e], &sh[e], relu);
                 s[e] += g;
                 q[e] = fmaf(g, (f - mu[e]) * is[e], q[e]);
             }
@@ -777,27 +778,14 @@ __global__ __launch_bounds__(256) void bf16_bn_bwd_apply_kernel(const __bf16* __
     for (int e = 0; e < 8; ++e) {
         const int c = c0 + e;
         const float f = (float)xv[e];
-        float g = (float)gv[e];
-        if (relu && !(fmaf(f, P[0][c], P[1][c]) > 0.0f)) g = 0.0f;
+        const float g = mvsbn::masked_grad((float)gv[e], f, &P[0][c], &P[1][c], relu);
         o[e] = (__bf16)(P[4][c] * (g - P[5][c] - (f - P[2][c]) * P[3][c] * P[6][c]));
     }
     reinterpret_cast<bf16x8*>(dx)[i] = o;
 }
 
-bool chan_ok(int c) { return c == 8 || c == 16 || c == 32 || c == 64; }
-
-// K split over a block's wavefronts (see bf16_conv_kernel): 32 / 64 input channels (27 / 54 steps per wavefront) while the launch has
-// at most ~3 work items per CU.  Every block streams the whole packed weight image (221 KB at 64 -> 64) from L2, and with one 64-voxel item
-// per block that traffic is what bounds a larger launch: measured per call (tools/exp_small_conv.py, 64 -> 64 stride 1), split / not split:
-// 256 items 14 / 37 us, 512 items 28 / 39 us, 1024 items 53 / 41 us (32 -> 64 stride (1,2,2): 11 / 21, 21 / 22, 41 / 24 us).
-bool conv_ksplit(int cin, int items, int taps) {
-    static const int lim = mvs::env_int("MVS_BF16_KSPLIT_ITEMS", 768);
-    return taps == 27 && cin >= 32 && items <= lim;
-}
-
 template <int GATHER, int SD, int SHW>
-int launch_conv(const ConvArgs& a, int cin, int nt, hipStream_t s) {
-    const bool ks = conv_ksplit(cin, a.items, 27);
+int launch_conv(const ConvArgs& a, int cin, int nt, bool ks, hipStream_t s) {
     const unsigned grid = (unsigned)((((ks ? a.items : (a.items + 3) / 4) + 7) / 8) * 8);
 #define MVS_BF16_GO(CINV, NTV, KSV) hipLaunchKernelGGL((bf16_conv_kernel<CINV, NTV, GATHER, SD, SHW, 27, KSV>), dim3(grid), dim3(256), 0, s, a)
 #define MVS_BF16_NT(CINV, KSV)                      \
@@ -890,68 +878,39 @@ extern "C" int mvs_bf16_pack_table_run(const void* dev_table, int njobs, int tot
     return mvs::finish_launch("mvs_bf16_pack_table_run");
 }
 
-// gather: 0 = Conv3d (out = (in - 1)/stride + 1), 1 = ConvTranspose3d k3 p1 op(stride-1) (out = in*stride)
-static int bf16_conv3d_impl(const void* x, const void* wpacked, const float* scale, const float* shift, const void* residual, void* y,
-                            int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd, int shw, int relu, float* stats_part,
-                            int groups, double* sums, mvs_stream_t stream, bool block_rows = false, int taps = 27, const void* bn_y = nullptr,
-                            const float* bn4 = nullptr, int bn_relu = 0, int bn_groups = 1);
+namespace {
+// What a convolution launch does beyond the raw product (nothing by default): the epilogue y = [relu](acc*scale[co] + shift[co])
+// [+ residual]; statistics rows (see ConvArgs) - one per work item, reduced here into `sums` per (group, channel), or with block_rows one
+// per BLOCK, transposed, left in stats_part for the caller's own second launch; with bn_y those hold a BatchNorm backward's two sums.
+struct ConvOpts {
+    const float *scale = nullptr, *shift = nullptr, *bn4 = nullptr;
+    const void *residual = nullptr, *bn_y = nullptr;
+    int relu = 0, bn_relu = 0, groups = 1;               // groups: of the statistics / of bn4
+    float* stats_part = nullptr;
+    double* sums = nullptr;
+    bool block_rows = false;
+};
 
-extern "C" int mvs_bf16_conv3d(const void* x, const void* wpacked, const float* scale, const float* shift, const void* residual, void* y,
-                               int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd, int shw, int relu,
-                               mvs_stream_t stream) {
-    return bf16_conv3d_impl(x, wpacked, scale, shift, residual, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, relu, nullptr, 1, nullptr, stream);
-}
-
-// mvs_bf16_conv3d without an epilogue and with a tap count: taps = 9 runs a 2-D kernel (the centre depth tap of a [*,*,1,3,3] weight) on a
-// D-agnostic volume - the visibility CNN's layers and their data gradients; weights packed with the same tap count
-extern "C" int mvs_bf16_conv3d_taps(const void* x, const void* wpacked, void* y, int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather,
-                                    int sd, int shw, int taps, mvs_stream_t stream) {
-    return bf16_conv3d_impl(x, wpacked, nullptr, nullptr, nullptr, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 0, nullptr, 1, nullptr, stream,
-                            false, taps);
-}
-
-// Raw convolution + the batch statistics of its (bf16-rounded) output in the same pass: sums [2*groups*Cout] = [sum | sum of squares]
-// per (group, channel), sample b in group b % groups - exactly what mvs_bf16_bn_stats would return for y.  workspace:
-// mvs_bf16_conv3d_stats_workspace_bytes (one partial row per work item, then the fixed-order reduce).
-extern "C" int64_t mvs_bf16_conv3d_stats_workspace_bytes(int B, int Cout, int Do, int Ho, int Wo) {
-    if (!chan_ok(Cout) || B < 1 || Do < 1 || Ho < 1 || Wo < 1) return -1;
-    return (int64_t)B * Do * Ho * ((Wo + 127) / 128) * 2 * 2 * Cout * (int64_t)sizeof(float);      // >= the work items of either form
-}
-
-extern "C" int mvs_bf16_conv3d_stats(const void* x, const void* wpacked, void* y, int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather,
-                                     int sd, int shw, int groups, double* sums, void* workspace, mvs_stream_t stream) {
-    MVS_REQUIRE(sums && workspace && groups >= 1 && B % groups == 0, "mvs_bf16_conv3d_stats: bad statistics arguments (B=%d groups=%d)", B, groups);
-    return bf16_conv3d_impl(x, wpacked, nullptr, nullptr, nullptr, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 0,
-                            reinterpret_cast<float*>(workspace), groups, sums, stream);
-}
-
-static int bf16_conv3d_impl(const void* x, const void* wpacked, const float* scale, const float* shift, const void* residual, void* y,
-                            int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd, int shw, int relu, float* stats_part,
-                            int groups, double* sums, mvs_stream_t stream, bool block_rows, int taps, const void* bn_y, const float* bn4,
-                            int bn_relu, int bn_groups) {
+// the launch by its plan (conv_plan is total: the callers plan first, the shape is checked here)
+int bf16_conv3d_impl(const void* x, const void* wpacked, void* y, int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd, int shw,
+                     int taps, const ConvPlan& p, const ConvOpts& o, mvs_stream_t stream) {
     MVS_REQUIRE(x && wpacked && y, "mvs_bf16_conv3d: null pointer");
     MVS_REQUIRE(taps == 27 || (taps == 9 && gather == 0 && sd == 1 && shw == 1 && Cin <= 16 && Cout <= 16),
                 "mvs_bf16_conv3d: taps = 9 (2-D kernel) is built for stride-1 convolutions of up to 16 channels");
     MVS_REQUIRE(chan_ok(Cin) && chan_ok(Cout), "mvs_bf16_conv3d: channels must be 8/16/32/64 (Cin=%d Cout=%d)", Cin, Cout);
     MVS_REQUIRE(B >= 1 && Di >= 1 && Hi >= 1 && Wi >= 1 && (gather == 0 || gather == 1), "mvs_bf16_conv3d: bad shape");
     MVS_REQUIRE((sd == 1 || sd == 2) && (shw == 1 || shw == 2) && !(sd == 2 && shw == 1), "mvs_bf16_conv3d: stride (%d,%d,%d) is not built", sd, shw, shw);
-    MVS_REQUIRE((!scale) == (!shift), "mvs_bf16_conv3d: scale and shift come together");
+    MVS_REQUIRE((!o.scale) == (!o.shift), "mvs_bf16_conv3d: scale and shift come together");
     MVS_REQUIRE((int64_t)Di * Hi * Wi * Cin * 2 < ((int64_t)1 << 31), "mvs_bf16_conv3d: one sample's input exceeds the 2 GiB buffer range");
+    MVS_REQUIRE(p.items < ((int64_t)1 << 30), "mvs_bf16_conv3d: too many rows");
     ConvArgs a{};
     a.x = reinterpret_cast<const __bf16*>(x), a.wp = reinterpret_cast<const __bf16*>(wpacked), a.y = reinterpret_cast<__bf16*>(y);
-    a.scale = scale, a.shift = shift, a.residual = reinterpret_cast<const __bf16*>(residual), a.relu = relu;
+    a.scale = o.scale, a.shift = o.shift, a.residual = reinterpret_cast<const __bf16*>(o.residual), a.relu = o.relu;
     a.B = B, a.Di = Di, a.Hi = Hi, a.Wi = Wi, a.Cout = Cout;
-    if (gather == 0) a.Do = (Di - 1) / sd + 1, a.Ho = (Hi - 1) / shw + 1, a.Wo = (Wi - 1) / shw + 1;
-    else a.Do = Di * sd, a.Ho = Hi * shw, a.Wo = Wi * shw;
-    // work items: 64 output voxels of a row; the transposed form with column stride 2 takes the two column parities of a 128-voxel chunk as two items
-    const bool wpar = gather == 1 && shw == 2;
-    a.nwchunks = wpar ? (a.Wo + 127) / 128 : (a.Wo + 63) / 64;
-    const int64_t items = (int64_t)B * a.Do * a.Ho * a.nwchunks * (wpar ? 2 : 1);
-    MVS_REQUIRE(items < ((int64_t)1 << 30), "mvs_bf16_conv3d: too many rows");
-    a.items = (int)items;
-    a.bn_y = reinterpret_cast<const __bf16*>(bn_y), a.bn4 = bn4, a.bn_relu = bn_relu, a.bn_groups = bn_groups;
-    a.stats_part = stats_part;
-    a.stats_rows = block_rows ? (int)(conv_ksplit(Cin, (int)items, taps) ? items : (items + 3) / 4) : 0;      // one row per BLOCK
+    a.Do = p.Do, a.Ho = p.Ho, a.Wo = p.Wo, a.nwchunks = p.nwchunks, a.items = (int)p.items;
+    a.bn_y = reinterpret_cast<const __bf16*>(o.bn_y), a.bn4 = o.bn4, a.bn_relu = o.bn_relu, a.bn_groups = o.groups;
+    a.stats_part = o.stats_part;
+    a.stats_rows = o.block_rows ? (int)p.block_rows : 0;
     hipStream_t s = MVS_STREAM(stream);
     const int nt = nt_of(Cout);
     int rc;
@@ -961,18 +920,51 @@ static int bf16_conv3d_impl(const void* x, const void* wpacked, const float* sca
         else hipLaunchKernelGGL((bf16_conv_kernel<16, 1, 0, 1, 1, 9>), dim3(grid), dim3(256), 0, s, a);
         rc = mvs::finish_launch("mvs_bf16_conv3d");
     } else if (gather == 0) {
-        if (sd == 1 && shw == 1) rc = launch_conv<0, 1, 1>(a, Cin, nt, s);
-        else if (sd == 2) rc = launch_conv<0, 2, 2>(a, Cin, nt, s);
-        else rc = launch_conv<0, 1, 2>(a, Cin, nt, s);
+        if (sd == 1 && shw == 1) rc = launch_conv<0, 1, 1>(a, Cin, nt, p.ksplit, s);
+        else if (sd == 2) rc = launch_conv<0, 2, 2>(a, Cin, nt, p.ksplit, s);
+        else rc = launch_conv<0, 1, 2>(a, Cin, nt, p.ksplit, s);
     } else {
-        if (sd == 1 && shw == 1) rc = launch_conv<1, 1, 1>(a, Cin, nt, s);
-        else if (sd == 2) rc = launch_conv<1, 2, 2>(a, Cin, nt, s);
-        else rc = launch_conv<1, 1, 2>(a, Cin, nt, s);
+        if (sd == 1 && shw == 1) rc = launch_conv<1, 1, 1>(a, Cin, nt, p.ksplit, s);
+        else if (sd == 2) rc = launch_conv<1, 2, 2>(a, Cin, nt, p.ksplit, s);
+        else rc = launch_conv<1, 1, 2>(a, Cin, nt, p.ksplit, s);
     }
-    if (rc != MVS_OK || !stats_part || block_rows) return rc;
-    // work items are sample-major, so the rows of sample b are [b*bps, (b+1)*bps): the grouped fixed-order reduce applies as is
-    mvs::launch_partials_reduce_grouped(stats_part, (int)(items / B), B, groups, Cout, sums, s);
+    if (rc != MVS_OK || !o.stats_part || o.block_rows) return rc;
+    // work items are sample-major, so the rows of sample b are [b*ips, (b+1)*ips): the grouped fixed-order reduce applies as is
+    mvs::launch_partials_reduce_grouped(o.stats_part, (int)p.items_per_sample, B, o.groups, Cout, o.sums, s);
     return mvs::finish_launch("mvs_bf16_conv3d_stats");
+}
+}  // namespace
+
+// gather: 0 = Conv3d (out = (in - 1)/stride + 1), 1 = ConvTranspose3d k3 p1 op(stride-1) (out = in*stride)
+extern "C" int mvs_bf16_conv3d(const void* x, const void* wpacked, const float* scale, const float* shift, const void* residual, void* y,
+                               int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather, int sd, int shw, int relu,
+                               mvs_stream_t stream) {
+    ConvOpts o;
+    o.scale = scale, o.shift = shift, o.residual = residual, o.relu = relu;
+    return bf16_conv3d_impl(x, wpacked, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 27, conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, 27, 1), o, stream);
+}
+
+// mvs_bf16_conv3d without an epilogue and with a tap count: taps = 9 runs a 2-D kernel (the centre depth tap of a [*,*,1,3,3] weight) on a
+// D-agnostic volume - the visibility CNN's layers and their data gradients; weights packed with the same tap count
+extern "C" int mvs_bf16_conv3d_taps(const void* x, const void* wpacked, void* y, int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather,
+                                    int sd, int shw, int taps, mvs_stream_t stream) {
+    return bf16_conv3d_impl(x, wpacked, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, taps, conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, taps, 1),
+                            ConvOpts{}, stream);
+}
+
+// Raw convolution + the batch statistics of its (bf16-rounded) output in the same pass: sums [2*groups*Cout] = [sum | sum of squares]
+// per (group, channel), sample b in group b % groups - exactly what mvs_bf16_bn_stats would return for y.  workspace:
+// mvs_bf16_conv3d_stats_workspace_bytes (one partial row per work item, then the fixed-order reduce).
+extern "C" int64_t mvs_bf16_conv3d_stats_workspace_bytes(int B, int Cout, int Do, int Ho, int Wo) {
+    return conv_rows_workspace_bytes(B, Cout, Do, Ho, Wo);
+}
+
+extern "C" int mvs_bf16_conv3d_stats(const void* x, const void* wpacked, void* y, int B, int Cin, int Cout, int Di, int Hi, int Wi, int gather,
+                                     int sd, int shw, int groups, double* sums, void* workspace, mvs_stream_t stream) {
+    MVS_REQUIRE(sums && workspace && groups >= 1 && B % groups == 0, "mvs_bf16_conv3d_stats: bad statistics arguments (B=%d groups=%d)", B, groups);
+    ConvOpts o;
+    o.stats_part = reinterpret_cast<float*>(workspace), o.groups = groups, o.sums = sums;
+    return bf16_conv3d_impl(x, wpacked, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 27, conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, 27, 1), o, stream);
 }
 
 namespace {
@@ -1242,8 +1234,22 @@ extern "C" int mvs_bf16_bn_bwd_reduce(const void* dy, const void* x, const float
 }
 
 namespace {
+// The tail of both fused finalize kernels once a (group, channel)'s sums are reduced (every thread holds them): mvsbn::finalize, the FIVE
+// rows of stats4 (o = its entry of row 0, rows CT apart) written by the `writer` thread, this group's turn at the running statistics.
+__device__ __forceinline__ void finalize_group(double s1, double s2, double count, float gamma, float beta, float eps, float momentum, bool writer,
+                                               float* __restrict__ o, int CT, float& rm, float& rv) {
+    float sc, sh, mean, invstd;
+    double var;
+    mvsbn::finalize(s1, s2, count, gamma, beta, eps, sc, sh, mean, invstd, var);
+    if (writer) {
+        o[0] = sc, o[CT] = sh, o[2 * CT] = mean, o[3 * CT] = invstd;
+        o[4 * CT] = gamma;                                   // the affine weight per (group, channel): what the backward's apply kernel reads
+    }
+    mvsbn::running_update(rm, rv, momentum, mean, var, count);
+}
+
 // partial rows -> per-(group, channel) sums -> mean / invstd / scale / shift and the running-statistics update, in ONE launch: the
-// arithmetic of partials_reduce_grouped followed by bn_finalize(_grouped) of train.hip (same order, same double-precision steps).
+// arithmetic of partials_reduce_grouped followed by bn_finalize_grouped of train.hip (same order, same double-precision steps).
 // One wavefront per base channel walks the groups in order (the running statistics take the groups' updates in order).
 __global__ __launch_bounds__(256) void bf16_bn_reduce_finalize_kernel(const float* __restrict__ part, int bps, int nsamples, int groups, int C,
                                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -1268,22 +1274,7 @@ __global__ __launch_bounds__(256) void bf16_bn_reduce_finalize_kernel(const floa
             s1 += __shfl_xor(s1, m, 64);
             s2 += __shfl_xor(s2, m, 64);
         }
-        const int cc = q * C + c;
-        const double mean = s1 / count;
-        double var = s2 / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        if (lane == 0) {
-            const float sc = g * invstd;
-            out4[cc] = sc;                                   // scale
-            out4[CT + cc] = (float)((double)bt - mean * (double)sc);   // shift (against the rounded scale, as bn_finalize_kernel)
-            out4[2 * CT + cc] = (float)mean;
-            out4[3 * CT + cc] = invstd;
-            out4[4 * CT + cc] = g;                          // the affine weight per (group, channel): what the backward's apply kernel reads
-        }
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        rm = (1.0f - momentum) * rm + momentum * (float)mean;
-        rv = (1.0f - momentum) * rv + momentum * (float)unbiased;
+        finalize_group(s1, s2, count, g, bt, eps, momentum, lane == 0, out4 + q * C + c, CT, rm, rv);
     }
     if (running_mean && lane == 0) {
         running_mean[c] = rm;
@@ -1320,7 +1311,17 @@ extern "C" int mvs_bf16_bn_train_fwd(const void* x, const void* residual, int re
 
 static int bn_bwd_apply_impl(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* invstd,
                              const float* gamma, const float* sums, double count, const float* count_dev, int relu, int C, int64_t R, int groups,
-                             int64_t rows_per_sample, void* dx, float* dgb, mvs_stream_t stream);
+                             int64_t rows_per_sample, void* dx, float* dgb, mvs_stream_t stream) {
+    BnShape sh;
+    MVS_REQUIRE(dy && x && scale && shift && mean && invstd && sums && dx && bn_shape(C, R, groups, rows_per_sample, &sh),
+                "mvs_bf16_bn_bwd_apply: bad arguments");
+    MVS_REQUIRE((int64_t)C * groups <= 256, "mvs_bf16_bn_bwd_apply: %d channels x %d groups exceed the 256 per-channel constants kept in LDS", C, groups);
+    const size_t total8 = (size_t)R * (C / 8);
+    hipLaunchKernelGGL(bf16_bn_bwd_apply_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, MVS_STREAM(stream),
+                       reinterpret_cast<const __bf16*>(dy), reinterpret_cast<const __bf16*>(x), scale, shift, mean, invstd, gamma, sums, count,
+                       count_dev, relu, C, total8, (size_t)sh.RS, groups, reinterpret_cast<__bf16*>(dx), dgb);
+    return mvs::finish_launch("mvs_bf16_bn_bwd_apply");
+}
 
 extern "C" int mvs_bf16_bn_bwd_apply(const void* dy, const void* x, const float* scale, const float* shift, const float* mean,
                                      const float* invstd, const float* gamma, const float* sums, double count, const float* count_dev,
@@ -1336,20 +1337,6 @@ extern "C" int mvs_bf16_bn_bwd_apply_dgb(const void* dy, const void* x, const fl
                                          mvs_stream_t stream) {
     MVS_REQUIRE(dgb, "mvs_bf16_bn_bwd_apply_dgb: null dgb");
     return bn_bwd_apply_impl(dy, x, scale, shift, mean, invstd, gamma, sums, count, count_dev, relu, C, R, groups, rows_per_sample, dx, dgb, stream);
-}
-
-static int bn_bwd_apply_impl(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* invstd,
-                             const float* gamma, const float* sums, double count, const float* count_dev, int relu, int C, int64_t R, int groups,
-                             int64_t rows_per_sample, void* dx, float* dgb, mvs_stream_t stream) {
-    BnShape sh;
-    MVS_REQUIRE(dy && x && scale && shift && mean && invstd && sums && dx && bn_shape(C, R, groups, rows_per_sample, &sh),
-                "mvs_bf16_bn_bwd_apply: bad arguments");
-    MVS_REQUIRE((int64_t)C * groups <= 256, "mvs_bf16_bn_bwd_apply: %d channels x %d groups exceed the 256 per-channel constants kept in LDS", C, groups);
-    const size_t total8 = (size_t)R * (C / 8);
-    hipLaunchKernelGGL(bf16_bn_bwd_apply_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, MVS_STREAM(stream),
-                       reinterpret_cast<const __bf16*>(dy), reinterpret_cast<const __bf16*>(x), scale, shift, mean, invstd, gamma, sums, count,
-                       count_dev, relu, C, total8, (size_t)sh.RS, groups, reinterpret_cast<__bf16*>(dx), dgb);
-    return mvs::finish_launch("mvs_bf16_bn_bwd_apply");
 }
 
 
@@ -1396,22 +1383,7 @@ __global__ __launch_bounds__(256) void bf16_bn_rows_finalize_kernel(const float*
         __syncthreads();
         s1 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
         s2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        const int cc = q * C + c;
-        const double mean = s1 / count;
-        double var = s2 / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        if (tid == 0) {
-            const float sc = g * invstd;
-            out4[cc] = sc;
-            out4[CT + cc] = (float)((double)bt - mean * (double)sc);
-            out4[2 * CT + cc] = (float)mean;
-            out4[3 * CT + cc] = invstd;
-            out4[4 * CT + cc] = g;                          // the affine weight per (group, channel): what the backward's apply kernel reads
-        }
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        rm = (1.0f - momentum) * rm + momentum * (float)mean;
-        rv = (1.0f - momentum) * rv + momentum * (float)unbiased;
+        finalize_group(s1, s2, count, g, bt, eps, momentum, tid == 0, out4 + q * C + c, CT, rm, rv);
     }
     if (running_mean && tid == 0) {
         running_mean[c] = rm;
@@ -1419,9 +1391,6 @@ __global__ __launch_bounds__(256) void bf16_bn_rows_finalize_kernel(const float*
     }
 }
 
-}  // namespace
-
-namespace {
 // part = [2C][nrows] transposed block rows (rows of sample b = [b*rps, (b+1)*rps), sample b in group b % groups) -> sums
 // [sum (groups*C) | second sum (groups*C)], fixed order: one block per (group, row kind j), its threads stride over the group's rows
 __global__ __launch_bounds__(256) void bf16_rows_reduce_kernel(const float* __restrict__ part, int nrows, int rps, int nsamples, int groups, int C,
@@ -1451,25 +1420,21 @@ extern "C" int mvs_bf16_conv3d_bnbwd(const void* x, const void* wpacked, void* y
                                      void* workspace, mvs_stream_t stream) {
     MVS_REQUIRE(bn_y && bn4 && sums && workspace && groups >= 1 && B % groups == 0, "mvs_bf16_conv3d_bnbwd: bad arguments (B=%d groups=%d)", B, groups);
     MVS_REQUIRE((sd == 1 || sd == 2) && (shw == 1 || shw == 2) && (gather == 0 || gather == 1), "mvs_bf16_conv3d_bnbwd: bad stride / gather");
-    int Do, Ho, Wo;
-    if (gather == 0) Do = (Di - 1) / sd + 1, Ho = (Hi - 1) / shw + 1, Wo = (Wi - 1) / shw + 1;
-    else Do = Di * sd, Ho = Hi * shw, Wo = Wi * shw;
-    const int64_t ips = (gather == 1 && shw == 2) ? (int64_t)Do * Ho * ((Wo + 127) / 128) * 2 : (int64_t)Do * Ho * ((Wo + 63) / 64);
-    const bool ks = conv_ksplit(Cin, (int)(ips * B), taps);
-    MVS_REQUIRE(B == 1 || ks || ips % 4 == 0, "mvs_bf16_conv3d_bnbwd: %lld work items per sample are not a multiple of 4", (long long)ips);
-    if (int rc = bf16_conv3d_impl(x, wpacked, nullptr, nullptr, addend, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 0,
-                                  reinterpret_cast<float*>(workspace), groups, nullptr, stream, true, taps, bn_y, bn4, relu, groups))
-        return rc;
-    const int nrows = ks ? (int)(ips * B) : (int)((ips * B + 3) / 4), rps = B == 1 ? nrows : (int)(ks ? ips : ips / 4);
+    // (one statistics group: the plan walks the rows as ONE sample, same rows, same order; blocks that straddle samples stay refused)
+    const ConvPlan p = conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, taps, groups);
+    MVS_REQUIRE(B == 1 || p.ksplit || p.items_per_sample % 4 == 0, "mvs_bf16_conv3d_bnbwd: %lld work items per sample are not a multiple of 4",
+                (long long)p.items_per_sample);
+    ConvOpts o;
+    o.residual = addend, o.stats_part = reinterpret_cast<float*>(workspace), o.groups = groups, o.block_rows = true;
+    o.bn_y = bn_y, o.bn4 = bn4, o.bn_relu = relu;
+    if (int rc = bf16_conv3d_impl(x, wpacked, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, taps, p, o, stream)) return rc;
     hipLaunchKernelGGL(bf16_rows_reduce_kernel, dim3(groups * 2 * Cout), dim3(256), 0, MVS_STREAM(stream), reinterpret_cast<const float*>(workspace),
-                       nrows, rps, B, groups, Cout, sums);
+                       (int)p.block_rows, (int)p.rows_per_sample, p.samples, groups, Cout, sums);
     return mvs::finish_launch("mvs_bf16_conv3d_bnbwd");
 }
 
 extern "C" int64_t mvs_bf16_conv3d_bn_fwd_workspace_bytes(int B, int Cout, int Do, int Ho, int Wo) {
-    if (!chan_ok(Cout) || B < 1 || Do < 1 || Ho < 1 || Wo < 1) return -1;
-    const int64_t items = (int64_t)B * Do * Ho * ((Wo + 127) / 128) * 2;           // >= the work items of either form (see bf16_conv3d_impl)
-    return items * 2 * Cout * (int64_t)sizeof(float);      // one row per block: up to one block per work item (the K-split form)
+    return conv_rows_workspace_bytes(B, Cout, Do, Ho, Wo);       // one row per block: up to one block per work item (the K-split form)
 }
 
 // y = raw conv(x) (kept: the BatchNorm backward needs it), z = [relu](BatchNorm_train(y)) [+ residual]; stats4 = [scale | shift | mean |
@@ -1483,28 +1448,22 @@ extern "C" int mvs_bf16_conv3d_bn_fwd(const void* x, const void* wpacked, void* 
                 "mvs_bf16_conv3d_bn_fwd: bad arguments (B=%d groups=%d; channels x groups <= 256)", B, groups);
     MVS_REQUIRE((!running_mean) == (!running_var), "mvs_bf16_conv3d_bn_fwd: running_mean and running_var come together");
     MVS_REQUIRE((sd == 1 || sd == 2) && (shw == 1 || shw == 2) && (gather == 0 || gather == 1), "mvs_bf16_conv3d_bn_fwd: bad stride / gather");
-    int Do, Ho, Wo;
-    if (gather == 0) Do = (Di - 1) / sd + 1, Ho = (Hi - 1) / shw + 1, Wo = (Wi - 1) / shw + 1;
-    else Do = Di * sd, Ho = Hi * shw, Wo = Wi * shw;
-    const int64_t ips = (gather == 1 && shw == 2) ? (int64_t)Do * Ho * ((Wo + 127) / 128) * 2 : (int64_t)Do * Ho * ((Wo + 63) / 64);   // work items per sample
-    const bool ks = conv_ksplit(Cin, (int)(ips * B), taps);                  // one work item per block then: four times the rows
     // (one statistics group: every row belongs to it, a block may straddle samples; the K-split form has one work item per row anyway)
-    MVS_REQUIRE(B == 1 || groups == 1 || ks || ips % 4 == 0,
-                "mvs_bf16_conv3d_bn_fwd: %lld work items per sample are not a multiple of 4 (block rows would straddle samples of different groups)", (long long)ips);
-    if (int rc = bf16_conv3d_impl(x, wpacked, nullptr, nullptr, nullptr, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 0,
-                                  reinterpret_cast<float*>(workspace), groups, nullptr, stream, true, taps))
-        return rc;
+    const ConvPlan p = conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, taps, groups);
+    MVS_REQUIRE(p.rows_per_sample >= 0,
+                "mvs_bf16_conv3d_bn_fwd: %lld work items per sample are not a multiple of 4 (block rows would straddle samples of different groups)",
+                (long long)p.items_per_sample);
+    ConvOpts o;
+    o.stats_part = reinterpret_cast<float*>(workspace), o.groups = groups, o.block_rows = true;
+    if (int rc = bf16_conv3d_impl(x, wpacked, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, taps, p, o, stream)) return rc;
     hipStream_t s = MVS_STREAM(stream);
-    const bool one = B == 1 || groups == 1;                                  // all rows are one group's
-    const int nrows = ks ? (int)(ips * B) : (int)((ips * B + 3) / 4), rps = one ? nrows : (int)(ks ? ips : ips / 4);
-    const int64_t R = (int64_t)B * Do * Ho * Wo;
-    hipLaunchKernelGGL(bf16_bn_rows_finalize_kernel, dim3(Cout), dim3(256), 0, s, reinterpret_cast<const float*>(workspace), nrows, rps, one ? 1 : B, groups,
-                       Cout, gamma, beta, running_mean, running_var, momentum, eps, (double)(R / groups), stats4,
+    const int64_t R = (int64_t)B * p.Do * p.Ho * p.Wo;
+    hipLaunchKernelGGL(bf16_bn_rows_finalize_kernel, dim3(Cout), dim3(256), 0, s, reinterpret_cast<const float*>(workspace), (int)p.block_rows,
+                       (int)p.rows_per_sample, p.samples, groups, Cout, gamma, beta, running_mean, running_var, momentum, eps, (double)(R / groups), stats4,
                        reinterpret_cast<long long*>(num_batches_tracked));
     const size_t total8 = (size_t)R * (Cout / 8);
-    const int CT = Cout * groups;
     hipLaunchKernelGGL(bf16_affine_act_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const __bf16*>(y),
-                       stats4, stats4 + CT, reinterpret_cast<const __bf16*>(residual), relu, Cout, total8, (size_t)(R / B), groups,
+                       stats4, stats4 + Cout * groups, reinterpret_cast<const __bf16*>(residual), relu, Cout, total8, (size_t)(R / B), groups,
                        reinterpret_cast<__bf16*>(z));
     return mvs::finish_launch("mvs_bf16_conv3d_bn_fwd");
 }

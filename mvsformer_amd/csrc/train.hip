@@ -9,11 +9,13 @@
 #include "common.h"
 #include "prims.h"
 #include "reduce_f64.h"
+#include "bn_core.h"
 
 namespace {
 
 using mvsprim::f32x4;
 using mvsprim::resolve_count;
+using mvsbn::block_sum;
 constexpr int CHUNK = 4096;            // elements of one (b, c) row handled by a block (256 threads x 4 x 4)
 
 // Activation codes of the BatchNorm kernels' `relu` argument (0 / 1 keep their old meaning): 0 none, 1 ReLU (the 3-D regularizer and the
@@ -35,30 +37,6 @@ __device__ __forceinline__ float act_grad(float z, int act) {          // d act(
     }
     if (act == 4) return 0.5f * (1.0f + erff(z * 0.70710678118654752440f)) + z * 0.39894228040143267794f * expf(-0.5f * z * z);   // Phi(z) + z phi(z)
     return 1.0f;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float t = 0.0f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-    return t;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-    return t;
 }
 
 // part[p][c] = sum x, part[p][C + c] = sum x^2 over this block's share of channel c; p = b * gridDim.x + blockIdx.x.
@@ -87,34 +65,10 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     }
 }
 
-// mean/var from the (possibly all-reduced) sums; eval-style scale/shift for the apply kernel; running-stat update
-__global__ void bn_finalize_kernel(const double* __restrict__ sums, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                   float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps,
-                                   double count_host, const float* __restrict__ count_dev, int C, float* __restrict__ scale,
-                                   float* __restrict__ shift, float* __restrict__ mean_out, float* __restrict__ invstd_out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const double count = resolve_count(count_host, count_dev);
-    const double mean = sums[c] / count;
-    double var = sums[C + c] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[c] : 1.0f, bt = beta ? beta[c] : 0.0f;
-    const float sc = g * invstd;
-    scale[c] = sc;
-    shift[c] = (float)((double)bt - mean * (double)sc);     // against the ROUNDED scale: x*scale + shift = (x - mean)*scale + beta, one rounding of |mean/std|
-    mean_out[c] = (float)mean;
-    invstd_out[c] = invstd;
-    if (running_mean) {
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
-        running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
-}
-
-// Grouped form: the tensor holds `groups` independent BatchNorm calls of the SAME module side by side as channels
-// g*C + c (the visibility CNN is applied once per source view in the reference, mvsformer_model.py:91: statistics per view,
-// one set of affine parameters, running statistics updated once per call IN ORDER).  One thread per base channel walks the groups.
+// mean/var from the (possibly all-reduced) sums; eval-style scale/shift for the apply kernel; running-stat update (mvsbn::finalize /
+// running_update).  The tensor holds `groups` independent BatchNorm calls of the SAME module side by side as channels g*C + c (the
+// visibility CNN is applied once per source view in the reference, mvsformer_model.py:91: statistics per view, one set of affine
+// parameters, running statistics updated once per call IN ORDER); a plain BatchNorm is groups = 1.  One thread per base channel walks the groups.
 __global__ void bn_finalize_grouped_kernel(const double* __restrict__ sums, const float* __restrict__ gamma, const float* __restrict__ beta,
                                            float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps,
                                            double count_host, const float* __restrict__ count_dev, int C, int groups,
@@ -128,18 +82,11 @@ __global__ void bn_finalize_grouped_kernel(const double* __restrict__ sums, cons
     float rm = running_mean ? running_mean[c] : 0.0f, rv = running_var ? running_var[c] : 0.0f;
     for (int q = 0; q < groups; ++q) {
         const int cc = q * C + c;
-        const double mean = sums[cc] / count;
-        double var = sums[CT + cc] / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float sc = g * invstd;
-        scale[cc] = sc;
-        shift[cc] = (float)((double)bt - mean * (double)sc);
-        mean_out[cc] = (float)mean;
-        invstd_out[cc] = invstd;
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        rm = (1.0f - momentum) * rm + momentum * (float)mean;
-        rv = (1.0f - momentum) * rv + momentum * (float)unbiased;
+        float sc, sh, mean, invstd;
+        double var;
+        mvsbn::finalize(sums[cc], sums[CT + cc], count, g, bt, eps, sc, sh, mean, invstd, var);
+        scale[cc] = sc, shift[cc] = sh, mean_out[cc] = mean, invstd_out[cc] = invstd;
+        mvsbn::running_update(rm, rv, momentum, mean, var, count);
     }
     if (running_mean) {
         running_mean[c] = rm;
@@ -313,8 +260,8 @@ extern "C" int mvs_bn_finalize(const double* sums, const float* gamma, const flo
                                float momentum, float eps, double count, const float* count_dev, int C, float* scale, float* shift,
                                float* mean, float* invstd, mvs_stream_t stream) {
     MVS_REQUIRE(sums && scale && shift && mean && invstd && C >= 1 && (count_dev || count >= 1.0), "mvs_bn_finalize: bad arguments");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, MVS_STREAM(stream), sums, gamma, beta, running_mean,
-                       running_var, momentum, eps, count, count_dev, C, scale, shift, mean, invstd);
+    hipLaunchKernelGGL(bn_finalize_grouped_kernel, dim3((C + 63) / 64), dim3(64), 0, MVS_STREAM(stream), sums, gamma, beta, running_mean,
+                       running_var, momentum, eps, count, count_dev, C, 1, scale, shift, mean, invstd);
     return mvs::finish_launch("mvs_bn_finalize");
 }
 

@@ -1002,37 +1002,28 @@ def bn_stats(x: torch.Tensor) -> torch.Tensor:
     return sums
 
 
-def _bn_args(sums, gamma, beta, running_mean, running_var, count_dev):
+def _bn_finalize(entry, dims, sums, gamma, beta, running_mean, running_var, momentum, eps, count, count_dev):
+    """The body of both finalize calls: ``dims`` = the entry point's channel arguments, ``(C,)`` or ``(C, groups)``."""
     _chk(sums, "sums", dtype=torch.float64), _opt(gamma, "bn.weight"), _opt(beta, "bn.bias"), _opt(running_mean, "bn.running_mean")
     _opt(running_var, "bn.running_var"), _opt(count_dev, "count_dev")
+    scale, shift, mean, invstd = (torch.empty(sums.numel() // 2, device=sums.device, dtype=torch.float32) for _ in range(4))
+    if running_mean is not None:
+        bump_weights_epoch()                                 # running statistics are written through raw pointers
+    _call(entry, None, _ptr(sums), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), float(count),
+          _ptr(count_dev), *dims, _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _stream())
+    return scale, shift, mean, invstd
 
 
 def bn_finalize(sums, gamma, beta, running_mean, running_var, momentum, eps, count, count_dev=None):
     """``count``: per-channel element count (host float); ``count_dev`` (SyncBatchNorm): device floats ``[n/4096, n%4096]``
     summed over the ranks with the sums - then ``count`` is ignored and nothing is read back to the host."""
-    _bn_args(sums, gamma, beta, running_mean, running_var, count_dev)
-    C = sums.numel() // 2
-    dev = sums.device
-    scale, shift, mean, invstd = (torch.empty(C, device=dev, dtype=torch.float32) for _ in range(4))
-    if running_mean is not None:
-        bump_weights_epoch()                                 # running statistics are written through raw pointers
-    _call("mvs_bn_finalize", None, _ptr(sums), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(momentum),
-          float(eps), float(count), _ptr(count_dev), C, _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _stream())
-    return scale, shift, mean, invstd
+    return _bn_finalize("mvs_bn_finalize", (sums.numel() // 2,), sums, gamma, beta, running_mean, running_var, momentum, eps, count, count_dev)
 
 
 def bn_finalize_grouped(sums, gamma, beta, running_mean, running_var, momentum, eps, count, groups: int, count_dev=None):
     """``groups`` BatchNorm calls of one module side by side as channels ``g*C + c``: ``sums [2*groups*C]``, parameters ``[C]``."""
-    _bn_args(sums, gamma, beta, running_mean, running_var, count_dev)
-    CT = sums.numel() // 2
-    C = CT // groups
-    dev = sums.device
-    scale, shift, mean, invstd = (torch.empty(CT, device=dev, dtype=torch.float32) for _ in range(4))
-    if running_mean is not None:
-        bump_weights_epoch()                                 # running statistics are written through raw pointers
-    _call("mvs_bn_finalize_grouped", None, _ptr(sums), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(momentum),
-          float(eps), float(count), _ptr(count_dev), C, int(groups), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _stream())
-    return scale, shift, mean, invstd
+    return _bn_finalize("mvs_bn_finalize_grouped", (sums.numel() // 2 // groups, int(groups)), sums, gamma, beta, running_mean, running_var,
+                        momentum, eps, count, count_dev)
 
 
 def affine_act(x, scale, shift, residual, relu):
@@ -1714,10 +1705,9 @@ class PackTable:
         return self.outs
 
 
-def bf16_conv3d(x, wpacked, cin, cout, gather: int, stride, scale=None, shift=None, residual=None, relu=False, taps: int = 27):
-    """``x [B,D,H,W,cin]`` bf16 -> ``[B,Do,Ho,Wo,cout]`` bf16; ``gather`` 0 = Conv3d, 1 = ConvTranspose3d (k3, p1, op = stride-1).
-    ``taps`` = 9: a 2-D kernel (no epilogue arguments then)."""
-    _chk16(x, "x"), _chk16(wpacked, "packed weights"), _opt(scale, "scale"), _opt(shift, "shift")
+def _bf16_conv_io(x, cin, cout, gather: int, stride, taps: int = 27):
+    """Shapes, the empty output and the useful FLOPs of a bf16 convolution of ``x [B,Di,Hi,Wi,cin]`` ->
+    ``(B, Di, Hi, Wi, Do, Ho, Wo, y, flops)``: every output voxel of a Conv3d has ``taps`` taps, of a ConvTranspose3d ``taps`` per INPUT voxel."""
     B, Di, Hi, Wi, C = x.shape
     assert C == cin
     sd, shw = stride
@@ -1726,20 +1716,30 @@ def bf16_conv3d(x, wpacked, cin, cout, gather: int, stride, scale=None, shift=No
     else:
         Do, Ho, Wo = Di * sd, Hi * shw, Wi * shw
     y = torch.empty(B, Do, Ho, Wo, cout, device=x.device, dtype=torch.bfloat16)
+    return B, Di, Hi, Wi, Do, Ho, Wo, y, 2.0 * taps * cin * cout * B * (Do * Ho * Wo if gather == 0 else Di * Hi * Wi)
+
+
+def _bf16_conv_tag(kernel: str, cin, cout, gather: int, stride, taps: int, flops: float):
+    """The timer tag of a bf16 convolution launch: the kernel instance and the FLOPs it is credited with."""
+    return ("%s<%d,%d,g%d,s%d%d%s>" % (kernel, cin, cout, gather, stride[0], stride[1], "" if taps == 27 else ",2d"), "flops", flops)
+
+
+def bf16_conv3d(x, wpacked, cin, cout, gather: int, stride, scale=None, shift=None, residual=None, relu=False, taps: int = 27):
+    """``x [B,D,H,W,cin]`` bf16 -> ``[B,Do,Ho,Wo,cout]`` bf16; ``gather`` 0 = Conv3d, 1 = ConvTranspose3d (k3, p1, op = stride-1).
+    ``taps`` = 9: a 2-D kernel (no epilogue arguments then)."""
+    _chk16(x, "x"), _chk16(wpacked, "packed weights"), _opt(scale, "scale"), _opt(shift, "shift")
+    B, Di, Hi, Wi, Do, Ho, Wo, y, flops = _bf16_conv_io(x, cin, cout, gather, stride, taps)
     if residual is not None:
         _chk16(residual, "residual")
         if residual.shape != y.shape:
             raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
-    # credited with the kernel's useful FLOPs: every output voxel of a Conv3d has 27 taps, of a ConvTranspose3d 27 per INPUT voxel
-    flops = 2.0 * 27 * cin * cout * B * (Do * Ho * Wo if gather == 0 else Di * Hi * Wi)
+    tag = _bf16_conv_tag("bf16_conv_kernel", cin, cout, gather, stride, taps, flops)
     if taps != 27:
         assert scale is None and shift is None and residual is None and not relu
-        tag = ("bf16_conv_kernel<%d,%d,g%d,s%d%d,2d>" % (cin, cout, gather, sd, shw), "flops", flops * taps / 27.0)
-        _call("mvs_bf16_conv3d_taps", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), sd, shw, int(taps), _stream())
+        _call("mvs_bf16_conv3d_taps", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), *stride, int(taps), _stream())
         return y
-    tag = ("bf16_conv_kernel<%d,%d,g%d,s%d%d>" % (cin, cout, gather, sd, shw), "flops", flops)
     _call("mvs_bf16_conv3d", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin, cout, Di, Hi, Wi,
-          int(gather), sd, shw, int(relu), _stream())
+          int(gather), *stride, int(relu), _stream())
     return y
 
 
@@ -1749,14 +1749,7 @@ def bf16_conv3d_bnbwd(x, wpacked, cin, cout, gather: int, stride, bn_y, bn4, rel
     ``bn4 [4, groups*cout]`` = the forward's (scale, shift, mean, invstd).  ``addend``: the tensor's other gradient (it also fed a skip
     connection), added before the rounding and the sums."""
     _chk16(x, "x"), _chk16(wpacked, "packed weights"), _chk16(bn_y, "bn_y"), _chk(bn4, "bn4")
-    B, Di, Hi, Wi, C = x.shape
-    assert C == cin
-    sd, shw = stride
-    if gather == 0:
-        Do, Ho, Wo = (Di - 1) // sd + 1, (Hi - 1) // shw + 1, (Wi - 1) // shw + 1
-    else:
-        Do, Ho, Wo = Di * sd, Hi * shw, Wi * shw
-    y = torch.empty(B, Do, Ho, Wo, cout, device=x.device, dtype=torch.bfloat16)
+    B, Di, Hi, Wi, Do, Ho, Wo, y, flops = _bf16_conv_io(x, cin, cout, gather, stride, taps)
     if tuple(bn_y.shape) != tuple(y.shape) or bn4.dim() != 2 or bn4.shape[0] < 4 or bn4.shape[1] != groups * cout or B % groups:
         raise _lib.MvsHipError("bf16_conv3d_bnbwd: BatchNorm input %s / statistics %s do not match the gradient %s (groups %d)" % (
             tuple(bn_y.shape), tuple(bn4.shape), tuple(y.shape), groups))
@@ -1766,9 +1759,8 @@ def bf16_conv3d_bnbwd(x, wpacked, cin, cout, gather: int, stride, bn_y, bn4, rel
             raise _lib.MvsHipError("bf16_conv3d_bnbwd: addend %s does not match the gradient %s" % (tuple(addend.shape), tuple(y.shape)))
     sums = torch.empty(2 * groups * cout, device=x.device, dtype=torch.float32)
     ws = _reduce_ws("mvs_bf16_conv3d_bn_fwd_workspace_bytes", x.device, B, cout, Do, Ho, Wo)
-    flops = 2.0 * taps * cin * cout * B * (Do * Ho * Wo if gather == 0 else Di * Hi * Wi)
-    tag = ("bf16_conv_kernel<%d,%d,g%d,s%d%d%s>" % (cin, cout, gather, sd, shw, ",2d" if taps == 9 else ""), "flops", flops)
-    _call("mvs_bf16_conv3d_bnbwd", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), sd, shw, int(taps), _ptr(bn_y),
+    tag = _bf16_conv_tag("bf16_conv_kernel", cin, cout, gather, stride, taps, flops)
+    _call("mvs_bf16_conv3d_bnbwd", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), *stride, int(taps), _ptr(bn_y),
           _ptr(bn4), int(relu), int(groups), _ptr(addend), _ptr(sums), _ptr(ws), _stream())
     return y, sums
 
@@ -1777,21 +1769,13 @@ def bf16_conv3d_stats(x, wpacked, cin, cout, gather: int, stride, groups: int = 
     """Raw convolution + the batch statistics of its bf16-rounded output in one pass -> ``(y, sums [2*groups*cout])``: the sums are
     what :func:`bf16_bn_stats` ``(y, groups)`` would return, without the extra pass over ``y``."""
     _chk16(x, "x"), _chk16(wpacked, "packed weights")
-    B, Di, Hi, Wi, C = x.shape
-    assert C == cin
-    sd, shw = stride
-    if gather == 0:
-        Do, Ho, Wo = (Di - 1) // sd + 1, (Hi - 1) // shw + 1, (Wi - 1) // shw + 1
-    else:
-        Do, Ho, Wo = Di * sd, Hi * shw, Wi * shw
+    B, Di, Hi, Wi, Do, Ho, Wo, y, flops = _bf16_conv_io(x, cin, cout, gather, stride)
     if B % groups:
         raise _lib.MvsHipError("grouped statistics: batch %d is not a multiple of %d groups" % (B, groups))
-    y = torch.empty(B, Do, Ho, Wo, cout, device=x.device, dtype=torch.bfloat16)
     sums = torch.empty(2 * groups * cout, device=x.device, dtype=torch.float64)
     ws = _reduce_ws("mvs_bf16_conv3d_stats_workspace_bytes", x.device, B, cout, Do, Ho, Wo)
-    flops = 2.0 * 27 * cin * cout * B * (Do * Ho * Wo if gather == 0 else Di * Hi * Wi)
-    tag = ("bf16_conv_kernel<%d,%d,g%d,s%d%d>" % (cin, cout, gather, sd, shw), "flops", flops)
-    _call("mvs_bf16_conv3d_stats", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), sd, shw, int(groups),
+    tag = _bf16_conv_tag("bf16_conv_kernel", cin, cout, gather, stride, 27, flops)
+    _call("mvs_bf16_conv3d_stats", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), *stride, int(groups),
           _ptr(sums), _ptr(ws), _stream())
     return y, sums
 
@@ -1938,16 +1922,9 @@ def bf16_conv3d_bn_fwd(x, wpacked, cin, cout, gather: int, stride, residual, rel
     statistics ride the convolution's epilogue) -> ``(y raw conv output, z, stats [5, groups*cout] = scale | shift | mean | invstd | gamma per (group, channel))``."""
     _chk16(x, "x"), _chk16(wpacked, "packed weights")
     _opt(gamma, "bn.weight"), _opt(beta, "bn.bias"), _opt(running_mean, "bn.running_mean"), _opt(running_var, "bn.running_var")
-    B, Di, Hi, Wi, C = x.shape
-    assert C == cin
-    sd, shw = stride
-    if gather == 0:
-        Do, Ho, Wo = (Di - 1) // sd + 1, (Hi - 1) // shw + 1, (Wi - 1) // shw + 1
-    else:
-        Do, Ho, Wo = Di * sd, Hi * shw, Wi * shw
+    B, Di, Hi, Wi, Do, Ho, Wo, y, flops = _bf16_conv_io(x, cin, cout, gather, stride, taps)
     if B % groups:
         raise _lib.MvsHipError("grouped statistics: batch %d is not a multiple of %d groups" % (B, groups))
-    y = torch.empty(B, Do, Ho, Wo, cout, device=x.device, dtype=torch.bfloat16)
     z = torch.empty_like(y)
     if residual is not None:
         _chk16(residual, "residual")
@@ -1957,12 +1934,11 @@ def bf16_conv3d_bn_fwd(x, wpacked, cin, cout, gather: int, stride, residual, rel
         _chk(num_batches_tracked, "bn.num_batches_tracked", dtype=torch.int64)
     st = torch.empty(5, groups * cout, device=x.device, dtype=torch.float32)
     ws = _reduce_ws("mvs_bf16_conv3d_bn_fwd_workspace_bytes", x.device, B, cout, Do, Ho, Wo)
-    flops = 2.0 * taps * cin * cout * B * (Do * Ho * Wo if gather == 0 else Di * Hi * Wi)
-    tag = ("bf16_conv_bn_fwd<%d,%d,g%d,s%d%d%s>" % (cin, cout, gather, sd, shw, ",2d" if taps == 9 else ""), "flops", flops)
+    tag = _bf16_conv_tag("bf16_conv_bn_fwd", cin, cout, gather, stride, taps, flops)
     if running_mean is not None:
         bump_weights_epoch()                                 # running statistics are written through raw pointers
     _call("mvs_bf16_conv3d_bn_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(y), _ptr(z), _ptr(residual), int(relu), B, cin, cout, Di, Hi, Wi,
-          int(gather), sd, shw, int(taps), int(groups), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(momentum), float(eps),
+          int(gather), *stride, int(taps), int(groups), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(momentum), float(eps),
           _ptr(num_batches_tracked), _ptr(st), _ptr(ws), _stream())
     return y, z, st
 

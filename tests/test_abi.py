@@ -393,3 +393,18 @@ def test_env_reader_matches_atoi_under_sanitizers(tmp_path):
                            os.path.join(REPO, "tests", "env_reader_check.cpp"), "-o", exe])
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip() == "ok" and not run.stderr.strip(), (run.returncode, run.stdout, run.stderr)
+
+
+def test_bf16_conv_plan_matches_the_replaced_formulas_under_sanitizers(tmp_path):
+    """tests/bf16_conv_plan_check.cpp: a stand-alone host program (its own main, host code only, sanitizers on the host side only, as
+    env_reader_check.cpp) that sweeps ``mvsplan::conv_plan`` / ``conv_rows_workspace_bytes`` (csrc/bf16_conv_plan.h) over every tile edge
+    against the three hand-copied formula sets they replaced: equal field by field, the statistics rows the convolution kernel writes
+    fit the workspace its callers allocate, and the fused entry points accept exactly the shapes they accepted.  This is the
+    buffer-sizing invariant of the bf16 training convolutions; it holds on the host before anything is launched."""
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "bf16_conv_plan_check")
+    subprocess.check_call([hipcc, "-std=c++17", "-x", "hip", "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           os.path.join(REPO, "tests", "bf16_conv_plan_check.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok" and not run.stderr.strip(), (run.returncode, run.stdout, run.stderr)
