@@ -1420,9 +1420,11 @@ extern "C" int mvs_bf16_conv3d_bnbwd(const void* x, const void* wpacked, void* y
                                      void* workspace, mvs_stream_t stream) {
     MVS_REQUIRE(bn_y && bn4 && sums && workspace && groups >= 1 && B % groups == 0, "mvs_bf16_conv3d_bnbwd: bad arguments (B=%d groups=%d)", B, groups);
     MVS_REQUIRE((sd == 1 || sd == 2) && (shw == 1 || shw == 2) && (gather == 0 || gather == 1), "mvs_bf16_conv3d_bnbwd: bad stride / gather");
-    // (one statistics group: the plan walks the rows as ONE sample, same rows, same order; blocks that straddle samples stay refused)
+    // (one statistics group: the plan walks the rows as ONE sample, same rows, same order - a block may straddle samples, every voxel reads
+    // group 0's bn4 - as in mvs_bf16_conv3d_bn_fwd; blocks that would straddle samples of DIFFERENT groups stay refused)
     const ConvPlan p = conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, taps, groups);
-    MVS_REQUIRE(B == 1 || p.ksplit || p.items_per_sample % 4 == 0, "mvs_bf16_conv3d_bnbwd: %lld work items per sample are not a multiple of 4",
+    MVS_REQUIRE(p.rows_per_sample >= 0,
+                "mvs_bf16_conv3d_bnbwd: %lld work items per sample are not a multiple of 4 (block rows would straddle samples of different groups)",
                 (long long)p.items_per_sample);
     ConvOpts o;
     o.residual = addend, o.stats_part = reinterpret_cast<float*>(workspace), o.groups = groups, o.block_rows = true;

@@ -102,12 +102,14 @@ int main() {
         // (c) the forward accepts exactly the shapes it accepted, with the same rows per sample and samples
         CHECK((p.rows_per_sample >= 0) == f.accepted);
         if (f.accepted) CHECK(p.rows_per_sample == f.rps && p.samples == f.samples && p.rows_per_sample * p.samples == p.block_rows);
-        // ... and so does the backward form (its own, stricter test, written with the plan's fields as the entry point writes it).  Its old
+        // ... and so does the backward form where its old copy accepted (that copy's own, stricter test, written with the plan's fields; the
+        // entry point has since taken the forward's test, rows_per_sample >= 0: a one-group batch whose blocks straddle samples runs).  Its old
         // copy walked a one-group batch as B samples of rps rows; the plan walks it as ONE sample of B * rps rows: bf16_rows_reduce_kernel
         // visits row (i / rps) * rps + i % rps = i for i < B * rps either way, so only the pair (rps, samples) differs, not the rows or their order.
         const OldRows w = old_bnbwd(B, Cin, Di, Hi, Wi, gather, sd, shw, taps);
         CHECK(p.items_per_sample == w.ips && p.ksplit == w.ks && p.block_rows == w.nrows);
-        CHECK((B == 1 || p.ksplit || p.items_per_sample % 4 == 0) == w.accepted);
+        CHECK(!w.accepted || p.rows_per_sample >= 0);      // what the entry point tests now (= the forward's f.accepted above) includes the old set
+        CHECK(w.accepted || p.rows_per_sample < 0 || (groups == 1 && B > 1));      // ... and adds only one-group batches
         if (w.accepted) {
             CHECK(p.rows_per_sample >= 0 && p.rows_per_sample * p.samples == p.block_rows && (int64_t)w.rps * w.samples == p.block_rows);
             if (groups > 1 || B == 1) CHECK(p.rows_per_sample == w.rps && p.samples == w.samples);
