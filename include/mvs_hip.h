@@ -46,7 +46,7 @@ extern "C" {
 
 #define MVS_OK 0
 #define MVS_EINVAL (-22)
-#define MVS_ABI_VERSION 50
+#define MVS_ABI_VERSION 51
 
 typedef void* mvs_stream_t;
 
@@ -853,6 +853,68 @@ int mvs_cloud_voxel_downsample_write(const float* attr, int64_t N, const int64_t
 int64_t mvs_cloud_score_workspace_bytes(int64_t M);
 int mvs_cloud_score(const float* dist, int64_t M, float max_dist, const float* taus_host, int K, void* workspace, void* record,
                     mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Sample preparation (csrc/sample_prep.hip): what the reference's data-set classes do between a decoded image and the network's input,
+ * on the caller's stream, with no host synchronisation.  Everything that changes per sample is read from device tables, so launch
+ * geometry depends on the static sizes only and a captured graph replays with new tables.  Every source index is clamped into its image.
+ *
+ * ptab [B][V][MVS_PREP_VIEW_INTS] int32, per view: [0] rw = int(W0 * resize_scale), [1] rh = int(H0 * resize_scale) (the ACTUAL resized
+ *   size: the resize's scale factor is W0 / rw and H0 / rh per axis, not the nominal resize_scale), [2] offset_x, [3] offset_y of the crop
+ *   inside the resized image, [4] != 0: take the offset from chosen[b] instead (the reference view; every view under consist_crop),
+ *   [5] resize_scale as fp32 bits (the intrinsics' factor), [6] != 0: pre_resize ran (resize_scale != 1.0), [7] 0.
+ * chosen [B][4] int32: offset_y, offset_x, accepted, index of the candidate - written by mvs_prep_accept, read by the others.
+ *
+ * mvs_prep_accept     datasets/dtu_dataset_ms.py:310-317: per sample the first of K candidate offsets cand [B][K][2] (y, x) whose crop has
+ *                     a positive pixel in generate_stage_depth's stage1 mask (dtu_dataset_ms.py:173-181: INTER_NEAREST to (w/8, h/8) of
+ *                     the crop of the INTER_NEAREST resize (:215-218) of the raw mask PNG binarised with > 10 (:160-165)); none: the last
+ *                     candidate and accepted = 0.  require_positive = 0 (mode != 'train'): candidate 0 as it is.
+ *                     INTER_NEAREST: source index min(floor(d * (src / dst)), src - 1), the quotient and the product in double.
+ * mvs_prep_geometry   depth_pyr / mask_pyr: mvs_prep_pyramid_floats(B, h, w) floats each = stage4 [B][h][w], stage3 [B][h/2][w/2], stage2
+ *                     [B][h/4][w/4], stage1 [B][h/8][w/8] back to back (generate_stage_depth over the reference view's cropped depth_hr
+ *                     [B][H0][W0] and mask); proj [4][B][V][2][4][4], stage1 first (dtu_dataset_ms.py:210-212,233-235,335-367: rows 0-1
+ *                     of the intrinsics times float32(resize_scale) when pre_resize ran, principal point minus the offset, then rows 0-1
+ *                     times 0.125, 0.25, 0.5 for stages 1-3, all fp32; [1][3][3] stays 0 as in the reference); depth_values [B][L] =
+ *                     np.arange(depth_min, depth_interval * ndepths + depth_min, depth_interval, dtype=float32) (:324-325) for depth_range
+ *                     [B][2] double = (depth_min, depth_interval): elements 0 and 1 are start and start + step formed in double and
+ *                     rounded, element i >= 2 is e0 + i * (e1 - e0) in fp32 (numpy's fill loop).  L is arange's length, which the caller
+ *                     computes: ceil((stop - start) / step) in double.
+ * mvs_prep_area_crop  pre_resize + final_crop fused (dtu_dataset_ms.py:205-208,222-231): out uint8 [B][V][h][w][3] = the crop window of
+ *                     cv2.resize(img, (rw, rh), INTER_AREA) of imgs uint8 [B][V][H0][W0][3].  OpenCV's area table per axis (cell
+ *                     [d * scale, d * scale + scale) clipped to the source, weight = covered length / min(scale, src - d * scale) formed in
+ *                     double and rounded to fp32, partial pixels narrower than 1e-3 dropped), horizontal pass then vertical in fp32,
+ *                     rounded to nearest-even and saturated; exact 2:1 on both axes: (a + b + c + d + 2) >> 2; rw = W0 and rh = H0: a copy.
+ *                     Built for reductions below 3:1 per axis (W0 < 3 * rw, H0 < 3 * rh; the reference's range is 0.45 .. 1): the
+ *                     table is on the device, so the entry cannot check it - the writer of ptab does (sample_prep.TrainTables); a
+ *                     smaller rw / rh gives clamped, truncated sums (at most 8 taps per axis), never an access outside imgs.
+ * mvs_prep_jitter_tail  datasets/color_jittor.py:53-83 as torchvision applies it to PIL images (ImageEnhance.Brightness / Contrast / Color,
+ *                     convert('HSV') + uint8 hue shift + convert('RGB')), then ToTensor, RandomGamma with clip_image=True and Normalize
+ *                     (dtu_dataset_ms.py:18-37,76-85,341-349): img uint8 [B][V][h][w][3] -> out fp32 [B][V][3][h][w]; out_u8 (may be NULL)
+ *                     [B][V][h][w][3] = the jittered bytes.  jtab [B][MVS_PREP_JITTER_INTS] int32: [0..3] fn_idx, [4] bit op = operation op
+ *                     is enabled (its range is not None), [5] != 0: gamma, [6] the uint8 hue shift, [8] brightness, [9] contrast, [10]
+ *                     saturation, [11] gamma factors as fp32 bits.  augment = 0: ToTensor + Normalize only.  has_contrast != 0: lsum [B][V]
+ *                     uint64 receives the sum of L over the image as it stands when contrast's turn comes (a launch of its own; contrast
+ *                     blends with int(sum / (h * w) + 0.5)).
+ * mvs_prep_eval_resize  datasets/general_eval.py:108-128,198-205: cv2.resize(img, (W, H)) (INTER_LINEAR, OpenCV's 8-bit fixed point: source
+ *                     coordinate (d + 0.5) * src / dst - 0.5 in fp32 clamped at the borders, coefficients round(w * 2048), vertical pass
+ *                     (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2; an exact 2:1 is INTER_AREA's integer path, as cv2.resize
+ *                     switches it) of src uint8 [V][H0][W0][3] with pad_rows rows of edge padding above and below (read_img's 'tt': 4) ->
+ *                     out_u8 [V][H][W][3] and / or out fp32 [V][3][H][W] after ToTensor + Normalize (either may be NULL, not both).
+ * ------------------------------------------------------------------------------------------------------- */
+#define MVS_PREP_VIEW_INTS 8
+#define MVS_PREP_JITTER_INTS 16
+int64_t mvs_prep_pyramid_floats(int B, int h, int w);
+int mvs_prep_accept(const uint8_t* mask_raw, const int32_t* ptab, const int32_t* cand, int B, int V, int H0, int W0, int h, int w, int K,
+                    int require_positive, int32_t* chosen, mvs_stream_t stream);
+int mvs_prep_geometry(const float* depth_hr, const uint8_t* mask_raw, const int32_t* ptab, const int32_t* chosen, const float* intrinsics,
+                      const float* extrinsics, const double* depth_range, int B, int V, int H0, int W0, int h, int w, int L, float* depth_pyr,
+                      float* mask_pyr, float* proj, float* depth_values, mvs_stream_t stream);
+int mvs_prep_area_crop(const uint8_t* imgs, const int32_t* ptab, const int32_t* chosen, int B, int V, int H0, int W0, int h, int w,
+                       uint8_t* out, mvs_stream_t stream);
+int mvs_prep_jitter_tail(const uint8_t* img, const int32_t* jtab, int B, int V, int h, int w, int augment, int has_contrast, uint64_t* lsum,
+                         float* out, uint8_t* out_u8, mvs_stream_t stream);
+int mvs_prep_eval_resize(const uint8_t* src, int V, int H0, int W0, int H, int W, int pad_rows, uint8_t* out_u8, float* out,
+                         mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * the DINO ViT-small feature branch of MVSFormer-P (csrc/vit.hip; models/vision_transformer.py:104-154,194-214,324-451,

@@ -20,7 +20,7 @@ from . import switches as sw
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIB: diagnostics only - another BUILD of the same library (tests/test_hip_multistream.py's variants); never a fallback
 LIB_PATH = sw.text("MVS_HIP_LIB") or os.path.join(_HERE, "libmvs_hip.so")
-ABI_VERSION = 50
+ABI_VERSION = 51
 
 from ctypes import c_double  # noqa: E402
 
@@ -173,6 +173,12 @@ SIGNATURES = {
     "mvs_cloud_voxel_downsample_write": (I, [P, L, P, P, P, L, P, P]),
     "mvs_cloud_score_workspace_bytes": (L, [L]),
     "mvs_cloud_score": (I, [P, L, F, P, I, P, P, P]),
+    "mvs_prep_pyramid_floats": (L, [I, I, I]),
+    "mvs_prep_accept": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P]),
+    "mvs_prep_geometry": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),
+    "mvs_prep_area_crop": (I, [P, P, P, I, I, I, I, I, I, P, P]),
+    "mvs_prep_jitter_tail": (I, [P, P, I, I, I, I, I, I, P, P, P, P]),
+    "mvs_prep_eval_resize": (I, [P, I, I, I, I, I, I, P, P, P]),
     "mvs_bf16_embed_ch0": (I, [P, P, L, P]),
     "mvs_gemm_x3": (I, [P, P, P, I, I, I, I, I, I, I, I, L, L, L, L, L, L, I, I, I, I, I, F, P, P, I, P, P, P]),
     "mvs_attention_x3": (I, [P, P, P, I, I, I, I, I, F, P]),

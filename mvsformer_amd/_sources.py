@@ -30,6 +30,7 @@ _RULES = [
      r"mvs_init_range|mvs_schedule_range|mvs_conf)", ["head.hip", "common.h", PUB]),
     (r"^(proj_|mvs_proj)", ["proj.hip", "common.h", PUB]),
     (r"^(depth_metrics|mvs_depth_metrics)", ["metrics.hip", "common.h", PUB]),
+    (r"^(prep_|mvs_prep)", ["sample_prep.hip", "common.h", PUB]),
     (r"^(cloud_|mvs_cloud)", ["cloud_eval.hip", "common.h", PUB]),
     (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
     (r"^(fpn_v2_tail|mvs_fpn_v2_tail)", ["fpn_v2_tail.hip", "conv_common.h", "common.h", "prims.h", PUB]),

@@ -2610,3 +2610,113 @@ def upsample2x_bwd(dy: torch.Tensor) -> torch.Tensor:
     dx = torch.empty(N, C, H // 2, W // 2, device=dy.device, dtype=torch.float32)
     _call("mvs_upsample2x_bwd", "upsample2x_bwd", _ptr(dy), _ptr(dx), N * C, H // 2, W // 2, _stream())
     return dx
+
+
+# ------------------------------------------------------------------------------------- sample preparation (csrc/sample_prep.hip)
+PREP_VIEW_INTS = 8                                           # MVS_PREP_VIEW_INTS
+PREP_JITTER_INTS = 16                                        # MVS_PREP_JITTER_INTS
+
+
+def _chk_prep_tables(ptab, chosen, B, V):
+    _chk(ptab, "ptab", torch.int32), _chk(chosen, "chosen", torch.int32)
+    if tuple(ptab.shape) != (B, V, PREP_VIEW_INTS) or tuple(chosen.shape) != (B, 4):
+        raise _lib.MvsHipError("sample_prep: ptab %s / chosen %s for B=%d V=%d" % (tuple(ptab.shape), tuple(chosen.shape), B, V))
+
+
+def prep_accept(mask_raw, ptab, cand, crop_hw, require_positive=True, chosen=None):
+    """``mask_raw`` uint8 ``[B,H0,W0]`` (the raw PNG), ``ptab`` int32 ``[B,V,8]``, ``cand`` int32 ``[B,K,2]`` (y, x) -> ``chosen`` int32
+    ``[B,4]`` = (offset_y, offset_x, accepted, index): the first candidate whose stage-1 mask has a positive pixel.  No host sync."""
+    _chk(mask_raw, "mask_raw", torch.uint8), _chk(cand, "cand", torch.int32)
+    if mask_raw.dim() != 3 or cand.dim() != 3 or cand.shape[0] != mask_raw.shape[0] or cand.shape[2] != 2 or ptab.dim() != 3:
+        raise _lib.MvsHipError("prep_accept: shapes %s %s" % (tuple(mask_raw.shape), tuple(cand.shape)))
+    B, H0, W0 = mask_raw.shape
+    V, K = ptab.shape[1], cand.shape[1]
+    if chosen is None:
+        chosen = torch.empty(B, 4, device=mask_raw.device, dtype=torch.int32)
+    _chk_prep_tables(ptab, chosen, B, V)
+    h, w = crop_hw
+    _call("mvs_prep_accept", "prep_accept", _ptr(mask_raw), _ptr(ptab), _ptr(cand), B, V, H0, W0, int(h), int(w), K, int(bool(require_positive)),
+          _ptr(chosen), _stream())
+    return chosen
+
+
+def prep_geometry(depth_hr, mask_raw, ptab, chosen, intrinsics, extrinsics, depth_range, crop_hw, length):
+    """-> ``(depth {stage1..4: [B,hs,ws]}, mask {...}, proj {stage1..4: [B,V,2,4,4]}, depth_values [B,length])``; ``depth_range`` fp64
+    ``[B,2]`` = (depth_min, depth_interval), ``length`` = the number of hypotheses ``np.arange`` yields for them."""
+    _chk(depth_hr, "depth_hr"), _chk(mask_raw, "mask_raw", torch.uint8), _chk(intrinsics, "intrinsics"), _chk(extrinsics, "extrinsics")
+    _chk(depth_range, "depth_range", torch.float64)
+    if depth_hr.dim() != 3 or mask_raw.shape != depth_hr.shape or ptab.dim() != 3:
+        raise _lib.MvsHipError("prep_geometry: depth_hr %s mask_raw %s" % (tuple(depth_hr.shape), tuple(mask_raw.shape)))
+    B, H0, W0 = depth_hr.shape
+    V = ptab.shape[1]
+    _chk_prep_tables(ptab, chosen, B, V)
+    if tuple(intrinsics.shape) != (B, V, 3, 3) or tuple(extrinsics.shape) != (B, V, 4, 4) or tuple(depth_range.shape) != (B, 2):
+        raise _lib.MvsHipError("prep_geometry: intrinsics %s extrinsics %s depth_range %s" % (tuple(intrinsics.shape), tuple(extrinsics.shape),
+                                                                                             tuple(depth_range.shape)))
+    h, w = int(crop_hw[0]), int(crop_hw[1])
+    n = _lib.load().mvs_prep_pyramid_floats(B, h, w)
+    if n < 0:
+        raise _lib.MvsHipError("prep_geometry: crop %dx%d is too small for the 1/8 stage" % (h, w))
+    dev = depth_hr.device
+    dpyr, mpyr = torch.empty(n, device=dev), torch.empty(n, device=dev)
+    proj = torch.empty(4, B, V, 2, 4, 4, device=dev)
+    dv = torch.empty(B, int(length), device=dev)
+    _call("mvs_prep_geometry", "prep_geometry", _ptr(depth_hr), _ptr(mask_raw), _ptr(ptab), _ptr(chosen), _ptr(intrinsics), _ptr(extrinsics),
+          _ptr(depth_range), B, V, H0, W0, h, w, int(length), _ptr(dpyr), _ptr(mpyr), _ptr(proj), _ptr(dv), _stream())
+    depth, mask, at = {}, {}, 0
+    for s in range(4):
+        hs, ws = h >> s, w >> s
+        depth["stage%d" % (4 - s)] = dpyr[at:at + B * hs * ws].view(B, hs, ws)
+        mask["stage%d" % (4 - s)] = mpyr[at:at + B * hs * ws].view(B, hs, ws)
+        at += B * hs * ws
+    return depth, mask, {"stage%d" % (s + 1): proj[s] for s in range(4)}, dv
+
+
+def prep_area_crop(imgs, ptab, chosen, crop_hw):
+    """``imgs`` uint8 ``[B,V,H0,W0,3]`` -> uint8 ``[B,V,h,w,3]``: the crop window of the INTER_AREA resize to the table's (rw, rh)."""
+    _chk(imgs, "imgs", torch.uint8)
+    if imgs.dim() != 5 or imgs.shape[4] != 3:
+        raise _lib.MvsHipError("prep_area_crop: imgs must be [B,V,H0,W0,3], got %s" % (tuple(imgs.shape),))
+    B, V, H0, W0, _ = imgs.shape
+    _chk_prep_tables(ptab, chosen, B, V)
+    h, w = int(crop_hw[0]), int(crop_hw[1])
+    out = torch.empty(B, V, h, w, 3, device=imgs.device, dtype=torch.uint8)
+    _call("mvs_prep_area_crop", ("prep_area_crop", "bytes", float(B * V * h * w * 3) * 2), _ptr(imgs), _ptr(ptab), _ptr(chosen), B, V, H0, W0, h, w,
+          _ptr(out), _stream())
+    return out
+
+
+def prep_jitter_tail(img, jtab=None, has_contrast=True, want_u8=False):
+    """``img`` uint8 ``[B,V,h,w,3]`` -> ``(imgs fp32 [B,V,3,h,w], lsum uint64-as-int64 [B,V] or None, jittered uint8 or None)``.  ``jtab``
+    int32 ``[B,16]`` (None: ToTensor + Normalize only)."""
+    _chk(img, "img", torch.uint8)
+    if img.dim() != 5 or img.shape[4] != 3:
+        raise _lib.MvsHipError("prep_jitter_tail: img must be [B,V,h,w,3], got %s" % (tuple(img.shape),))
+    B, V, h, w, _ = img.shape
+    augment = jtab is not None
+    if augment:
+        _chk(jtab, "jtab", torch.int32)
+        if tuple(jtab.shape) != (B, PREP_JITTER_INTS):
+            raise _lib.MvsHipError("prep_jitter_tail: jtab must be [%d,%d], got %s" % (B, PREP_JITTER_INTS, tuple(jtab.shape)))
+    dev = img.device
+    lsum = torch.empty(B, V, device=dev, dtype=torch.int64) if augment and has_contrast else None
+    out = torch.empty(B, V, 3, h, w, device=dev)
+    u8 = torch.empty_like(img) if want_u8 else None
+    _call("mvs_prep_jitter_tail", ("prep_jitter_tail", "bytes", float(B * V * h * w * 3) * 5), _ptr(img), _ptr(jtab), B, V, h, w, int(augment),
+          int(bool(has_contrast)), _ptr(lsum), _ptr(out), _ptr(u8), _stream())
+    return out, lsum, u8
+
+
+def prep_eval_resize(src, out_hw, pad_rows=0, want="f32"):
+    """``src`` uint8 ``[V,H0,W0,3]`` -> the 8-bit INTER_LINEAR resize to ``out_hw``: ``want='f32'`` fp32 ``[V,3,H,W]`` after ToTensor +
+    Normalize, ``'u8'`` uint8 ``[V,H,W,3]``, ``'both'`` the pair (u8, f32)."""
+    _chk(src, "src", torch.uint8)
+    if src.dim() != 4 or src.shape[3] != 3 or want not in ("f32", "u8", "both"):
+        raise _lib.MvsHipError("prep_eval_resize: src must be [V,H0,W0,3], got %s (want=%r)" % (tuple(src.shape), want))
+    V, H0, W0, _ = src.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    u8 = torch.empty(V, H, W, 3, device=src.device, dtype=torch.uint8) if want != "f32" else None
+    f32 = torch.empty(V, 3, H, W, device=src.device) if want != "u8" else None
+    _call("mvs_prep_eval_resize", ("prep_eval_resize", "bytes", float(V * H * W * 3) * 5), _ptr(src), V, H0, W0, H, W, int(pad_rows), _ptr(u8),
+          _ptr(f32), _stream())
+    return (u8, f32) if want == "both" else (u8 if want == "u8" else f32)

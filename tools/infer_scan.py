@@ -3,13 +3,16 @@
 
     python tools/infer_scan.py --scan SCAN_FOLDER --checkpoint model_best.pth [--config config.json] [--num_view 5] [--numdepth 192]
         [--interval_scale 1.06] [--tmp 5,5,5,1] [--out OUT_FOLDER] [--ply cloud.ply] [--prob_threshold 0.5,0.5,0.5,0.5] [--method pcd]
-        [--gt_depth DIR --gt_mask DIR]
+        [--gt_depth DIR --gt_mask DIR] [--max_h 864 --max_w 1152]
 
 ``SCAN_FOLDER`` holds ``images/%08d.jpg|png``, ``cams/%08d_cam.txt`` and ``pair.txt`` (the layout ``general_eval.py`` reads).  ``--out`` gets
 the files the reference's ``save_depth`` writes (``depth_est/``, ``confidence/``, ``cams/``, ``images/``: ``tools/fuse_scan.py`` and the
-reference's own filter step consume them); ``--ply`` fuses the scan on the device with no file in between.  Images are used as they are:
-their size must be a multiple of 64 (resize / crop beforehand - datasets are out of scope here), and the intrinsics in the camera files
-must belong to that size.  ``--gt_depth`` / ``--gt_mask`` (with ``--out``): ground truth per reference view, ``DIR/%08d.pfm`` and
+reference's own filter step consume them); ``--ply`` fuses the scan on the device with no file in between.  Without ``--max_h`` /
+``--max_w`` images are used as they are: their size must be a multiple of 64 and the intrinsics in the camera files must belong to that
+size.  With either flag (the other takes the reference's default, 864 / 1152; both multiples of 64) every image goes through
+``scale_mvs_input`` on the device (``mvsformer_amd.sample_prep.prepare_eval_views``: the 8-bit ``INTER_LINEAR`` resize to
+``max_w x max_h``, intrinsics rows 0-1 times ``max_w / w`` and ``max_h / h``), so a 1600x1200 DTU scan is accepted and the written
+``cams/`` carry the scaled intrinsics, as ``test.py`` writes them.  ``--gt_depth`` / ``--gt_mask`` (with ``--out``): ground truth per reference view, ``DIR/%08d.pfm`` and
 ``DIR/%08d.png`` (or DTU's ``depth_map_%04d.pfm`` / ``depth_visual_%04d.png``; a mask pixel is valid above 10, as the reference's loader
 reads it), already at the images' size - ``OUT_FOLDER/depth_metric.txt`` then holds test.py's seven accuracy entries.  Needs the GPU.
 """
@@ -24,7 +27,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mvsformer_amd as m  # noqa: E402
-from mvsformer_amd import data_io, metrics  # noqa: E402
+from mvsformer_amd import data_io, metrics, sample_prep  # noqa: E402
 from mvsformer_amd.scene import IMAGENET_MEAN, IMAGENET_STD  # noqa: E402
 
 DEFAULT_ARGS = dict(fix=True, depth_type="ce", fusion_type="cnn", inverse_depth=True, attn_temp=2.0, base_ch=8, ndepths=[32, 16, 8, 4], feat_chs=[8, 16, 32, 64],
@@ -59,7 +62,15 @@ def load_gt(depth_dir, mask_dir, vid, dev):
     return torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(dev), torch.from_numpy(np.ascontiguousarray(mask)).to(dev)
 
 
-def main():
+def scaled_camera(cam_file, src_hw, out_hw):
+    """-> the ``[2,4,4]`` camera of ``cam_file`` for an image of ``src_hw`` resized to ``out_hw`` (None: as it is)."""
+    cam = data_io._cam_2x4x4(cam_file)
+    if out_hw is not None:
+        cam[1, :3, :3] = sample_prep.scale_intrinsics(cam[1, :3, :3], src_hw, out_hw)
+    return cam
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--scan", required=True)
     ap.add_argument("--checkpoint", required=True)
@@ -78,11 +89,22 @@ def main():
     ap.add_argument("--extract_batch", type=int, default=4)
     ap.add_argument("--gt_depth", default=None, help="folder of ground-truth depth maps (PFM) at the images' size; with --gt_mask and --out: depth_metric.txt")
     ap.add_argument("--gt_mask", default=None, help="folder of validity masks (PNG, valid above 10)")
-    a = ap.parse_args()
+    ap.add_argument("--max_h", type=int, default=None, help="resize every image to max_w x max_h as scale_mvs_input does (default with --max_w: 864)")
+    ap.add_argument("--max_w", type=int, default=None, help="default with --max_h: 1152")
+    a = ap.parse_args(argv)
+    if a.max_h is not None or a.max_w is not None:
+        a.max_h, a.max_w = a.max_h or 864, a.max_w or 1152
+        if a.max_h % 64 or a.max_w % 64 or a.max_h < 64 or a.max_w < 64:
+            raise SystemExit("--max_h %d --max_w %d: both must be multiples of 64" % (a.max_h, a.max_w))
     if not a.out and not a.ply:
         raise SystemExit("nothing to do: give --out and / or --ply")
     if bool(a.gt_depth) != bool(a.gt_mask) or (a.gt_depth and not a.out):
         raise SystemExit("--gt_depth and --gt_mask go together and need --out (depth_metric.txt is written there)")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("infer_scan.py runs the MI355X path: no GPU")
     dev = torch.device("cuda:0")
@@ -119,12 +141,16 @@ def main():
         if path is None:
             raise SystemExit("no images/{:0>8}.jpg (or .png) in {}".format(v, a.scan))
         img = data_io.read_img(path)
-        if img.shape[0] % 64 or img.shape[1] % 64:
-            raise SystemExit("%s is %dx%d: H and W must be multiples of 64 (resize / crop the scan first)" % (path, img.shape[0], img.shape[1]))
         cam_file = os.path.join(a.scan, "cams/{:0>8}_cam.txt".format(v))
-        x = ((img.astype(np.float32) / 255.0 - mean) / std).transpose(2, 0, 1)
-        si.add_image(v, torch.from_numpy(np.ascontiguousarray(x)).to(dev), torch.from_numpy(data_io._cam_2x4x4(cam_file)).to(dev),
-                     torch.from_numpy(depth_values(cam_file, a.numdepth, a.interval_scale)).to(dev))
+        if a.max_h is not None:
+            x, _ = sample_prep.prepare_eval_views(torch.from_numpy(np.ascontiguousarray(img)).to(dev)[None], None, a.max_h, a.max_w)
+            x, cam = x[0], scaled_camera(cam_file, img.shape[:2], (a.max_h, a.max_w))
+        else:
+            if img.shape[0] % 64 or img.shape[1] % 64:
+                raise SystemExit("%s is %dx%d: H and W must be multiples of 64 (give --max_h / --max_w to resize)" % (path, img.shape[0], img.shape[1]))
+            x = torch.from_numpy(np.ascontiguousarray(((img.astype(np.float32) / 255.0 - mean) / std).transpose(2, 0, 1))).to(dev)
+            cam = data_io._cam_2x4x4(cam_file)
+        si.add_image(v, x, torch.from_numpy(cam).to(dev), torch.from_numpy(depth_values(cam_file, a.numdepth, a.interval_scale)).to(dev))
     si.set_pairs(pairs, num_views=a.num_view)
     th = [float(x) for x in a.prob_threshold.split(",")]
     fusion = m.SceneFusion(a.method, th, combine_conf=a.combine_conf, device="cuda:0") if a.ply else None
