@@ -855,6 +855,39 @@ int mvs_cloud_score(const float* dist, int64_t M, float max_dist, const float* t
                     mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Greedy radius thinning of a cloud (DTU's rule; csrc/cloud_eval.hip).  Visit the points in `order` (a permutation of 0..N-1); a visited
+ * point that has not been removed is KEPT, and a kept point removes every other point at Euclidean distance <= dist (inclusive).  A
+ * non-finite point is never kept and removes nothing.  The kept set is the lexicographically first maximal independent set under `order`
+ * of the graph with an edge per pair within `dist`; it is unique, so the parallel form below gives exactly the sequential result.
+ *
+ * The distance contract: d2 = (dx*dx + dy*dy) + dz*dz in fp32, uncontracted, compared as d2 <= dist2 with dist2 = dist*dist rounded once
+ * to fp32 (one IEEE multiplication of the fp32 `dist`).
+ *
+ * The index is the grid of mvs_cloud_bounds / _grid_keys / _grid_build over the SAME cloud, built WITH sorted_pts, whose cell is large
+ * enough that every pair within `dist` lies in cells that differ by at most 1 per axis.  Cells are computed in fp32, so cell = dist is
+ * not enough: points in cells 2 apart on an axis are only known to be farther apart than (1 - slack) * cell, slack = 2^-22 * 1.01 *
+ * (cells per axis + 4).  The entry reads the grid record and returns MVS_EINVAL unless 0.99999 * (1 - slack) * cell >= dist;
+ * cell = max(1.0001 * dist + extent * 2^-21, extent * 2^-20), extent = the largest axis extent, always passes.
+ *
+ * Rounds: every indexed point has a rank (its place in `order`) and a state UNDECIDED / KEPT / REMOVED, written at most once.  One launch
+ * per round over the list of points still undecided: a point with a KEPT neighbour (within dist) of lower rank becomes REMOVED; one whose
+ * lower-ranked neighbours are all REMOVED (or that has none) becomes KEPT; any other is appended to the next round's list.  A stale read
+ * of a neighbour's state only postpones a decision.  No block waits for another; the lowest-ranked undecided point always decides, so at
+ * most N rounds run.  The host launches MVS_GREEDY_THIN_BATCH rounds, then reads the number of undecided points (one stream
+ * synchronisation per batch; a round whose list is empty exits at once) and repeats while it is not 0.  A working round past N cannot
+ * happen and is reported as MVS_EINVAL instead of looping on.
+ *
+ * mvs_greedy_thin: keep [N] uint8 (1 = kept, original index order; the caller compacts with it), *rounds_host = the rounds that had
+ * work.  An `order` that is no permutation: MVS_EINVAL after the first synchronisation, before any round.  1 <= N <= 2^36.
+ * workspace: mvs_greedy_thin_workspace_bytes(N) bytes, 8-byte aligned.  Plain vector stores and 64-bit integer atomics only.
+ * ------------------------------------------------------------------------------------------------------- */
+#define MVS_GREEDY_THIN_BATCH 4
+int64_t mvs_greedy_thin_workspace_bytes(int64_t N);
+int mvs_greedy_thin(int64_t N, const int64_t* order, const void* grid, float dist, const float* sorted_pts, const int64_t* perm,
+                    const int64_t* cell_keys, const int64_t* cell_start, void* workspace, uint8_t* keep, int64_t* rounds_host,
+                    mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Sample preparation (csrc/sample_prep.hip): what the reference's data-set classes do between a decoded image and the network's input,
  * on the caller's stream, with no host synchronisation.  Everything that changes per sample is read from device tables, so launch
  * geometry depends on the static sizes only and a captured graph replays with new tables.  Every source index is clamped into its image.

@@ -4,7 +4,7 @@ Hand-written HIP kernels behind a C ABI (``include/mvs_hip.h`` -> ``libmvs_hip.s
 reference's own Python interface: ``StageNet`` (alias ``DepthNet``), ``CostRegNet``, ``CostRegNet3D``,
 ``homo_warping_3D_with_mask`` (alias ``homo_warping``), ``depth_regression``, the inverse- and linear-depth schedulers, the depth metrics of ``utils.py``
 (``Thres_metrics``, ``AbsDepthError_metrics``, ``metrics.DeviceAverageMeter``, ``metrics.valid_epoch``), the point-cloud scores
-(``cloud_eval.evaluate``, ``nn_distance``, ``voxel_downsample``), and
+(``cloud_eval.evaluate``, ``nn_distance``, ``voxel_downsample``, ``greedy_thin``), and
 ``install()`` to rebind them inside an unmodified reference checkout.  ``synth`` (pure torch) builds the
 synthetic DTU-shaped inputs used by the tests and ``bench.py``.
 
@@ -17,7 +17,7 @@ __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "Casca
            "schedule_inverse_range", "init_range", "schedule_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
            "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference",
            "metrics", "Thres_metrics", "AbsDepthError_metrics", "depth_metrics", "DeviceAverageMeter", "valid_epoch",
-           "cloud_eval", "nn_distance", "voxel_downsample", "evaluate_cloud"]
+           "cloud_eval", "nn_distance", "voxel_downsample", "greedy_thin", "evaluate_cloud"]
 
 
 def __getattr__(name):
@@ -64,7 +64,7 @@ def __getattr__(name):
     if name == "cloud_eval":
         import importlib
         return importlib.import_module(".cloud_eval", __name__)
-    if name in ("nn_distance", "voxel_downsample"):
+    if name in ("nn_distance", "voxel_downsample", "greedy_thin"):
         from . import cloud_eval
         return getattr(cloud_eval, name)
     if name == "evaluate_cloud":

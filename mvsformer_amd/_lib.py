@@ -173,6 +173,8 @@ SIGNATURES = {
     "mvs_cloud_voxel_downsample_write": (I, [P, L, P, P, P, L, P, P]),
     "mvs_cloud_score_workspace_bytes": (L, [L]),
     "mvs_cloud_score": (I, [P, L, F, P, I, P, P, P]),
+    "mvs_greedy_thin_workspace_bytes": (L, [L]),
+    "mvs_greedy_thin": (I, [L, P, P, F, P, P, P, P, P, P, P, P]),
     "mvs_prep_pyramid_floats": (L, [I, I, I]),
     "mvs_prep_accept": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P]),
     "mvs_prep_geometry": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),

@@ -3,16 +3,19 @@ a reconstructed cloud and a ground-truth cloud (csrc/cloud_eval.hip).  The refer
 site; here the clouds stay where ``SceneFusion.fuse(on_device=True)`` left them.
 
 * :func:`nn_distance`: exact nearest-neighbour distances, capped at ``max_dist``, over a uniform grid of the target.
-* :func:`voxel_downsample`: one point per occupied voxel, the centroid of the voxel's points (the Open3D / T&T rule).  DTU's own 0.2 mm
-  thinning is a greedy pass over a random shuffle and is not reproduced: scores after thinning are comparable to the MATLAB numbers, not
-  equal to them; the distances themselves are exact.
+* :func:`voxel_downsample`: one point per occupied voxel, the centroid of the voxel's points (the Open3D / T&T rule).
+* :func:`greedy_thin`: DTU's own thinning (0.2 mm there) - a greedy pass over a shuffle of the points: a visited point that has not been
+  removed is kept and removes every other point within ``dist``.  The rule is reproduced exactly for a given visiting order; the order is
+  an input (default: a seeded device permutation).  MATLAB's shuffle is not reproduced, so scores after thinning are those of the same
+  protocol under another shuffle, not the MATLAB numbers bit for bit; the distances themselves are exact.
 * :func:`evaluate`: both directions, the means and the shares under every threshold, read back in ONE 256-byte record at the end.
 * :func:`in_box`, :func:`in_volume`, :func:`above_plane`: DTU's bounding-box, observation-mask and above-plane filters as boolean masks
   (elementwise torch code).
 
 Host reads: the scores are one record.  Before that each grid build reads its 32-byte bounds record (``mvs_cloud_grid_keys`` refuses a grid
-of 2^21 cells or more per axis on the host, and the default cell size is derived from the bounds), and a thinning reads its voxel count
-to size its output.  The key sort is ``torch.sort(stable=True)``; everything else is the HIP path, and a CPU tensor is refused.
+of 2^21 cells or more per axis on the host, and the default cell size is derived from the bounds), a voxel thinning reads its voxel count
+to size its output, and a greedy thinning reads its counter of undecided points once per batch of rounds.  The key sort is
+``torch.sort(stable=True)``; everything else is the HIP path, and a CPU tensor is refused.
 
 The default cell (``cell=None``): ``cbrt(V / N)`` with ``V`` the target's bounding-box volume over the axes that have an extent (the square
 or the length itself for a flat or a straight cloud) and ``N`` its finite points - about one point per cell of a filled box, a handful per
@@ -134,6 +137,69 @@ def voxel_downsample(xyz, voxel: float, rgb=None):
     return out, col
 
 
+def thin_cell(bounds: Sequence[float], dist: float) -> float:
+    """The cell edge of a greedy thinning's grid: ``max(dist, extent / 2^20)`` widened by what fp32 cell coordinates can be off by, so that
+    two points within ``dist`` always lie in cells that differ by at most 1 per axis (``mvs_greedy_thin`` checks it; include/mvs_hip.h):
+    ``max(1.0001 * dist + extent * 2^-21, extent * 2^-20)``, ``extent`` = the largest axis extent."""
+    ext = max(float(bounds[3 + a]) - float(bounds[a]) for a in range(3))
+    cell = max(1.0001 * dist + ext * 2.0 ** -21, ext * 2.0 ** -20)
+    return float(np.float32(cell) * np.float32(1.0 + 2.0 ** -20))          # rounded to fp32, never below the rule
+
+
+def _order(order, n: int, seed: int, device) -> torch.Tensor:
+    if order is None:
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(seed))
+        return torch.randperm(n, generator=gen, device=device)
+    if not isinstance(order, torch.Tensor) or order.device != device or order.dtype != torch.int64 or order.shape != (n,):
+        raise MvsHipError("order must be an int64 tensor [%d] on the cloud's device (a permutation of 0..%d)" % (n, n - 1))
+    return order.contiguous()
+
+
+def _greedy(xyz: torch.Tensor, dist: float, order, seed: int):
+    """-> ``(keep bool [N], rounds)``; ``xyz`` is fp32 ``[N,3]`` on the current device."""
+    n = xyz.shape[0]
+    order = _order(order, n, seed, xyz.device)
+    none = torch.zeros(n, dtype=torch.bool, device=xyz.device)
+    if n == 0:
+        return none, 0
+    grid, bounds, n_bad = ops.cloud_bounds(xyz)
+    if n_bad == n:
+        return none, 0                                                     # nothing finite: no index, no round
+    keys = ops.cloud_grid_keys(xyz, thin_cell(bounds, dist), grid, bounds, n_bad)
+    skeys, perm = torch.sort(keys, stable=True)
+    sorted_pts, cell_keys, cell_start = ops.cloud_grid_build(xyz, skeys, perm, grid, True)
+    return ops.greedy_thin(order, grid, dist, sorted_pts, perm, cell_keys, cell_start)       # refuses an order that is no permutation
+
+
+@torch.no_grad()
+def greedy_thin(xyz, dist: float, order=None, seed: int = 0, rgb=None, return_mask: bool = False):
+    """DTU's thinning: visit the points in ``order``; a visited point that has not been removed is kept and removes every other point at
+    distance ``<= dist`` (``(dx*dx + dy*dy) + dz*dz <= dist*dist`` in fp32).  -> the kept points ``[K,3]`` in their original index order
+    (a subset of the input, pairwise farther apart than ``dist``), ``(xyz, rgb)`` with ``rgb [N,3]`` (any dtype: rows are selected, not
+    averaged), and with ``return_mask`` also ``keep`` bool ``[N]`` as the last item.  Non-finite points are never kept and remove nothing.
+
+    ``order``: int64 ``[N]`` on the cloud's device, a permutation of ``0..N-1`` (checked; anything else is refused).  Default:
+    ``torch.randperm(N, generator=<device generator seeded with seed>)`` - the same seed gives the same points.  The shuffle is this
+    function's, not MATLAB's.
+
+    The kept set is the lexicographically first maximal independent set under ``order``; the kernel finds it in rounds (a point decides
+    once every neighbour of lower rank has), which gives exactly what the sequential loop gives.  The keep mask is the kernel's; the
+    compaction is ``torch`` indexing with that mask (``xyz[keep]``), which preserves index order."""
+    xyz = _cloud(xyz, "xyz")
+    dist = _positive(dist, "dist")
+    if rgb is not None and (not isinstance(rgb, torch.Tensor) or not rgb.is_cuda or rgb.shape != xyz.shape):
+        raise MvsHipError("rgb must be a GPU tensor of xyz's shape %s" % (tuple(xyz.shape),))
+    with torch.cuda.device(xyz.device):
+        keep = _greedy(xyz, dist, order, seed)[0]
+        out = [xyz[keep]]
+        if rgb is not None:
+            out.append(rgb[keep])
+    if return_mask:
+        out.append(keep)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def _valid(xyz: torch.Tensor, mask) -> torch.Tensor:
     ok = torch.isfinite(xyz).all(dim=1)
     if mask is not None:
@@ -145,11 +211,13 @@ def _valid(xyz: torch.Tensor, mask) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate(pred_xyz, gt_xyz, max_dist: float, taus: Sequence[float] = (), voxel: Optional[float] = None, pred_mask=None, gt_mask=None,
-             cell: Optional[float] = None) -> Dict[str, object]:
+             cell: Optional[float] = None, greedy: Optional[float] = None, greedy_seed: int = 0, greedy_order=None) -> Dict[str, object]:
     """Scores of ``pred_xyz [M,3]`` against ``gt_xyz [N,3]`` (device tensors; ``SceneFusion.fuse(on_device=True)['xyz']`` as it is):
 
     * ``n_pred``, ``n_gt``: points after the masks (boolean ``[M]`` / ``[N]``; non-finite points are dropped too) and the thinning
-      (``voxel``: :func:`voxel_downsample` of both clouds first);
+      (``voxel``: :func:`voxel_downsample` of both clouds first; or ``greedy``: :func:`greedy_thin` with that radius of the PREDICTION
+      only, as DTU does - its ground truth is sampled already - in the order ``greedy_order`` ``[M]`` or a shuffle seeded with
+      ``greedy_seed``; a masked-out point is never kept and removes nothing; ``voxel`` and ``greedy`` together are refused);
     * ``accuracy``: the mean of the pred -> gt distances that are ``< max_dist`` (DTU: ``d[d < max_dist].mean()``), ``completeness``: the
       same for gt -> pred, ``overall``: their mean; ``pred_below_max`` / ``gt_below_max``: how many distances those means are over;
     * per ``tau`` (``taus``, each ``<= max_dist``; lists in that order): ``precision`` = the share of pred points closer than ``tau`` to the
@@ -172,6 +240,9 @@ def evaluate(pred_xyz, gt_xyz, max_dist: float, taus: Sequence[float] = (), voxe
     if cell is not None and max_dist / cell > ops.CLOUD_MAX_SHELLS:
         raise MvsHipError("max_dist / cell = %g: at most %d shells are walked" % (max_dist / cell, ops.CLOUD_MAX_SHELLS))
     voxel = None if voxel is None else _positive(voxel, "voxel")
+    greedy = None if greedy is None else _positive(greedy, "greedy")
+    if voxel is not None and greedy is not None:
+        raise MvsHipError("voxel and greedy are two thinning rules: pass one of them")
     nan = float("nan")
     with torch.cuda.device(pred.device):
         clouds = []
@@ -181,6 +252,9 @@ def evaluate(pred_xyz, gt_xyz, max_dist: float, taus: Sequence[float] = (), voxe
             if voxel is not None:
                 xyz = _thin(xyz, voxel)[0]
                 ok = torch.ones(xyz.shape[0], dtype=torch.bool, device=xyz.device)
+            elif greedy is not None and not clouds:                        # the prediction only; its dropped points are non-finite by now
+                ok = _greedy(xyz, greedy, greedy_order, greedy_seed)[0]
+                xyz = torch.where(ok[:, None], xyz, torch.full((), nan, dtype=torch.float32, device=xyz.device))
             clouds.append((xyz, ok))
         rec = torch.zeros(2, ops.CLOUD_SCORE_RECORD_BYTES // 8, dtype=torch.int64, device=pred.device)
         for i, ((src, ok), (dst, _)) in enumerate((clouds, clouds[::-1])):

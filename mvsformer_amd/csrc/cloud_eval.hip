@@ -17,6 +17,8 @@
 //   5. mvs_cloud_voxel_*:     the same table with cell = voxel: one lane per occupied voxel adds its points in double in original order.
 //   6. mvs_cloud_score:       counts below max_dist and below each tau (ballot + popcount, 64-bit integer atomics), the distances below
 //                             max_dist added in double per block, the block sums added in a fixed order by a second launch.
+//   7. mvs_greedy_thin:       DTU's thinning over the same table with cell >= dist (neighbours lie in the 3 x 3 x 3 cells around a point):
+//                             rounds over the points still undecided, one launch each; the host reads a counter per batch of rounds.
 // No float atomics, no block waits on another block, every phase is its own launch on one stream.
 //
 // Exactness of the search.  The cell of a point is computed in fp32, so a cell is not an exact box: with u = fl(fl(x - origin) / cell)
@@ -432,10 +434,191 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_score_final_kernel(const dou
     }
 }
 
+// --------------------------------------------------------------------------------------------------- greedy thinning
+// DTU's rule (include/mvs_hip.h): the lexicographically first maximal independent set under the visiting order, found in rounds.  All
+// per-point arrays are in CELL order (position j of the sorted index), so a neighbour scan reads consecutive points, ranks and states.
+constexpr int TH_BATCH = MVS_GREEDY_THIN_BATCH;
+constexpr int TH_UNDECIDED = 0, TH_KEPT = 1, TH_REMOVED = 2;
+
+// the head of the workspace (128 bytes)
+struct ThinRec {
+    long long bad_order;                  // entries of `order` out of range or repeated
+    long long rounds;                     // rounds that had work
+    long long reserved[2];
+    long long counts[TH_BATCH + 1];       // counts[i]: the length of the list round i of the current batch reads; round i adds to counts[i + 1]
+    long long pad[16 - 4 - (TH_BATCH + 1)];
+};
+static_assert(sizeof(ThinRec) == 128, "ThinRec layout");
+
+// inv[order[i]] = i; inv starts as all ones.  N entries into N slots: in range and never twice <=> a permutation
+__global__ __launch_bounds__(CE_THREADS) void thin_rank_kernel(const long long* __restrict__ order, long long N, long long* __restrict__ inv,
+                                                               ThinRec* __restrict__ rec) {
+    const long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (i >= N) return;
+    const long long o = order[i];
+    bool bad = o < 0 || o >= N;
+    if (!bad) bad = atomicCAS(reinterpret_cast<unsigned long long*>(&inv[o]), ~0ull, (unsigned long long)i) != ~0ull;
+    if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(&rec->bad_order), 1ull);
+}
+
+__global__ __launch_bounds__(CE_THREADS) void thin_init_kernel(const long long* __restrict__ perm, long long N, const CloudGrid* __restrict__ g,
+                                                               const long long* __restrict__ inv, long long* __restrict__ srank,
+                                                               int* __restrict__ sstate, long long* __restrict__ list, ThinRec* __restrict__ rec) {
+    const long long j = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    const long long n_valid = min(g->n_valid, N);
+    if (j == 0) rec->counts[0] = n_valid;                                   // every indexed point starts undecided
+    if (j >= n_valid) return;
+    const long long src = perm[j];
+    srank[j] = (src >= 0 && src < N) ? inv[src] : -1;
+    sstate[j] = TH_UNDECIDED;
+    list[j] = j;
+}
+
+// the neighbours of point j (rank r) in the cells x0..x1 of row (y, z): true as soon as one of lower rank within dist is KEPT; `pending`
+// when one of them is still UNDECIDED.  States are read with relaxed atomic loads: another block may write them during this launch, and
+// any value read - old or new - is safe (a state is written once and is final).
+__device__ __forceinline__ bool thin_row(int x0, int x1, int y, int z, const CloudGrid& g, long long n_cells, const long long* __restrict__ cell_keys,
+                                         const long long* __restrict__ cell_start, const float* __restrict__ spts,
+                                         const long long* __restrict__ srank, int* sstate, long long j, long long r, float qx, float qy,
+                                         float qz, float dist2, bool& pending) {
+    if (y < 0 || y >= g.ncell[1] || z < 0 || z >= g.ncell[2]) return false;
+    x0 = max(x0, 0);
+    x1 = min(x1, g.ncell[0] - 1);
+    if (x0 > x1) return false;
+    const long long a = lower_bound(cell_keys, 0, n_cells, make_key(x0, y, z));
+    if (a >= n_cells) return false;
+    const long long e = lower_bound(cell_keys, a, min(n_cells, a + (long long)(x1 - x0 + 1)), make_key(x1, y, z) + 1);
+    if (e <= a) return false;
+    const long long k0 = cell_start[a], k1 = min(cell_start[e], g.n_valid);
+    for (long long k = k0; k < k1; ++k) {
+        const float dx = qx - spts[3 * k], dy = qy - spts[3 * k + 1], dz = qz - spts[3 * k + 2];
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 <= dist2 && k != j && srank[k] < r) {
+            const int s = __hip_atomic_load(&sstate[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (s == TH_KEPT) return true;
+            pending |= s == TH_UNDECIDED;
+        }
+    }
+    return false;
+}
+
+// one round: lane t takes entry t of the list of undecided points; what stays undecided is appended to the next list (one 64-bit atomic
+// per wavefront; the order of that list does not matter).  Blocks past the end of the list leave at once.
+__global__ __launch_bounds__(CE_THREADS) void thin_round_kernel(const CloudGrid* __restrict__ gp, const float* __restrict__ spts,
+                                                                const long long* __restrict__ srank, int* sstate,
+                                                                const long long* __restrict__ cell_keys, const long long* __restrict__ cell_start,
+                                                                float dist2, const long long* __restrict__ list_in, long long* __restrict__ list_out,
+                                                                long long cap, ThinRec* rec, int round) {
+    const long long n_in = min(rec->counts[round], cap);                    // written by earlier launches only
+    const long long t = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if ((long long)blockIdx.x * CE_THREADS >= n_in) return;                 // the whole block: nothing undecided here
+    if (t == 0) rec->rounds += 1;
+    const CloudGrid g = *gp;
+    bool stay = false;
+    long long j = -1;
+    if (t < n_in) {
+        j = list_in[t];
+        if (j >= 0 && j < g.n_valid && j < cap) {
+            const float qx = spts[3 * j], qy = spts[3 * j + 1], qz = spts[3 * j + 2];
+            const long long r = srank[j];
+            // the point's own cell, by the operations (and the clamp) that made its key
+            const int cx = min(max((int)cell_coord(qx, g.origin[0], g.cell), 0), g.ncell[0] - 1);
+            const int cy = min(max((int)cell_coord(qy, g.origin[1], g.cell), 0), g.ncell[1] - 1);
+            const int cz = min(max((int)cell_coord(qz, g.origin[2], g.cell), 0), g.ncell[2] - 1);
+            bool removed = false, pending = false;
+            for (int dz = -1; dz <= 1 && !removed; ++dz)
+                for (int dy = -1; dy <= 1 && !removed; ++dy)
+                    removed = thin_row(cx - 1, cx + 1, cy + dy, cz + dz, g, g.n_cells, cell_keys, cell_start, spts, srank, sstate, j, r, qx, qy, qz,
+                                       dist2, pending);
+            if (removed) __hip_atomic_store(&sstate[j], TH_REMOVED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (!pending) __hip_atomic_store(&sstate[j], TH_KEPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else stay = true;
+        }
+    }
+    const unsigned long long b = __ballot(stay);
+    if (b == 0) return;                                                     // uniform over the wavefront
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)b) - 1;
+    const uint32_t place = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    long long base = 0;
+    if (lane == leader) base = (long long)atomicAdd(reinterpret_cast<unsigned long long*>(&rec->counts[round + 1]), (unsigned long long)__popcll(b));
+    base = __shfl(base, leader, 64);
+    if (stay && base + place < cap) list_out[base + place] = j;            // at most n_in <= cap entries are ever appended
+}
+
+__global__ __launch_bounds__(CE_THREADS) void thin_keep_kernel(const long long* __restrict__ perm, long long N, const CloudGrid* __restrict__ g,
+                                                               const int* __restrict__ sstate, uint8_t* __restrict__ keep) {
+    const long long j = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (j >= N || j >= g->n_valid) return;
+    const long long src = perm[j];
+    if (src >= 0 && src < N) keep[src] = sstate[j] == TH_KEPT ? 1 : 0;
+}
+
 inline unsigned blocks_for(long long n, int per) { return (unsigned)mvs::ceil_div(n, (long long)per); }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace
+
+extern "C" int64_t mvs_greedy_thin_workspace_bytes(int64_t N) {
+    if (N < 1 || N > CE_MAX_POINTS) return -1;
+    return (int64_t)(sizeof(ThinRec) + 4 * 8 * N + 8 * mvs::ceil_div((long long)N, 2LL));      // record, inv / srank / two lists, states
+}
+
+extern "C" int mvs_greedy_thin(int64_t N, const int64_t* order, const void* grid, float dist, const float* sorted_pts, const int64_t* perm,
+                               const int64_t* cell_keys, const int64_t* cell_start, void* workspace, uint8_t* keep, int64_t* rounds_host,
+                               mvs_stream_t stream) {
+    MVS_REQUIRE(order && grid && sorted_pts && perm && cell_keys && cell_start && workspace && keep && rounds_host, "mvs_greedy_thin: null pointer");
+    MVS_REQUIRE(N >= 1 && N <= CE_MAX_POINTS, "mvs_greedy_thin: N=%lld points, 1..2^36 are taken (an empty cloud needs no launch)", (long long)N);
+    MVS_REQUIRE(isfinite(dist) && dist > 0.0f, "mvs_greedy_thin: dist=%g must be positive and finite", (double)dist);
+    MVS_REQUIRE(aligned8(order) && aligned8(grid) && aligned8(perm) && aligned8(cell_keys) && aligned8(cell_start) && aligned8(workspace),
+                "mvs_greedy_thin: 64-bit arrays must be 8-byte aligned");
+    hipStream_t s = MVS_STREAM(stream);
+    const long long n = (long long)N;
+    ThinRec* rec = reinterpret_cast<ThinRec*>(workspace);
+    long long* inv = reinterpret_cast<long long*>(rec + 1);
+    long long* srank = inv + n;
+    long long* lists[2] = {srank + n, srank + 2 * n};
+    int* sstate = reinterpret_cast<int*>(srank + 3 * n);
+    const CloudGrid* g = reinterpret_cast<const CloudGrid*>(grid);
+    const long long* pm = reinterpret_cast<const long long*>(perm);
+    const long long* ck = reinterpret_cast<const long long*>(cell_keys);
+    const long long* cs = reinterpret_cast<const long long*>(cell_start);
+    const float dist2 = dist * dist;                                        // rounded once to fp32
+    *rounds_host = 0;
+    if (hipMemsetAsync(rec, 0, sizeof(ThinRec), s) != hipSuccess || hipMemsetAsync(inv, 0xff, 8 * (size_t)n, s) != hipSuccess ||
+        hipMemsetAsync(keep, 0, (size_t)n, s) != hipSuccess)
+        return mvs::finish_launch("mvs_greedy_thin(memset)");
+    const unsigned nb = blocks_for(n, CE_THREADS);
+    hipLaunchKernelGGL(thin_rank_kernel, dim3(nb), dim3(CE_THREADS), 0, s, reinterpret_cast<const long long*>(order), n, inv, rec);
+    hipLaunchKernelGGL(thin_init_kernel, dim3(nb), dim3(CE_THREADS), 0, s, pm, n, g, inv, srank, sstate, lists[0], rec);
+    if (int rc = mvs::finish_launch("mvs_greedy_thin(init)")) return rc;
+    CloudGrid hg;
+    ThinRec h;
+    if (hipMemcpyAsync(&hg, g, sizeof(hg), hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(&h, rec, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return mvs::finish_launch("mvs_greedy_thin(copy)");
+    MVS_REQUIRE(h.bad_order == 0, "mvs_greedy_thin: order is not a permutation of 0..%lld (%lld entries out of range or repeated)", n - 1, h.bad_order);
+    MVS_REQUIRE(hg.n_valid >= 0 && hg.n_valid <= n && hg.n_cells >= 0 && hg.n_cells <= hg.n_valid, "mvs_greedy_thin: the grid does not belong to %lld points", n);
+    const float slack = 2.4082e-7f * (float)(std::max(hg.ncell[0], std::max(hg.ncell[1], hg.ncell[2])) + 4);     // 2^-22 * 1.01, as in the query
+    MVS_REQUIRE(0.99999f * (1.0f - slack) * hg.cell >= dist, "mvs_greedy_thin: cell=%g is too small for dist=%g: neighbours must lie in adjacent cells",
+                (double)hg.cell, (double)dist);
+    long long cur = h.counts[0];
+    int side = 0;
+    while (cur > 0) {
+        MVS_REQUIRE(h.rounds <= n, "mvs_greedy_thin: %lld points still undecided after %lld rounds", cur, h.rounds);
+        if (hipMemsetAsync(&rec->counts[1], 0, 8 * TH_BATCH, s) != hipSuccess) return mvs::finish_launch("mvs_greedy_thin(memset)");
+        for (int i = 0; i < TH_BATCH; ++i, side ^= 1)                      // counts only fall: `cur` bounds every list of the batch
+            hipLaunchKernelGGL(thin_round_kernel, dim3(blocks_for(cur, CE_THREADS)), dim3(CE_THREADS), 0, s, g, sorted_pts, srank, sstate, ck, cs, dist2,
+                               lists[side], lists[side ^ 1], n, rec, i);
+        if (int rc = mvs::finish_launch("mvs_greedy_thin(round)")) return rc;
+        if (hipMemcpyAsync(&rec->counts[0], &rec->counts[TH_BATCH], 8, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(&h, rec, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return mvs::finish_launch("mvs_greedy_thin(copy)");
+        cur = h.counts[0];
+    }
+    hipLaunchKernelGGL(thin_keep_kernel, dim3(nb), dim3(CE_THREADS), 0, s, pm, n, g, sstate, keep);
+    *rounds_host = h.rounds;
+    return mvs::finish_launch("mvs_greedy_thin");
+}
 
 extern "C" int mvs_cloud_bounds(const float* pts, int64_t N, void* grid, float* bounds_host, int64_t* n_nonfinite_host, mvs_stream_t stream) {
     MVS_REQUIRE(pts && grid && bounds_host && n_nonfinite_host, "mvs_cloud_bounds: null pointer");

@@ -1594,6 +1594,26 @@ def cloud_score(dist, max_dist: float, taus=(), record=None) -> torch.Tensor:
     return record
 
 
+GREEDY_THIN_BATCH = 4                                        # MVS_GREEDY_THIN_BATCH
+
+
+def greedy_thin(order, grid, dist: float, sorted_pts, perm, cell_keys, cell_start):
+    """DTU's greedy thinning over a built grid (see include/mvs_hip.h): ``order [N]`` int64, a permutation (checked on the device) ->
+    ``(keep [N] bool in original index order, rounds that had work)``.  One host synchronisation per ``GREEDY_THIN_BATCH`` rounds."""
+    _chk(order, "order", torch.int64), _chk_cloud(sorted_pts, "sorted_pts"), _chk(grid, "grid", torch.int64)
+    for t, name in ((perm, "perm"), (cell_keys, "cell_keys"), (cell_start, "cell_start")):
+        _chk(t, name, torch.int64)
+    n = sorted_pts.shape[0]
+    if order.shape != (n,) or perm.shape != (n,) or cell_keys.shape != (n,) or cell_start.shape != (n + 1,):
+        raise _lib.MvsHipError("greedy_thin: order and the index arrays do not belong to %d points" % n)
+    ws = torch.empty(_lib.load().mvs_greedy_thin_workspace_bytes(n) // 8, device=order.device, dtype=torch.int64)
+    keep = torch.empty(n, device=order.device, dtype=torch.uint8)
+    rounds = ctypes.c_int64(0)
+    _call("mvs_greedy_thin", "cloud_greedy_thin", n, _ptr(order), _ptr(grid), float(dist), _ptr(sorted_pts), _ptr(perm), _ptr(cell_keys),
+          _ptr(cell_start), _ptr(ws), _ptr(keep), ctypes.addressof(rounds), _stream())
+    return keep.view(torch.bool), int(rounds.value)
+
+
 def bf16_embed_ch0(x: torch.Tensor) -> torch.Tensor:
     """fp32 ``[...]`` -> bf16 ``[..., 8]`` with the value in channel 0, zeros elsewhere (one launch instead of a fill and a strided copy)."""
     _chk(x, "x")

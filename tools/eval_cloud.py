@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Score a reconstructed point cloud against a ground-truth cloud on the MI355X (needs the GPU):
 
-    python tools/eval_cloud.py --pred fused.ply --gt stl.ply --max_dist 20 --tau 1,2 [--voxel 0.2] \\
+    python tools/eval_cloud.py --pred fused.ply --gt stl.ply --max_dist 20 --tau 1,2 [--voxel 0.2 | --thin-dist 0.2 [--thin-seed 0]] \\
         [--box x0,y0,z0,x1,y1,z1] [--plane a,b,c,d] --out scores.json
 
 Both files are read with ``data_io.read_ply`` (the layout ``write_ply`` / ``fuse_scan`` write).  ``--box`` keeps the points of BOTH clouds
 inside the box, ``--plane`` those with ``a x + b y + c z + d > 0`` (DTU's bounding box and table plane).  The scores are
 ``mvsformer_amd.cloud_eval.evaluate``'s: accuracy / completeness / overall (DTU: means of the distances below ``--max_dist``) and, per
-``--tau``, precision / recall / F-score (Tanks and Temples).  ``--voxel`` thins both clouds to one centroid per voxel first; DTU's own
-0.2 mm thinning is a greedy pass over a random shuffle, so scores after thinning are comparable to the MATLAB numbers, not equal to them.
+``--tau``, precision / recall / F-score (Tanks and Temples).  ``--voxel`` thins both clouds to one centroid per voxel first (the Open3D /
+Tanks-and-Temples rule).  ``--thin-dist`` thins the PREDICTION only by DTU's rule (``cloud_eval.greedy_thin``: a greedy pass over a shuffle
+of the points; a kept point removes every other point within the distance), after the box and the plane; the shuffle is a device
+permutation seeded with ``--thin-seed``, not MATLAB's, so the scores are those of DTU's protocol under another shuffle.
 """
 import argparse
 import json
@@ -35,7 +37,10 @@ def main(argv=None):
     ap.add_argument("--gt", required=True)
     ap.add_argument("--max_dist", type=float, required=True)
     ap.add_argument("--tau", type=floats, default=[])
-    ap.add_argument("--voxel", type=float, default=None)
+    thin = ap.add_mutually_exclusive_group()
+    thin.add_argument("--voxel", type=float, default=None)
+    thin.add_argument("--thin-dist", type=float, default=None)
+    ap.add_argument("--thin-seed", type=int, default=0)
     ap.add_argument("--box", type=lambda t: floats(t, 6), default=None)
     ap.add_argument("--plane", type=lambda t: floats(t, 4), default=None)
     ap.add_argument("--out", required=True)
@@ -57,9 +62,10 @@ def main(argv=None):
         clouds.append(xyz)
         masks.append(mask)
     t1 = time.perf_counter()
-    scores = cloud_eval.evaluate(clouds[0], clouds[1], a.max_dist, a.tau, voxel=a.voxel, pred_mask=masks[0], gt_mask=masks[1])
+    scores = cloud_eval.evaluate(clouds[0], clouds[1], a.max_dist, a.tau, voxel=a.voxel, pred_mask=masks[0], gt_mask=masks[1],
+                                 greedy=a.thin_dist, greedy_seed=a.thin_seed)
     t2 = time.perf_counter()
-    scores.update(pred=a.pred, gt=a.gt, max_dist=a.max_dist, voxel=a.voxel, box=a.box, plane=a.plane, points_read=[int(c.shape[0]) for c in clouds],
+    scores.update(pred=a.pred, gt=a.gt, max_dist=a.max_dist, voxel=a.voxel, thin_dist=a.thin_dist, thin_seed=a.thin_seed, box=a.box, plane=a.plane, points_read=[int(c.shape[0]) for c in clouds],
                   seconds=dict(read=t1 - t0, evaluate=t2 - t1))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
