@@ -888,6 +888,41 @@ int mvs_greedy_thin(int64_t N, const int64_t* order, const void* grid, float dis
                     mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Cloud alignment (csrc/cloud_align.hip): what the Tanks-and-Temples protocol does between a fused cloud and the distances - a similarity
+ * transform, the crop volume, and the reduction of one iteration of point-to-point ICP with a scale factor.  Clouds are dense fp32 [N][3]
+ * in DEVICE memory, sizes 64-bit (0 <= N <= 2^36; an empty cloud launches nothing).  Matrices, polygons and origins are HOST doubles.
+ *
+ * mvs_align_transform     out[i][r] = round_fp32(((R[r][0] * x + R[r][1] * y) + R[r][2] * z) + t[r]) with every operation in fp64, in this
+ *                         order, uncontracted.  srt_host[12]: the 3 x 3 matrix (scale times rotation) row-major, then t.  A non-finite
+ *                         coordinate passes through as the arithmetic leaves it.  out may not alias pts partially (the same pointer is fine).
+ * mvs_align_crop_polygon  mask [N] uint8: Open3D's SelectionPolygonVolume test AS RESTATED HERE (Open3D itself was not available to compare
+ *                         with).  axis 0 / 1 / 2 = X / Y / Z is the orthogonal axis; the other two are (u, v) = (Y, Z) / (X, Z) / (X, Y).
+ *                         polygon_host [K][2] = (u, v) per vertex, 3 <= K <= MVS_ALIGN_CROP_MAX_K (more: MVS_EINVAL).  A point is kept iff
+ *                         axis_min <= p[axis] <= axis_max and the even-odd rule says inside: over consecutive vertices a, b (the ring
+ *                         closes; the edge (last, first) is taken first), toggle when (a.v > v) != (b.v > v) and
+ *                         u < ((b.u - a.u) * (v - a.v)) / (b.v - a.v) + a.u.  All in fp64 from the fp32 coordinates, in this order.  A point
+ *                         with a non-finite coordinate is out.
+ * mvs_align_pair_sums     over the pairs (src[i], dst[idx[i]]) with 0 <= idx[i] < N (idx, dist [M] as mvs_cloud_nn_query returns them; an
+ *                         index outside that range is no pair and is never dereferenced), with p = src[i] - origin and q = dst[idx[i]] -
+ *                         origin formed in fp64: record (MVS_ALIGN_PAIR_RECORD_BYTES, 8-byte aligned, device) = int64 n pairs, int64 rows of
+ *                         src with three finite coordinates, then 18 doubles: sum p [3], sum q [3], sum q p^T [3][3] (row = q's axis),
+ *                         sum |p|^2, sum |q|^2, sum dist^2 (dist widened to fp64 first), then 32 bytes of zeros.  Order of the additions:
+ *                         a lane adds its grid-stride points in index order; min(ceil(M / 256), MVS_ALIGN_PAIR_MAX_ROWS) blocks of 256
+ *                         lanes; the wavefront's shuffle tree; (w0 + w1) + (w2 + w3); a second single-block launch adds the block rows in
+ *                         index order within 8 contiguous chunks and the chunks in order.  No atomics: the record depends on the input
+ *                         alone.  workspace: mvs_align_pair_sums_workspace_bytes(M), 8-byte aligned.
+ * ------------------------------------------------------------------------------------------------------- */
+#define MVS_ALIGN_CROP_MAX_K 64
+#define MVS_ALIGN_PAIR_RECORD_BYTES 192
+#define MVS_ALIGN_PAIR_MAX_ROWS 1024
+int mvs_align_transform(const float* pts, int64_t N, const double* srt_host, float* out, mvs_stream_t stream);
+int mvs_align_crop_polygon(const float* pts, int64_t N, int axis, double axis_min, double axis_max, const double* polygon_host, int K,
+                           uint8_t* mask, mvs_stream_t stream);
+int64_t mvs_align_pair_sums_workspace_bytes(int64_t M);
+int mvs_align_pair_sums(const float* src, int64_t M, const float* dst, int64_t N, const int64_t* idx, const float* dist,
+                        const double* origin_host, void* workspace, void* record, mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Sample preparation (csrc/sample_prep.hip): what the reference's data-set classes do between a decoded image and the network's input,
  * on the caller's stream, with no host synchronisation.  Everything that changes per sample is read from device tables, so launch
  * geometry depends on the static sizes only and a captured graph replays with new tables.  Every source index is clamped into its image.

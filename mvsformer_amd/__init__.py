@@ -17,7 +17,7 @@ __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "Casca
            "schedule_inverse_range", "init_range", "schedule_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
            "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference",
            "metrics", "Thres_metrics", "AbsDepthError_metrics", "depth_metrics", "DeviceAverageMeter", "valid_epoch",
-           "cloud_eval", "nn_distance", "voxel_downsample", "greedy_thin", "evaluate_cloud"]
+           "cloud_eval", "nn_distance", "voxel_downsample", "greedy_thin", "evaluate_cloud", "icp", "evaluate_tt"]
 
 
 def __getattr__(name):
@@ -64,7 +64,7 @@ def __getattr__(name):
     if name == "cloud_eval":
         import importlib
         return importlib.import_module(".cloud_eval", __name__)
-    if name in ("nn_distance", "voxel_downsample", "greedy_thin"):
+    if name in ("nn_distance", "voxel_downsample", "greedy_thin", "icp", "evaluate_tt"):
         from . import cloud_eval
         return getattr(cloud_eval, name)
     if name == "evaluate_cloud":

@@ -175,6 +175,10 @@ SIGNATURES = {
     "mvs_cloud_score": (I, [P, L, F, P, I, P, P, P]),
     "mvs_greedy_thin_workspace_bytes": (L, [L]),
     "mvs_greedy_thin": (I, [L, P, P, F, P, P, P, P, P, P, P, P]),
+    "mvs_align_transform": (I, [P, L, P, P, P]),
+    "mvs_align_crop_polygon": (I, [P, L, I, Dbl, Dbl, P, I, P, P]),
+    "mvs_align_pair_sums_workspace_bytes": (L, [L]),
+    "mvs_align_pair_sums": (I, [P, L, P, L, P, P, P, P, P, P]),
     "mvs_prep_pyramid_floats": (L, [I, I, I]),
     "mvs_prep_accept": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P]),
     "mvs_prep_geometry": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P]),

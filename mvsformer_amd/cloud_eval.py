@@ -9,6 +9,9 @@ site; here the clouds stay where ``SceneFusion.fuse(on_device=True)`` left them.
   an input (default: a seeded device permutation).  MATLAB's shuffle is not reproduced, so scores after thinning are those of the same
   protocol under another shuffle, not the MATLAB numbers bit for bit; the distances themselves are exact.
 * :func:`evaluate`: both directions, the means and the shares under every threshold, read back in ONE 256-byte record at the end.
+* :func:`transform`, :func:`crop_polygon`, :func:`icp`, :func:`register_tt`, :func:`evaluate_tt`: what Tanks and Temples does before the
+  distances - bring the reconstruction into the scanner's frame, refine that by point-to-point ICP with a scale factor, cut both clouds to
+  the crop volume (csrc/cloud_align.hip; one 192-byte record read per ICP iteration).
 * :func:`in_box`, :func:`in_volume`, :func:`above_plane`: DTU's bounding-box, observation-mask and above-plane filters as boolean masks
   (elementwise torch code).
 
@@ -274,6 +277,233 @@ def evaluate(pred_xyz, gt_xyz, max_dist: float, taus: Sequence[float] = (), voxe
     out.update(n_pred=n_pred, n_gt=n_gt, accuracy=acc, completeness=comp, overall=0.5 * (acc + comp), pred_below_max=pb, gt_below_max=gb,
                taus=taus, precision=prec, recall=rcl, pred_below_tau=pc, gt_below_tau=gc,
                fscore=[(2.0 * p * r / (p + r) if p + r > 0.0 else 0.0) if p == p and r == r else nan for p, r in zip(prec, rcl)])
+    return out
+
+
+# ------------------------------------------------------------------------- alignment: Tanks and Temples (csrc/cloud_align.hip)
+# The T&T toolbox brings a reconstruction into the scanner's frame with a given 4 x 4 matrix, refines it by point-to-point ICP with a scale
+# factor on three progressively finer down-samples, cuts both clouds to the scene's crop volume and only then measures distances.  It does
+# so with Open3D on the host.  Neither Open3D nor the toolbox was available to compare with: the crop rule is the one written out in
+# include/mvs_hip.h (UNVERIFIED against Open3D's SelectionPolygonVolume), and the default stages of register_tt are recalled, not checked
+# (UNVERIFIED against the toolbox) - which is why they are arguments.  The toolbox's trajectory-based initial alignment is not here: the
+# initial transform is an input.
+_AXES = {"X": 0, "Y": 1, "Z": 2, 0: 0, 1: 1, 2: 2}
+
+
+def _matrix(T, name: str = "T") -> np.ndarray:
+    try:
+        T = np.array(T, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise MvsHipError("%s must be a 4x4 matrix of numbers" % name)
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise MvsHipError("%s must be a finite 4x4 matrix, got shape %s" % (name, T.shape))
+    if not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+        raise MvsHipError("%s: the last row must be 0 0 0 1, got %s" % (name, T[3].tolist()))
+    return T
+
+
+@torch.no_grad()
+def transform(xyz, T) -> torch.Tensor:
+    """``xyz [N,3]`` moved by the 4 x 4 ``T`` (numpy float64 or nested lists; last row ``0 0 0 1``): per coordinate
+    ``(r0 x + r1 y) + r2 z + t`` in fp64, in this order, rounded to fp32 once.  Non-finite points pass through as the arithmetic leaves
+    them."""
+    xyz = _cloud(xyz, "xyz")
+    T = _matrix(T)
+    with torch.cuda.device(xyz.device):
+        return ops.align_transform(xyz, list(T[:3, :3].reshape(-1)) + list(T[:3, 3]))
+
+
+@torch.no_grad()
+def crop_polygon(xyz, axis, axis_min: float, axis_max: float, polygon) -> torch.Tensor:
+    """The test of Open3D's ``SelectionPolygonVolume`` as restated in include/mvs_hip.h (parity with Open3D itself is unverified: it was not
+    available) -> bool ``[N]``.  ``axis``: the orthogonal axis, ``"X" / "Y" / "Z"`` or ``0 / 1 / 2``; the polygon lives in the plane of the
+    other two, ``(u, v)`` = (Y, Z) / (X, Z) / (X, Y).  A point is kept iff ``axis_min <= p[axis] <= axis_max`` and the even-odd crossing
+    rule over the ring of vertices says inside, all in fp64 from the fp32 coordinates; a non-finite point is out.  ``polygon``: ``[K,3]``
+    (the orthogonal coordinate is ignored, as in the T&T json files) or ``[K,2]`` = ``(u, v)``; ``3 <= K <= 64``."""
+    xyz = _cloud(xyz, "xyz")
+    if axis not in _AXES:
+        raise MvsHipError("axis=%r: 'X', 'Y', 'Z' or 0, 1, 2" % (axis,))
+    axis = _AXES[axis]
+    poly = np.array(polygon, dtype=np.float64)
+    if poly.ndim != 2 or poly.shape[1] not in (2, 3) or poly.shape[0] < 3:
+        raise MvsHipError("polygon must be [K,3] or [K,2] with K >= 3, got %s" % (poly.shape,))
+    if poly.shape[1] == 3:
+        poly = poly[:, [a for a in range(3) if a != axis]]
+    with torch.cuda.device(xyz.device):
+        return ops.align_crop_polygon(xyz, axis, float(axis_min), float(axis_max), poly.tolist())
+
+
+class PairSums:
+    """The record of ``ops.align_pair_sums`` on the host: ``n`` pairs, ``n_finite`` source points, ``sp``, ``sq`` (3), ``sqp`` (3 x 3, row =
+    q's axis), ``spp``, ``sqq``, ``sdd`` - sums over the pairs of ``p = src - origin``, ``q = dst - origin`` and ``dist^2`` - and the
+    ``origin`` they were taken about."""
+
+    def __init__(self, n, n_finite, sp, sq, sqp, spp, sqq, sdd, origin=(0.0, 0.0, 0.0)):
+        self.n, self.n_finite = int(n), int(n_finite)
+        self.sp, self.sq = np.array(sp, dtype=np.float64).reshape(3), np.array(sq, dtype=np.float64).reshape(3)
+        self.sqp = np.array(sqp, dtype=np.float64).reshape(3, 3)
+        self.spp, self.sqq, self.sdd = float(spp), float(sqq), float(sdd)
+        self.origin = np.array(origin, dtype=np.float64).reshape(3)
+
+    @classmethod
+    def from_record(cls, record: torch.Tensor, origin) -> "PairSums":
+        host = record.cpu()                                                # the one read of an ICP iteration
+        s = host[2:20].view(torch.float64).numpy()
+        return cls(int(host[0]), int(host[1]), s[0:3], s[3:6], s[6:15], s[15], s[16], s[17], origin)
+
+
+def umeyama(record: PairSums, with_scaling: bool = True) -> np.ndarray:
+    """The least-squares similarity ``q ~ c R p + t`` from the sums of the pairs (Umeyama 1991) -> 4 x 4 float64.  Means ``mu_p, mu_q``,
+    covariance ``Sigma = (1/n) sum (q - mu_q)(p - mu_p)^T``, SVD ``Sigma = U D V^T``, ``S = diag(1, 1, sign(det U det V))``,
+    ``R = U S V^T``, ``c = tr(D S) / var_p`` (1 without scaling), ``t = mu_q - c R mu_p``, then the origin is added back.  Fewer than 3
+    pairs, non-finite sums, or a covariance of rank below 2 (all pairs on a line) raise: a NaN matrix is never returned."""
+    n = record.n
+    if n < 3:
+        raise MvsHipError("umeyama: %d pairs, at least 3 are needed" % n)
+    mp, mq = record.sp / n, record.sq / n
+    cov = record.sqp / n - np.outer(mq, mp)
+    var_p = record.spp / n - float(mp @ mp)
+    if not (np.isfinite(cov).all() and math.isfinite(var_p)):
+        raise MvsHipError("umeyama: the sums are not finite")
+    U, D, Vt = np.linalg.svd(cov)
+    if not (var_p > 0.0 and D[0] > 0.0 and D[1] > 1e-12 * D[0]):
+        raise MvsHipError("umeyama: the pairs do not span a plane (singular values %s, var_p %g): the rotation is undetermined" % (D.tolist(), var_p))
+    S = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) > 0.0 else -1.0])
+    R = U @ S @ Vt
+    c = float((D * np.diag(S)).sum()) / var_p if with_scaling else 1.0
+    A = c * R
+    T = np.eye(4)
+    T[:3, :3] = A
+    T[:3, 3] = (mq - A @ mp) + record.origin - A @ record.origin
+    if not np.isfinite(T).all():
+        raise MvsHipError("umeyama: the solution is not finite")
+    return T
+
+
+class IcpResult:
+    """``T`` 4 x 4 float64; ``fitness`` = pairs / finite source points and ``inlier_rmse`` = sqrt(sum dist^2 / pairs) as measured in the
+    last iteration (before its update, unless that iteration found the loop converged and applied none); ``iterations`` = evaluations made
+    (one record read each); ``converged``."""
+
+    def __init__(self, T, fitness, inlier_rmse, iterations, converged):
+        self.T, self.fitness, self.inlier_rmse, self.iterations, self.converged = T, fitness, inlier_rmse, iterations, converged
+
+    def __repr__(self):
+        return "IcpResult(fitness=%r, inlier_rmse=%r, iterations=%d, converged=%r, T=\n%r)" % (
+            self.fitness, self.inlier_rmse, self.iterations, self.converged, self.T)
+
+
+@torch.no_grad()
+def icp(src, dst, threshold: float, init=None, with_scaling: bool = True, max_iter: int = 20, fitness_tol: float = 1e-6,
+        rmse_tol: float = 1e-6, cell: Optional[float] = None) -> IcpResult:
+    """Open3D's point-to-point ICP loop (``TransformationEstimationPointToPoint(with_scaling)``) of ``src [M,3]`` onto ``dst [N,3]``.  The
+    target's grid is built once.  Per iteration: the ORIGINAL source moved by the accumulated fp64 ``T`` (:func:`transform`; roundings do
+    not pile up), the nearest target within ``threshold`` of every point, the pair sums about the target's bounding-box centre, ONE
+    record read, ``fitness`` and ``inlier_rmse``, the update (:func:`umeyama` on the pairs (moved source, target)), ``T = update @ T``.
+    The loop ends before the update when both ``|fitness - previous| < fitness_tol`` and ``|inlier_rmse - previous| < rmse_tol``
+    (absolute differences, as in Open3D despite its "relative" names), or after ``max_iter`` iterations.  No pair at all, or pairs that
+    determine no transform, raise."""
+    src, dst = _cloud(src, "src"), _cloud(dst, "dst")
+    if src.device != dst.device:
+        raise MvsHipError("src is on %s, dst on %s" % (src.device, dst.device))
+    threshold = _positive(threshold, "threshold")
+    T = np.eye(4) if init is None else _matrix(init, "init")
+    max_iter = int(max_iter)
+    if max_iter < 1:
+        raise MvsHipError("max_iter=%d: at least one iteration" % max_iter)
+    if src.shape[0] == 0 or dst.shape[0] == 0:
+        raise MvsHipError("icp: an empty cloud (%d source, %d target points)" % (src.shape[0], dst.shape[0]))
+    cell = None if cell is None else _positive(cell, "cell")
+    if cell is not None and threshold / cell > ops.CLOUD_MAX_SHELLS:
+        raise MvsHipError("threshold / cell = %g: at most %d shells are walked" % (threshold / cell, ops.CLOUD_MAX_SHELLS))
+    with torch.cuda.device(src.device):
+        index = _Index(dst, cell, threshold)
+        if index.n_valid == 0:
+            raise MvsHipError("icp: the target has no finite point")
+        origin = [0.5 * (float(index.bounds[a]) + float(index.bounds[3 + a])) for a in range(3)]
+        record = torch.empty(ops.ALIGN_PAIR_RECORD_BYTES // 8, dtype=torch.int64, device=src.device)
+        prev, fitness, rmse, converged, it = None, 0.0, 0.0, False, 0
+        while it < max_iter:
+            moved = ops.align_transform(src, list(T[:3, :3].reshape(-1)) + list(T[:3, 3]))
+            dist, idx = index.query(moved, threshold)
+            sums = PairSums.from_record(ops.align_pair_sums(moved, dst, idx, dist, origin, record), origin)
+            it += 1
+            if sums.n == 0:
+                raise MvsHipError("icp: no source point has a target within threshold=%g at iteration %d" % (threshold, it))
+            fitness, rmse = sums.n / max(1, sums.n_finite), math.sqrt(sums.sdd / sums.n)
+            if prev is not None and abs(fitness - prev[0]) < fitness_tol and abs(rmse - prev[1]) < rmse_tol:
+                converged = True
+                break
+            prev = (fitness, rmse)
+            T = umeyama(sums, with_scaling) @ T
+    return IcpResult(T, fitness, rmse, it, converged)
+
+
+def default_tt_stages(dtau: float):
+    """``(downsample, threshold, max_iter)`` per stage, as the T&T toolbox's three registrations are RECALLED (the toolbox was not available
+    to check them against, hence an argument of :func:`register_tt`): voxels of ``dtau`` with threshold ``80 dtau``, voxels of ``dtau / 2``
+    with ``20 dtau``, every k-th point up to about 4 M points with ``2 dtau``; 20 iterations each."""
+    return [(("voxel", dtau), 80.0 * dtau, 20), (("voxel", 0.5 * dtau), 20.0 * dtau, 20), (("uniform", 4e6), 2.0 * dtau, 20)]
+
+
+def _crop(xyz: torch.Tensor, crop) -> torch.Tensor:
+    if crop is None:
+        return xyz
+    try:
+        axis, lo, hi, poly = crop["orthogonal_axis"], crop["axis_min"], crop["axis_max"], crop["bounding_polygon"]
+    except (KeyError, TypeError):
+        raise MvsHipError("crop must be None or a mapping with orthogonal_axis, axis_min, axis_max, bounding_polygon (data_io.read_crop_volume)")
+    return xyz[crop_polygon(xyz, axis, lo, hi, poly)]
+
+
+def _downsample(xyz: torch.Tensor, how) -> torch.Tensor:
+    kind, value = how
+    if kind == "voxel":
+        return voxel_downsample(xyz, value)
+    if kind == "uniform":
+        return xyz[::max(1, int(round(xyz.shape[0] / float(value))))] if xyz.shape[0] else xyz
+    raise MvsHipError("downsample %r: ('voxel', size) or ('uniform', max_points)" % (how,))
+
+
+@torch.no_grad()
+def register_tt(pred, gt, init, crop, dtau: float, stages=None):
+    """The registration of the Tanks-and-Temples protocol -> ``(T 4 x 4 float64, [IcpResult per stage])``.  ``init``: the 4 x 4 that brings
+    ``pred`` roughly into ``gt``'s frame (the ``*_trans.txt`` of a training scene); ``crop``: ``data_io.read_crop_volume``'s mapping or
+    None.  A stage is ``(downsample, threshold, max_iter)`` with ``downsample`` = ``("voxel", size)`` (:func:`voxel_downsample`) or
+    ``("uniform", max_points)`` (every k-th point, ``k = max(1, round(N / max_points))``).  Each stage moves ``pred`` by the current
+    ``T``, crops it and ``gt``, down-samples both, runs :func:`icp` from identity with scaling and composes the result into ``T``.
+    ``stages=None``: :func:`default_tt_stages` - recalled, not checked against the toolbox."""
+    pred, gt = _cloud(pred, "pred"), _cloud(gt, "gt")
+    T = _matrix(init, "init")
+    dtau = _positive(dtau, "dtau")
+    stages = default_tt_stages(dtau) if stages is None else list(stages)
+    results = []
+    gt_c = _crop(gt, crop)
+    for how, threshold, max_iter in stages:
+        src = _downsample(_crop(transform(pred, T), crop), how)
+        dst = _downsample(gt_c, how)
+        res = icp(src, dst, threshold, with_scaling=True, max_iter=max_iter)
+        T = res.T @ T
+        results.append(res)
+    return T, results
+
+
+@torch.no_grad()
+def evaluate_tt(pred, gt, init, crop, dtau: float, max_dist: Optional[float] = None, taus: Optional[Sequence[float]] = None, stages=None,
+                refine: bool = True) -> Dict[str, object]:
+    """The Tanks-and-Temples score of ``pred`` against ``gt``: :func:`register_tt` (skipped with ``refine=False``: ``init`` as it is), then
+    ``pred`` moved and cropped, ``gt`` cropped, and :func:`evaluate` with ``voxel = dtau / 2``, ``taus = (dtau,)`` unless given, and
+    ``max_dist`` (default ``5 dtau``; it caps the accuracy / completeness means only).  -> :func:`evaluate`'s dict plus ``T`` (nested
+    lists), ``stages`` (fitness, inlier_rmse, iterations, converged per stage) and ``n_pred_cropped`` / ``n_gt_cropped``."""
+    dtau = _positive(dtau, "dtau")
+    if refine:
+        T, results = register_tt(pred, gt, init, crop, dtau, stages)
+    else:
+        T, results = _matrix(init, "init"), []
+    pred_c, gt_c = _crop(transform(pred, T), crop), _crop(_cloud(gt, "gt"), crop)
+    out = evaluate(pred_c, gt_c, 5.0 * dtau if max_dist is None else max_dist, (dtau,) if taus is None else taus, voxel=0.5 * dtau)
+    out.update(T=T.tolist(), n_pred_cropped=int(pred_c.shape[0]), n_gt_cropped=int(gt_c.shape[0]),
+               stages=[dict(fitness=r.fitness, inlier_rmse=r.inlier_rmse, iterations=r.iterations, converged=r.converged) for r in results])
     return out
 
 

@@ -240,3 +240,42 @@ def read_ply(path) -> Tuple[np.ndarray, np.ndarray]:
     xyz = np.stack([v["x"], v["y"], v["z"]], -1) if n else np.zeros((0, 3), np.float32)
     rgb = np.stack([v["red"], v["green"], v["blue"]], -1) if n else np.zeros((0, 3), np.uint8)
     return xyz.astype(np.float32, copy=False), rgb.astype(np.uint8, copy=False)
+
+
+def read_alignment(path) -> np.ndarray:
+    """The ``*_trans.txt`` of a Tanks-and-Temples training scene: 16 whitespace-separated numbers, a 4 x 4 matrix row by row whose last
+    row is ``0 0 0 1`` -> float64 ``[4,4]``.  Anything else is refused."""
+    with open(path) as f:
+        tokens = f.read().split()
+    try:
+        values = [float(t) for t in tokens]
+    except ValueError:
+        raise ValueError("read_alignment: %s holds something that is not a number" % path)
+    if len(values) != 16:
+        raise ValueError("read_alignment: %s holds %d numbers, a 4x4 matrix has 16" % (path, len(values)))
+    T = np.array(values, dtype=np.float64).reshape(4, 4)
+    if not np.isfinite(T).all() or not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError("read_alignment: %s: the matrix must be finite with the last row 0 0 0 1, got %s" % (path, T[3].tolist()))
+    return T
+
+
+def read_crop_volume(path) -> Dict[str, object]:
+    """Open3D's ``SelectionPolygonVolume`` json (the ``<scene>.json`` of Tanks and Temples) -> ``{"orthogonal_axis": "X" | "Y" | "Z",
+    "axis_min": float, "axis_max": float, "bounding_polygon": float64 [K,3]}``, what ``cloud_eval.crop_polygon`` / ``evaluate_tt`` take.
+    Another ``class_name`` or a missing key is refused."""
+    import json
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or doc.get("class_name") != "SelectionPolygonVolume":
+        raise ValueError("read_crop_volume: %s: class_name must be 'SelectionPolygonVolume', got %r" % (
+            path, doc.get("class_name") if isinstance(doc, dict) else type(doc).__name__))
+    for key in ("orthogonal_axis", "axis_min", "axis_max", "bounding_polygon"):
+        if key not in doc:
+            raise ValueError("read_crop_volume: %s has no %r" % (path, key))
+    axis = str(doc["orthogonal_axis"]).upper()
+    if axis not in ("X", "Y", "Z"):
+        raise ValueError("read_crop_volume: %s: orthogonal_axis must be X, Y or Z, got %r" % (path, doc["orthogonal_axis"]))
+    poly = np.array(doc["bounding_polygon"], dtype=np.float64)
+    if poly.ndim != 2 or poly.shape[1] != 3 or poly.shape[0] < 3 or not np.isfinite(poly).all():
+        raise ValueError("read_crop_volume: %s: bounding_polygon must be K >= 3 finite xyz triples, got shape %s" % (path, poly.shape))
+    return {"orthogonal_axis": axis, "axis_min": float(doc["axis_min"]), "axis_max": float(doc["axis_max"]), "bounding_polygon": poly}

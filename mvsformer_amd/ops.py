@@ -1614,6 +1614,61 @@ def greedy_thin(order, grid, dist: float, sorted_pts, perm, cell_keys, cell_star
     return keep.view(torch.bool), int(rounds.value)
 
 
+# --------------------------------------------------------------------------------------------- cloud alignment (csrc/cloud_align.hip)
+ALIGN_CROP_MAX_K = 64                                        # MVS_ALIGN_CROP_MAX_K
+ALIGN_PAIR_RECORD_BYTES = 192                                # MVS_ALIGN_PAIR_RECORD_BYTES
+ALIGN_PAIR_MAX_ROWS = 1024                                   # MVS_ALIGN_PAIR_MAX_ROWS
+
+
+def align_transform(pts, srt) -> torch.Tensor:
+    """``pts [N,3]`` (N >= 0), ``srt``: 12 host doubles (the 3 x 3 matrix row-major, then t) -> ``[N,3]``, each coordinate evaluated in fp64
+    as ``(r0 x + r1 y) + r2 z + t`` and rounded once."""
+    _chk_cloud(pts, "pts")
+    srt = [float(v) for v in srt]
+    if len(srt) != 12:
+        raise _lib.MvsHipError("align_transform: 12 numbers (3x3 row-major, then t), got %d" % len(srt))
+    n = pts.shape[0]
+    out = torch.empty(n, 3, device=pts.device, dtype=torch.float32)
+    a = (ctypes.c_double * 12)(*srt)
+    _call("mvs_align_transform", ("align_transform", "bytes", 24.0 * n), _ptr(pts) if n else None, n, ctypes.addressof(a), _ptr(out) if n else None,
+          _stream())
+    return out
+
+
+def align_crop_polygon(pts, axis: int, axis_min: float, axis_max: float, polygon_uv) -> torch.Tensor:
+    """``pts [N,3]`` -> bool ``[N]``: the slab ``axis_min <= p[axis] <= axis_max`` and the even-odd rule against ``polygon_uv`` (K pairs of
+    host doubles in the plane of the other two axes; include/mvs_hip.h has the rule)."""
+    _chk_cloud(pts, "pts")
+    uv = [(float(u), float(v)) for u, v in polygon_uv]
+    if len(uv) > ALIGN_CROP_MAX_K:
+        raise _lib.MvsHipError("align_crop_polygon: %d polygon vertices, at most %d are built" % (len(uv), ALIGN_CROP_MAX_K))
+    n = pts.shape[0]
+    mask = torch.empty(n, device=pts.device, dtype=torch.uint8)
+    poly = (ctypes.c_double * max(2, 2 * len(uv)))(*[c for p in uv for c in p])
+    _call("mvs_align_crop_polygon", ("align_crop_polygon", "bytes", 13.0 * n), _ptr(pts) if n else None, n, int(axis), float(axis_min),
+          float(axis_max), ctypes.addressof(poly), len(uv), _ptr(mask) if n else None, _stream())
+    return mask.view(torch.bool)
+
+
+def align_pair_sums(src, dst, idx, dist, origin, record=None) -> torch.Tensor:
+    """The sums of one ICP iteration (include/mvs_hip.h) -> the device record, int64 ``[24]``: pairs, finite rows of ``src``, then (as
+    float64 bits) 18 sums.  ``idx`` / ``dist`` ``[M]`` as ``cloud_nn_query`` returns them.  No host synchronisation."""
+    _chk_cloud(src, "src"), _chk_cloud(dst, "dst"), _chk(idx, "idx", torch.int64), _chk(dist, "dist")
+    m, n = src.shape[0], dst.shape[0]
+    if idx.shape != (m,) or dist.shape != (m,):
+        raise _lib.MvsHipError("align_pair_sums: idx %s and dist %s must be [%d]" % (tuple(idx.shape), tuple(dist.shape), m))
+    if record is None:
+        record = torch.empty(ALIGN_PAIR_RECORD_BYTES // 8, device=src.device, dtype=torch.int64)
+    _chk(record, "record", torch.int64)
+    if record.numel() != ALIGN_PAIR_RECORD_BYTES // 8:
+        raise _lib.MvsHipError("align_pair_sums: the record holds %d int64" % (ALIGN_PAIR_RECORD_BYTES // 8))
+    ws = torch.empty(_lib.load().mvs_align_pair_sums_workspace_bytes(m) // 8, device=src.device, dtype=torch.float64)
+    o = (ctypes.c_double * 3)(*[float(v) for v in origin])
+    _call("mvs_align_pair_sums", ("align_pair_sums", "bytes", 36.0 * m), _ptr(src) if m else None, m, _ptr(dst) if n else None, n,
+          _ptr(idx) if m else None, _ptr(dist) if m else None, ctypes.addressof(o), _ptr(ws), _ptr(record), _stream())
+    return record
+
+
 def bf16_embed_ch0(x: torch.Tensor) -> torch.Tensor:
     """fp32 ``[...]`` -> bf16 ``[..., 8]`` with the value in channel 0, zeros elsewhere (one launch instead of a fill and a strided copy)."""
     _chk(x, "x")
