@@ -739,6 +739,45 @@ int mvs_pointcloud_scatter(const uint8_t* photo_mask, const uint8_t* geo_mask, c
                            uint8_t* records, float* xyz, uint8_t* rgb, mvs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Gipuma-style sequential fusion (the reference's default `--filter_method gipuma`: misc/gipuma.py writes .dmb files and
+ * runs the external CUDA binary `fusibile`), csrc/gipuma.hip.  The binary's source is not part of the reference: the
+ * rule below is RESTATED, every parameter is an argument, and parity with the binary is UNVERIFIED.  It carries no
+ * normals (the reference feeds a constant normal with normal_thresh = 360: the test is vacuous) and a point takes its
+ * reference pixel's colour (fusibile averages the colours).
+ *
+ * All arithmetic below is fp32, every operation rounded on its own in the order written, divisions IEEE.
+ *   depth [Nv,H,W]   what each view contributes; the caller has zeroed the pixels that fail the probability filter.
+ *   Tables, built by the caller in fp64 and rounded once (R_v, t_v = cam[0][:3,:3], cam[0][:3,3]; K_v = cam[1][:3,:3];
+ *   P_s = K_s [R_s | t_s]):
+ *     B [Nv,3,3] = R_v^T K_v^-1        c [Nv,3] = -R_v^T t_v
+ *     A [Nv,Nv,3,3]: A[r][s] = P_s[:, :3] B_r        b [Nv,Nv,3]: b[r][s] = P_s[:, :3] c_r + P_s[:, 3]
+ *     fb [Nv,Nv]: fb[r][s] = K_r[0][0] * |c_r - c_s|   (focal length x baseline; entries with r = s are never read)
+ * Job k = reference view ref_idx[k] against the source views src_idx[k][0 .. n_src[k]) in that order (the job table of
+ * mvs_geo_filter_scene_fwd: DEVICE memory, validated by the caller, src_idx padded to Vmax).  All three NULL (then
+ * R = Nv, Vmax = Nv - 1): job k = view k against every other view, ascending.  One kernel per job, enqueued in job order
+ * on the stream, no host synchronisation.  For the pixel (x, y) of job k, with r its reference view, d = depth[r][y][x]:
+ *   1. eligible iff depth_min < d < depth_max and used[r][y][x] == 0  (job k never writes used[r])
+ *   2. X_i = ((B[r][i][0] x + B[r][i][1] y) + B[r][i][2]) d + c[r][i];   sum = X, n = 0
+ *   3. for each source s, in order; s is consistent iff all of
+ *        q_i = ((A[r][s][i][0] x + A[r][s][i][1] y) + A[r][s][i][2]) d + b[r][s][i],  z = q_2 > 0
+ *        fx = floor(q_0 / z + 0.5), fy = floor(q_1 / z + 0.5),  0 <= fx < W and 0 <= fy < H (as floats: NaN, inf fail)
+ *        d_s = depth[s][fy][fx],  depth_min < d_s < depth_max
+ *        |fb[r][s] / z - fb[r][s] / d_s| < disp_thresh        (strict: NaN is not consistent)
+ *      then sum += X_s (step 2 with B[s], c[s], (fx, fy), d_s) and n += 1
+ *   4. kept iff float(n) >= num_consistent; then point = sum / float(n + 1) and used[s][fy][fx] = 1 for every
+ *      consistent s.
+ * Outputs: used [Nv,H,W] uint8 (zeroed here first), keep [R,H,W] uint8, count [R,H,W] uint8 (may be NULL) = min(n, 255),
+ * 0 where the pixel was not eligible; points [R,3,H,W], 0 where not kept.  keep and points are what mvs_pointcloud_count /
+ * mvs_pointcloud_scatter take as geo_mask / points (photo_mask: all ones, or the probability mask that zeroed depth).
+ * A job whose row is inconsistent (an index outside [0,Nv), a source equal to the reference, n_src outside [1,Vmax])
+ * keeps nothing and marks nothing.  Refused with MVS_EINVAL before anything is enqueued: a NULL pointer other than
+ * count, a job table given in part, Nv < 2, H or W < 1 or > 2^24, R or Vmax that do not fit the table, a NaN threshold. */
+int mvs_gipuma_fuse_scene(const float* depth, const float* B, const float* c, const float* A, const float* b, const float* fb, int Nv,
+                          const int32_t* ref_idx, const int32_t* src_idx, const int32_t* n_src, int R, int Vmax, int H, int W,
+                          float disp_thresh, float num_consistent, float depth_min, float depth_max, uint8_t* used, uint8_t* keep,
+                          uint8_t* count, float* points, mvs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * the classification loss fused with the head's gradient, one stage of ce_loss_stage4
  * (models/losses.py:304-350, focal=False).
  *   logits [B,D,HW] = prob_volume_pre (D >= 2), depth_values [B,D,HW], depth_gt [B,HW], mask [B,HW] (valid where > 0.5)

@@ -232,6 +232,7 @@ SIGNATURES = {
     "mvs_pointcloud_record_offset": (L, [L]),
     "mvs_pointcloud_count": (I, [P, P, P, I, I, I, I, P, P, P, P]),
     "mvs_pointcloud_scatter": (I, [P, P, P, I, I, I, I, P, P, I, P, L, P, P, P, P]),
+    "mvs_gipuma_fuse_scene": (I, [P, P, P, P, P, P, I, P, P, P, I, I, I, I, F, F, F, F, P, P, P, P, P]),
     "mvs_init_inverse_range": (I, [P, I, I, I, I, I, P, P]),
     "mvs_schedule_inverse_range": (I, [P, P, I, F, I, I, I, I, P, P]),
     "mvs_init_range": (I, [P, I, I, I, I, I, P, P]),

@@ -9,6 +9,10 @@ averaged depth, fused world points) in ONE pass over the reference pixels with n
 ``SceneFusion`` / ``fuse_scan`` are the whole of test.py:404-560 (``filter_depth`` / ``dynamic_filter_depth`` /
 ``pcd_filter_worker``): every view of a scan on the device once, all reference views filtered in one launch through a job
 table, the surviving points and colours compacted on the device into the PLY vertex records.
+
+``GipumaFusion`` / ``gipuma_fuse_scan`` stand where the reference's default ``--filter_method gipuma`` (misc/gipuma.py ``gipuma_filter``) shells
+out to the external ``fusibile`` binary: sequential over the reference views, a disparity test against every other view, the consistent
+views' 3-D points averaged (``mvs_gipuma_fuse_scene``; the rule is restated in include/mvs_hip.h, parity with the binary is unverified).
 """
 from __future__ import annotations
 
@@ -258,6 +262,126 @@ def fuse_scan(pair_folder: str, scan_folder: str, plyfilename: str, prob_thresho
     scene = SceneFusion.from_folder(pair_folder, scan_folder, n_src_views, method=method, prob_threshold=prob_threshold,
                                     thres_disp=thres_disp, thres_view=thres_view, dist_base=dist_base, rel_diff_base=rel_diff_base,
                                     combine_conf=combine_conf, device=device)
+    torch.cuda.synchronize(scene.device)
+    t1 = time.perf_counter()
+    out = scene.fuse(want=("records",))
+    t2 = time.perf_counter()
+    data_io.write_ply_records(plyfilename, out["records"], out["n_points"])
+    t3 = time.perf_counter()
+    return dict(n_points=out["n_points"], stats=out["stats"], counts_per_view=out["counts_per_view"],
+                seconds=dict(load=t1 - t0, device=t2 - t1, write=t3 - t2))
+
+
+def gipuma_tables(cams) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The per-view and per-pair tables of ``mvs_gipuma_fuse_scene`` from ``cams [Nv,2,4,4]`` (numpy or tensor), computed in float64 on the
+    host and rounded once to float32: ``B [Nv,3,3] = R^T K^-1``, ``c [Nv,3] = -R^T t``, ``A [Nv,Nv,3,3]`` with ``A[r,s] = P_s[:, :3] B_r``,
+    ``b [Nv,Nv,3]`` with ``b[r,s] = P_s[:, :3] c_r + P_s[:, 3]`` (``P_s = K_s [R_s | t_s]``) and ``fb [Nv,Nv] = K_r[0,0] |c_r - c_s|``."""
+    cams = np.asarray(cams.detach().cpu() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
+    if cams.ndim != 4 or cams.shape[1:] != (2, 4, 4):
+        raise ValueError("gipuma_tables: cams must be [Nv,2,4,4], got %s" % (cams.shape,))
+    R, t, K = cams[:, 0, :3, :3], cams[:, 0, :3, 3], cams[:, 1, :3, :3]
+    Rt = R.transpose(0, 2, 1)
+    B = Rt @ np.linalg.inv(K)
+    c = -(Rt @ t[:, :, None])[:, :, 0]
+    M = K @ R                                                           # P_s[:, :3]
+    p3 = (K @ t[:, :, None])[:, :, 0]                                   # P_s[:, 3]
+    A = np.einsum("sij,rjk->rsik", M, B)
+    b = np.einsum("sij,rj->rsi", M, c) + p3[None]
+    fb = K[:, 0, 0][:, None] * np.linalg.norm(c[:, None] - c[None], axis=-1)
+    return tuple(np.ascontiguousarray(a, dtype=np.float32) for a in (B, c, A, b, fb))
+
+
+class GipumaFusion(SceneFusion):
+    """The scan-resident form of the reference's default filter (``gipuma_filter`` -> ``fusibile``): the surface of ``SceneFusion``
+    (``add_view`` / ``set_pairs`` / ``from_folder`` / ``fuse``, the same return dictionary), the rule of ``mvs_gipuma_fuse_scene``.
+
+    Views are processed in ``pairs`` order, each against its listed sources; ``pairs=None`` (``set_pairs`` never called): ascending view
+    id, each against every other view, as ``gipuma_filter`` walks its sorted file names.  ``prob_threshold`` / ``combine_conf`` zero the
+    depth of the pixels that fail (``probability_filter``, misc/gipuma.py:160-189) before any view is fused.  A point takes the colour
+    of its reference pixel; there are no normals."""
+
+    def __init__(self, prob_threshold: Sequence[float] = (0.5,), disp_threshold: float = 0.2, num_consistent: float = 3,
+                 depth_min: float = 0.001, depth_max: float = 100000.0, combine_conf: bool = False, device: Optional[str] = None):
+        super().__init__("pcd", prob_threshold, combine_conf=combine_conf, device=device)
+        if not depth_min >= 0.0:
+            raise ValueError("depth_min must be >= 0: a pixel zeroed by the probability filter has to stay ineligible")
+        self.method = "gipuma"
+        self.disp_threshold, self.num_consistent, self.depth_min, self.depth_max = disp_threshold, num_consistent, depth_min, depth_max
+
+    def set_pairs(self, pairs) -> None:
+        """``[(ref_id, [src_id, ...])]`` in processing order; ``None``: every view against all others, ascending id."""
+        self.pairs = [] if pairs is None else [(int(r), [int(v) for v in srcs]) for r, srcs in pairs]
+
+    @classmethod
+    def from_folder(cls, pair_folder: str, scan_folder: str, n_src_views: int = 10, **kwargs) -> "GipumaFusion":
+        """Every view of the scan folder that ``pair.txt`` names, in ascending id, each against all others (``n_src_views`` only bounds
+        which views the loader reads; the pair lists themselves are not used)."""
+        from . import data_io
+        scene = data_io.load_scene(pair_folder, scan_folder, n_src_views)
+        self = cls(**kwargs)
+        for i in sorted(range(len(scene["view_ids"])), key=lambda i: scene["view_ids"][i]):
+            self.add_view(scene["view_ids"][i], scene["depths"][i], scene["confs"][i], scene["cams"][i],
+                          None if scene["imgs"] is None else scene["imgs"][i])
+        return self
+
+    def fuse(self, want: Sequence[str] = ("records", "xyz", "rgb"), with_intermediates: bool = False,
+             on_device: bool = False) -> Dict[str, object]:
+        """As ``SceneFusion.fuse``.  ``stats``: ``photo`` = pixels passing the probability filter, ``geo`` = pixels kept by the rule,
+        ``final`` = both (= ``geo``: a filtered pixel has depth 0 and is never eligible).  ``with_intermediates`` adds ``photo_mask
+        [Nv,H,W]``, ``geo_mask [R,H,W]``, ``points_dense [R,3,H,W]``, ``used [Nv,H,W]``, ``count [R,H,W]`` and ``view_ids``."""
+        from ._lib import MvsHipError
+        if len(self.views) < 2:
+            raise ValueError("GipumaFusion.fuse: add_view() at least two views first")
+        ids = list(self.views)
+        index = {v: i for i, v in enumerate(ids)}
+        pairs = self.pairs or [(r, [v for v in sorted(ids) if v != r]) for r in sorted(ids)]
+        for r, srcs in pairs:
+            for v in [r] + srcs:
+                if v not in index:
+                    raise ValueError("view %d is named in the pairs but was never added" % v)
+            if not srcs:
+                raise ValueError("reference view %d has no source views" % r)
+        imgs = [v[3] for v in self.views.values()]
+        if any(i is None for i in imgs) and not all(i is None for i in imgs):
+            raise ValueError("either every view has an image or none")
+        if imgs[0] is not None and len({i.dtype for i in imgs}) != 1:
+            raise ValueError("images must be all uint8 or all float32")
+        nch = 1 if self.combine_conf else len(self.prob_threshold)
+        if any(v[1].shape[0] < nch for v in self.views.values()):
+            raise MvsHipError("%d thresholds but a view has fewer confidence channels" % nch)
+        with torch.cuda.device(self.device):
+            depths = torch.stack([v[0] for v in self.views.values()]).contiguous()             # a copy: zeroed in place below
+            confs = torch.stack([v[1][:nch] for v in self.views.values()]).contiguous()
+            cams = torch.stack([v[2] for v in self.views.values()])
+            images = None if imgs[0] is None else torch.stack(imgs).contiguous()
+            tables = tuple(torch.from_numpy(t).to(self.device) for t in gipuma_tables(cams))
+            table = ops.JobTable([(index[r], [index[v] for v in srcs]) for r, srcs in pairs], len(ids), self.device)
+            photo = ops.prob_filter(confs, self.prob_threshold[:nch], depth_inplace=depths).view(len(ids), *self.hw)
+            out = ops.gipuma_fuse_scene(depths, tables, table, self.disp_threshold, self.num_consistent, self.depth_min, self.depth_max,
+                                        want_count=with_intermediates)
+            comp = ops.pointcloud_compact(table, photo, out["keep"], out["points"], images, want=tuple(want))
+            res: Dict[str, object] = {k: comp[k] if on_device else comp[k].cpu().numpy() for k in want}
+        if with_intermediates:
+            res.update(photo_mask=photo, geo_mask=out["keep"], points_dense=out["points"], used=out["used"], count=out["count"], view_ids=ids)
+        hw = float(self.hw[0] * self.hw[1])
+        st = comp["stats"]
+        res["n_points"] = comp["total"]
+        res["counts_per_view"] = {r: int(st[i, 2]) for i, (r, _) in enumerate(pairs)}
+        res["stats"] = {r: dict(photo=st[i, 0] / hw, geo=st[i, 1] / hw, final=st[i, 2] / hw) for i, (r, _) in enumerate(pairs)}
+        return res
+
+
+def gipuma_fuse_scan(pair_folder: str, scan_folder: str, plyfilename: str, prob_threshold: Sequence[float], disp_threshold: float = 0.2,
+                     num_consistent: float = 3, depth_min: float = 0.001, depth_max: float = 100000.0, combine_conf: bool = False,
+                     n_src_views: int = 10, device: str = "cuda:0") -> Dict[str, object]:
+    """``gipuma_filter`` (misc/gipuma.py:192-228) without the .dmb round trip and the external binary: the scan folder
+    ``save_depth_outputs`` (+ ``images/``) left -> ``plyfilename``.  Returns what ``fuse_scan`` returns."""
+    import time
+    from . import data_io
+    t0 = time.perf_counter()
+    scene = GipumaFusion.from_folder(pair_folder, scan_folder, n_src_views, prob_threshold=prob_threshold, disp_threshold=disp_threshold,
+                                     num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, combine_conf=combine_conf,
+                                     device=device)
     torch.cuda.synchronize(scene.device)
     t1 = time.perf_counter()
     out = scene.fuse(want=("records",))

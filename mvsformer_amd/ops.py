@@ -1346,6 +1346,43 @@ def pointcloud_compact(table: JobTable, photo_mask, geo_mask, points, images=Non
     return out
 
 
+def gipuma_fuse_scene(depth, tables, table: Optional[JobTable] = None, disp_thresh: float = 0.2, num_consistent: float = 3,
+                      depth_min: float = 0.001, depth_max: float = 100000.0, want_count: bool = False) -> Dict[str, torch.Tensor]:
+    """``mvs_gipuma_fuse_scene``: ``depth [Nv,H,W]`` (prob-filtered pixels zeroed), ``tables`` = ``(B [Nv,3,3], c [Nv,3], A [Nv,Nv,3,3],
+    b [Nv,Nv,3], fb [Nv,Nv])`` device float32 (``fusion.gipuma_tables``), ``table`` = the jobs in processing order (None: every view
+    against all others, ascending) -> ``keep [R,H,W]`` bool, ``points [R,3,H,W]``, ``used [Nv,H,W]`` uint8 and, with ``want_count``,
+    ``count [R,H,W]`` uint8.  One launch per job on the current stream, no host synchronisation."""
+    _chk(depth, "depth")
+    if depth.dim() != 3 or len(tables) != 5:
+        raise _lib.MvsHipError("gipuma_fuse_scene: depth must be [Nv,H,W] and tables (B, c, A, b, fb)")
+    nv, h, w = depth.shape
+    B, c, A, b, fb = [_chk(t, "tables[%d]" % i) for i, t in enumerate(tables)]
+    if B.shape != (nv, 3, 3) or c.shape != (nv, 3) or A.shape != (nv, nv, 3, 3) or b.shape != (nv, nv, 3) or fb.shape != (nv, nv):
+        raise _lib.MvsHipError("gipuma_fuse_scene: tables %s do not fit %d views" % ([tuple(t.shape) for t in tables], nv))
+    if table is not None:
+        _chk(table.ref_idx, "ref_idx", torch.int32), _chk(table.src_idx, "src_idx", torch.int32), _chk(table.n_src, "n_src", torch.int32)
+        if table.n_views != nv:
+            raise _lib.MvsHipError("gipuma_fuse_scene: the job table is over %d views, depth holds %d" % (table.n_views, nv))
+        for r, srcs in table.jobs:
+            if r in srcs or len(set(srcs)) != len(srcs):
+                raise ValueError("gipuma_fuse_scene: reference view %d is among its own sources, or a source is listed twice" % r)
+        R, V, n_pairs = table.R, table.Vmax, sum(table.n_src_host)
+    else:
+        R, V, n_pairs = nv, nv - 1, nv * (nv - 1)
+    dev = depth.device
+    out = dict(used=torch.empty((nv, h, w), device=dev, dtype=torch.uint8), keep=torch.empty((R, h, w), device=dev, dtype=torch.uint8),
+               points=torch.empty((R, 3, h, w), device=dev, dtype=torch.float32))
+    if want_count:
+        out["count"] = torch.empty((R, h, w), device=dev, dtype=torch.uint8)
+    algo = h * w * (4.0 * n_pairs + R * (5.0 + 1.0 + 12.0 + (1.0 if want_count else 0.0)) + nv)
+    _call("mvs_gipuma_fuse_scene", ("gipuma_fuse_scene", "bytes", algo), _ptr(depth), _ptr(B), _ptr(c), _ptr(A), _ptr(b), _ptr(fb), nv,
+          *([_ptr(table.ref_idx), _ptr(table.src_idx), _ptr(table.n_src)] if table is not None else [None, None, None]), R, V, h, w,
+          float(disp_thresh), float(num_consistent), float(depth_min), float(depth_max), _ptr(out["used"]), _ptr(out["keep"]),
+          _ptr(out.get("count")), _ptr(out["points"]), _stream())
+    out["keep"] = out["keep"].view(torch.bool)
+    return out
+
+
 # ------------------------------------------------------------------------------------- fused CE loss (§8 f3)
 def ce_loss(logits, depth_values, depth_gt, mask, inverse_depth: bool, weight: float = 1.0, want_grad: bool = True,
             want_index: bool = False):
