@@ -29,9 +29,9 @@ _RULES = [
     (r"^(head_|prob1_kernel|mvs_prob1_fwd|init_inverse|schedule_inverse|init_range|schedule_range|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|"
      r"mvs_init_range|mvs_schedule_range|mvs_conf)", ["head.hip", "common.h", PUB]),
     (r"^(proj_|mvs_proj)", ["proj.hip", "common.h", PUB]),
-    (r"^(depth_metrics|mvs_depth_metrics)", ["metrics.hip", "common.h", PUB]),
-    (r"^(prep_|mvs_prep)", ["sample_prep.hip", "common.h", PUB]),
-    (r"^(cloud_|mvs_cloud)", ["cloud_eval.hip", "common.h", PUB]),
+    (r"^(depth_metrics|mvs_depth_metrics)", ["metrics.hip", "block_ops.h", "common.h", PUB]),
+    (r"^(prep_|mvs_prep)", ["sample_prep.hip", "block_ops.h", "common.h", PUB]),
+    (r"^(cloud_|mvs_cloud)", ["cloud_eval.hip", "block_ops.h", "common.h", PUB]),
     (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
     (r"^(fpn_v2_tail|mvs_fpn_v2_tail)", ["fpn_v2_tail.hip", "conv_common.h", "common.h", "prims.h", PUB]),
     (r"^(fpn8_cp|mvs_fpn_level_cp)", ["fpn_cp.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),

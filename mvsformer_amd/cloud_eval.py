@@ -64,13 +64,18 @@ def default_cell(bounds: Sequence[float], n_finite: int, max_dist: float) -> flo
 
 
 class _Index:
-    """The grid of one target cloud: what ``mvs_cloud_grid_build`` left on the device."""
+    """The grid of one target cloud: what ``mvs_cloud_grid_build`` left on the device.  ``cell``: the edge, a rule ``(bounds, n_valid) ->
+    edge``, or None for :func:`default_cell` with ``max_dist``.  ``skip_empty``: no finite point -> nothing is launched after the bounds."""
 
-    def __init__(self, pts: torch.Tensor, cell: Optional[float], max_dist: Optional[float], want_sorted: bool = True):
+    def __init__(self, pts: torch.Tensor, cell, max_dist: Optional[float] = None, want_sorted: bool = True, skip_empty: bool = False):
         self.pts, self.n = pts, pts.shape[0]
         self.grid, self.bounds, self.n_bad = ops.cloud_bounds(pts)
         self.n_valid = self.n - self.n_bad
-        self.cell = default_cell(self.bounds, self.n_valid, max_dist) if cell is None else cell
+        if skip_empty and self.n_valid == 0:
+            return
+        if cell is None:
+            cell = default_cell(self.bounds, self.n_valid, max_dist)
+        self.cell = cell(self.bounds, self.n_valid) if callable(cell) else cell
         keys = ops.cloud_grid_keys(pts, self.cell, self.grid, self.bounds, self.n_bad)
         skeys, self.perm = torch.sort(keys, stable=True)                   # plumbing: the one step of the index that is not HIP
         self.sorted_pts, self.cell_keys, self.cell_start = ops.cloud_grid_build(pts, skeys, self.perm, self.grid, want_sorted)
@@ -113,7 +118,7 @@ def _thin(xyz: torch.Tensor, voxel: float, attrs: Sequence[torch.Tensor] = ()):
     empty = [torch.empty(0, 3, dtype=torch.float32, device=xyz.device) for _ in range(1 + len(attrs))]
     if xyz.shape[0] == 0:
         return empty
-    index = _Index(xyz, voxel, None, want_sorted=False)
+    index = _Index(xyz, voxel, want_sorted=False)
     count = ops.cloud_voxel_count(index.grid) if index.n_valid else 0
     if count == 0:
         return empty
@@ -166,13 +171,10 @@ def _greedy(xyz: torch.Tensor, dist: float, order, seed: int):
     none = torch.zeros(n, dtype=torch.bool, device=xyz.device)
     if n == 0:
         return none, 0
-    grid, bounds, n_bad = ops.cloud_bounds(xyz)
-    if n_bad == n:
+    index = _Index(xyz, lambda bounds, n_valid: thin_cell(bounds, dist), skip_empty=True)
+    if index.n_valid == 0:
         return none, 0                                                     # nothing finite: no index, no round
-    keys = ops.cloud_grid_keys(xyz, thin_cell(bounds, dist), grid, bounds, n_bad)
-    skeys, perm = torch.sort(keys, stable=True)
-    sorted_pts, cell_keys, cell_start = ops.cloud_grid_build(xyz, skeys, perm, grid, True)
-    return ops.greedy_thin(order, grid, dist, sorted_pts, perm, cell_keys, cell_start)       # refuses an order that is no permutation
+    return ops.greedy_thin(order, index.grid, dist, index.sorted_pts, index.perm, index.cell_keys, index.cell_start)       # refuses an order that is no permutation
 
 
 @torch.no_grad()

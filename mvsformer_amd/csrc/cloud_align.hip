@@ -9,7 +9,7 @@
 //                               per-lane grid-stride accumulation, a fixed wavefront tree, one row per block; a second single-block launch
 //                               folds the rows in index order (eight contiguous chunks, then the chunks in order) and writes ONE record.
 // No float atomics, no block waits on another block: two runs over the same input give the same bits.
-#include "common.h"
+#include "block_ops.h"
 
 #include <math.h>
 
@@ -39,8 +39,8 @@ struct Affine { double r[3][3]; double t[3]; };
 struct Polygon { double u[CA_MAXK]; double v[CA_MAXK]; };
 struct Origin { double o[3]; };
 
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-inline unsigned blocks_for(long long n) { return (unsigned)mvs::ceil_div(n, (long long)CA_THREADS); }
+using blk::aligned8;
+using blk::blocks_for;
 
 // ------------------------------------------------------------------------------------------------------- transform
 __global__ __launch_bounds__(CA_THREADS) void align_transform_kernel(const float* __restrict__ pts, long long N, Affine a, float* __restrict__ out) {
@@ -78,15 +78,6 @@ __global__ __launch_bounds__(CA_THREADS) void align_crop_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------------- pair sums
-__device__ __forceinline__ double wave_sum(double s) {
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    return s;
-}
-__device__ __forceinline__ long long wave_sum(long long s) {
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    return s;
-}
-
 __global__ __launch_bounds__(CA_THREADS) void align_pair_sums_kernel(const float* __restrict__ src, long long M, const float* __restrict__ dst,
                                                                      long long N, const long long* __restrict__ idx, const float* __restrict__ dist,
                                                                      Origin og, double* __restrict__ rows) {
@@ -118,11 +109,11 @@ __global__ __launch_bounds__(CA_THREADS) void align_pair_sums_kernel(const float
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int k = 0; k < CA_SUMS; ++k) {
-        const double w = wave_sum(s[k]);
+        const double w = blk::wave_sum(s[k]);
         if (lane == 0) sred[wave][k] = w;
     }
-    n = wave_sum(n);
-    n_finite = wave_sum(n_finite);
+    n = blk::wave_sum(n);
+    n_finite = blk::wave_sum(n_finite);
     if (lane == 0) {
         sred[wave][CA_SUMS] = __longlong_as_double(n);
         sred[wave][CA_SUMS + 1] = __longlong_as_double(n_finite);
@@ -182,7 +173,7 @@ extern "C" int mvs_align_transform(const float* pts, int64_t N, const double* sr
         for (int c = 0; c < 3; ++c) a.r[r][c] = srt_host[3 * r + c];
         a.t[r] = srt_host[9 + r];
     }
-    hipLaunchKernelGGL(align_transform_kernel, dim3(blocks_for(N)), dim3(CA_THREADS), 0, MVS_STREAM(stream), pts, (long long)N, a, out);
+    hipLaunchKernelGGL(align_transform_kernel, dim3(blocks_for(N, CA_THREADS)), dim3(CA_THREADS), 0, MVS_STREAM(stream), pts, (long long)N, a, out);
     return mvs::finish_launch("mvs_align_transform");
 }
 
@@ -202,7 +193,7 @@ extern "C" int mvs_align_crop_polygon(const float* pts, int64_t N, int axis, dou
     }
     if (N == 0) return 0;
     const int ua = axis == 0 ? 1 : 0, va = axis == 2 ? 1 : 2;               // X: (Y, Z)   Y: (X, Z)   Z: (X, Y)
-    hipLaunchKernelGGL(align_crop_kernel, dim3(blocks_for(N)), dim3(CA_THREADS), 0, MVS_STREAM(stream), pts, (long long)N, axis, ua, va, axis_min,
+    hipLaunchKernelGGL(align_crop_kernel, dim3(blocks_for(N, CA_THREADS)), dim3(CA_THREADS), 0, MVS_STREAM(stream), pts, (long long)N, axis, ua, va, axis_min,
                        axis_max, poly, K, mask);
     return mvs::finish_launch("mvs_align_crop_polygon");
 }

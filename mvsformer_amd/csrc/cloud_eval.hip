@@ -9,7 +9,7 @@
 //   1. mvs_cloud_bounds:      min / max over the finite points, the number of non-finite ones; the caller reads 32 bytes.
 //   2. mvs_cloud_grid_keys:   one int64 key per point (non-finite points: the largest key, behind every cell).
 //      ... the caller sorts the keys (stable) and keeps the permutation ...
-//   3. mvs_cloud_grid_build:  heads of runs of equal keys -> count per 256-point block -> one-block scan -> scatter: the table of
+//   3. mvs_cloud_grid_build:  heads of runs of equal keys -> count per 256-point block -> one-block scan (block_ops.h) -> scatter: the table of
 //                             occupied cells (key, first point), and the points gathered into cell order.  Stable: the permutation of
 //                             a stable sort keeps the original order inside a cell.
 //   4. mvs_cloud_nn_query:    one lane per query, queries in cell order (their own sorted keys): Chebyshev shells of cells around the
@@ -25,7 +25,7 @@
 // and u* the real quotient, |u - u*| <= 2^-23 |u*| (two roundings).  Two points whose cells differ by s + 1 or more on an axis are
 // therefore farther apart than (s - slack) * cell with slack = 2^-22 * 1.01 * (largest |u| in play).  The walk uses that bound, shrunk by
 // another 1e-5 relative to cover the fp32 rounding of the distance itself: it never skips a point the brute-force scan would pick.
-#include "common.h"
+#include "block_ops.h"
 
 #include <math.h>
 #include <string.h>
@@ -33,6 +33,9 @@
 #include <algorithm>
 
 namespace {
+
+using blk::aligned8;
+using blk::blocks_for;
 
 constexpr int CE_THREADS = 256;
 constexpr int CE_AXIS_BITS = 21;
@@ -86,6 +89,14 @@ __device__ __forceinline__ long long make_key(int cx, int cy, int cz) {
     return (long long)cx | ((long long)cy << CE_AXIS_BITS) | ((long long)cz << (2 * CE_AXIS_BITS));
 }
 
+// the cell of an indexed point.  origin = the minimum, ncell sized from the maximum by the same monotone operations: 0 <= c < ncell <= 2^21;
+// the clamp only guards a caller whose bounds do not belong to these points
+struct Cell { int x, y, z; };
+__device__ __forceinline__ Cell own_cell(float x, float y, float z, const float (&origin)[3], float cell, const int (&ncell)[3]) {
+    return Cell{min(max((int)cell_coord(x, origin[0], cell), 0), ncell[0] - 1), min(max((int)cell_coord(y, origin[1], cell), 0), ncell[1] - 1),
+                min(max((int)cell_coord(z, origin[2], cell), 0), ncell[2] - 1)};
+}
+
 // ---------------------------------------------------------------------------------------------------------- bounds
 __global__ __launch_bounds__(CE_THREADS) void cloud_bounds_kernel(const float* __restrict__ pts, long long N, CloudGrid* __restrict__ g) {
     __shared__ uint32_t slo[3][CE_THREADS / 64], shi[3][CE_THREADS / 64], sbad[CE_THREADS / 64];
@@ -101,7 +112,7 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_bounds_kernel(const float* _
             ++bad;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int o = 32; o > 0; o >>= 1) {                                      // the count rides in the min / max tree: its own pass costs registers
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             lo[a] = min(lo[a], (uint32_t)__shfl_down(lo[a], o, 64));
@@ -123,8 +134,7 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_bounds_kernel(const float* _
         atomicMin(&g->lo_bits[a], l);
         atomicMax(&g->hi_bits[a], h);
     } else if (threadIdx.x == 3) {
-        uint32_t b = 0;
-        for (int w = 0; w < CE_THREADS / 64; ++w) b += sbad[w];
+        const uint32_t b = blk::sum4(sbad);
         if (b) atomicAdd(reinterpret_cast<unsigned long long*>(&g->n_bad), (unsigned long long)b);
     }
 }
@@ -146,12 +156,8 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_keys_kernel(const float* __r
     const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
     long long key = CE_BAD_KEY;
     if (finite3(x, y, z)) {
-        // origin is the minimum and ncell was sized from the maximum by the same monotone operations: 0 <= c < ncell <= 2^21; the clamp
-        // only guards a caller whose bounds do not belong to these points
-        const int cx = min(max((int)cell_coord(x, s.origin[0], s.cell), 0), s.ncell[0] - 1);
-        const int cy = min(max((int)cell_coord(y, s.origin[1], s.cell), 0), s.ncell[1] - 1);
-        const int cz = min(max((int)cell_coord(z, s.origin[2], s.cell), 0), s.ncell[2] - 1);
-        key = make_key(cx, cy, cz);
+        const Cell c = own_cell(x, y, z, s.origin, s.cell, s.ncell);
+        key = make_key(c.x, c.y, c.z);
     }
     keys[i] = key;
 }
@@ -190,55 +196,14 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_heads_count_kernel(const lon
     __shared__ uint32_t part[CE_THREADS / 64];
     const long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
     const bool h = i < N && is_head(sk, i, g->n_valid);
-    const uint32_t c = __popcll(__ballot(h));
+    const uint32_t c = blk::ballot_count(h);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+    if (threadIdx.x == 0) counts[blockIdx.x] = blk::sum4(part);
 }
 
-constexpr int CE_SCAN_THREADS = 1024, CE_SCAN_ITEMS = 8;
-
-// one block: exclusive 64-bit scan of the block counts in tiles of 8192 with a running carry; the total is the number of occupied cells
-__global__ __launch_bounds__(CE_SCAN_THREADS) void cloud_scan_kernel(const uint32_t* __restrict__ counts, long long nb, long long* __restrict__ offsets,
-                                                                     CloudGrid* __restrict__ g, long long* __restrict__ cell_start) {
-    __shared__ uint32_t wsum[CE_SCAN_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    long long carry = 0;
-    for (long long base = 0; base < nb; base += (long long)CE_SCAN_THREADS * CE_SCAN_ITEMS) {
-        const long long i0 = base + (long long)t * CE_SCAN_ITEMS;
-        uint32_t v[CE_SCAN_ITEMS], s = 0;
-#pragma unroll
-        for (int j = 0; j < CE_SCAN_ITEMS; ++j) {
-            v[j] = (i0 + j < nb) ? counts[i0 + j] : 0u;
-            s += v[j];
-        }
-        uint32_t inc = s;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += o;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t wbase = 0, tile = 0;
-        for (int w = 0; w < CE_SCAN_THREADS / 64; ++w) {
-            const uint32_t q = wsum[w];
-            wbase += (w < wave) ? q : 0u;
-            tile += q;
-        }
-        long long run = carry + (long long)wbase + (long long)(inc - s);
-#pragma unroll
-        for (int j = 0; j < CE_SCAN_ITEMS; ++j)
-            if (i0 + j < nb) { offsets[i0 + j] = run; run += v[j]; }
-        carry += tile;
-        __syncthreads();
-    }
-    if (t == 0) {
-        offsets[nb] = carry;
-        g->n_cells = carry;
-        cell_start[carry] = g->n_valid;                                     // carry <= N: cell_start holds N + 1 entries
-    }
-}
-
+// The scatter.  Lane 0 of block 0 also closes the table: cell_start[n_cells] = n_valid, n_cells = offsets[nb] as the scan left it
+// (n_cells <= N: cell_start holds N + 1 entries; no other lane of this launch writes that entry, and the first reader is a later launch).
 __global__ __launch_bounds__(CE_THREADS) void cloud_build_kernel(const float* __restrict__ pts, long long N, const long long* __restrict__ sk,
                                                                  const long long* __restrict__ perm, const CloudGrid* __restrict__ g,
                                                                  const long long* __restrict__ offsets, float* __restrict__ sorted_pts,
@@ -247,13 +212,11 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_build_kernel(const float* __
     const long long i = (long long)blockIdx.x * CE_THREADS + threadIdx.x;
     const long long n_valid = g->n_valid;
     const bool h = i < N && is_head(sk, i, n_valid);
-    const unsigned long long b = __ballot(h);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) wcnt[wave] = __popcll(b);
+    uint32_t wave_cnt, block_cnt;
+    const uint32_t rank = blk::ballot_rank(h, wave_cnt);
+    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = wave_cnt;
     __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < CE_THREADS / 64; ++w) woff += (w < wave) ? wcnt[w] : 0u;
+    const uint32_t woff = blk::block_rank_offset(wcnt, block_cnt);
     if (h) {
         const long long c = offsets[blockIdx.x] + (long long)(woff + rank);
         if (c >= 0 && c < N) { cell_keys[c] = sk[i]; cell_start[c] = i; }   // never past what the caller allocated
@@ -265,6 +228,10 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_build_kernel(const float* __
             sorted_pts[3 * i + 1] = pts[3 * src + 1];
             sorted_pts[3 * i + 2] = pts[3 * src + 2];
         }
+    }
+    if (i == 0) {
+        const long long n_cells = offsets[gridDim.x];
+        if (n_cells >= 0 && n_cells <= N) cell_start[n_cells] = n_valid;
     }
 }
 
@@ -280,19 +247,28 @@ __device__ __forceinline__ long long lower_bound(const long long* __restrict__ k
 
 struct Best { float d2; long long idx; };
 
+// the points [j0, j1) of the occupied cells among x0..x1 of row (y, z): one lookup (they are consecutive in cell order); false = none
+__device__ __forceinline__ bool row_range(int x0, int x1, int y, int z, const CloudGrid& g, long long n_cells, const long long* __restrict__ cell_keys,
+                                          const long long* __restrict__ cell_start, long long& j0, long long& j1) {
+    if (y < 0 || y >= g.ncell[1] || z < 0 || z >= g.ncell[2]) return false;
+    x0 = max(x0, 0);
+    x1 = min(x1, g.ncell[0] - 1);
+    if (x0 > x1) return false;
+    const long long a = lower_bound(cell_keys, 0, n_cells, make_key(x0, y, z));
+    if (a >= n_cells) return false;
+    const long long e = lower_bound(cell_keys, a, min(n_cells, a + (long long)(x1 - x0 + 1)), make_key(x1, y, z) + 1);
+    if (e <= a) return false;
+    j0 = cell_start[a];
+    j1 = min(cell_start[e], g.n_valid);
+    return true;
+}
+
 // the cells x0..x1 of row (y, z): one lookup, then their points (consecutive in cell order)
 __device__ __forceinline__ void visit_row(int x0, int x1, int y, int z, const CloudGrid& g, long long n_cells, const long long* __restrict__ cell_keys,
                                           const long long* __restrict__ cell_start, const float* __restrict__ spts,
                                           const long long* __restrict__ perm, float qx, float qy, float qz, Best& best) {
-    if (y < 0 || y >= g.ncell[1] || z < 0 || z >= g.ncell[2]) return;
-    x0 = max(x0, 0);
-    x1 = min(x1, g.ncell[0] - 1);
-    if (x0 > x1) return;
-    const long long a = lower_bound(cell_keys, 0, n_cells, make_key(x0, y, z));
-    if (a >= n_cells) return;
-    const long long e = lower_bound(cell_keys, a, min(n_cells, a + (long long)(x1 - x0 + 1)), make_key(x1, y, z) + 1);
-    if (e <= a) return;
-    const long long j0 = cell_start[a], j1 = min(cell_start[e], g.n_valid);
+    long long j0, j1;
+    if (!row_range(x0, x1, y, z, g, n_cells, cell_keys, cell_start, j0, j1)) return;
     for (long long j = j0; j < j1; ++j) {
         const float dx = qx - spts[3 * j], dy = qy - spts[3 * j + 1], dz = qz - spts[3 * j + 2];
         const float d2 = (dx * dx + dy * dy) + dz * dz;
@@ -383,7 +359,7 @@ constexpr int CE_SCORE_PPT = 4, CE_SCORE_P = CE_THREADS * CE_SCORE_PPT;
 __global__ __launch_bounds__(CE_THREADS) void cloud_score_kernel(const float* __restrict__ d, long long M, float max_dist, Taus taus, int K,
                                                                  CloudScore* __restrict__ rec, double* __restrict__ partial) {
     __shared__ double sred[CE_THREADS / 64];
-    __shared__ uint32_t cred[CE_THREADS / 64][1 + CE_MAXK];
+    __shared__ uint32_t cred[1 + CE_MAXK][CE_THREADS / 64];
     const long long p0 = (long long)blockIdx.x * CE_SCORE_P + threadIdx.x;
     double s = 0.0;
     uint32_t cnt[1 + CE_MAXK];
@@ -396,22 +372,20 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_score_kernel(const float* __
         const float v = in ? d[p] : 0.0f;
         const bool below = in && v < max_dist;                              // a NaN distance is below nothing
         s += below ? (double)v : 0.0;
-        cnt[0] += (uint32_t)__popcll(__ballot(below));
+        cnt[0] += blk::ballot_count(below);
 #pragma unroll
         for (int k = 0; k < CE_MAXK; ++k)
-            if (k < K) cnt[1 + k] += (uint32_t)__popcll(__ballot(in && v < taus.t[k]));
+            if (k < K) cnt[1 + k] += blk::ballot_count(in && v < taus.t[k]);
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    const int wave = threadIdx.x >> 6;
+    blk::block_sum_put(s, sred);
     if ((threadIdx.x & 63) == 0) {
-        sred[wave] = s;
 #pragma unroll
-        for (int c = 0; c <= CE_MAXK; ++c) cred[wave][c] = cnt[c];
+        for (int c = 0; c <= CE_MAXK; ++c) cred[c][threadIdx.x >> 6] = cnt[c];
     }
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+    if (threadIdx.x == 0) partial[blockIdx.x] = blk::sum4(sred);
     if (threadIdx.x <= K) {
-        const uint32_t c = (cred[0][threadIdx.x] + cred[1][threadIdx.x]) + (cred[2][threadIdx.x] + cred[3][threadIdx.x]);
+        const uint32_t c = blk::sum4(cred[threadIdx.x]);
         long long* dst = threadIdx.x == 0 ? &rec->n_below : &rec->below_tau[threadIdx.x - 1];
         if (c) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)c);
     }
@@ -423,11 +397,8 @@ __global__ __launch_bounds__(CE_THREADS) void cloud_score_final_kernel(const dou
     __shared__ double sred[CE_THREADS / 64];
     double s = 0.0;
     for (long long i = threadIdx.x; i < nblk; i += CE_THREADS) s += partial[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const double sum = blk::block_sum(s, sred);
     if (threadIdx.x == 0) {
-        const double sum = (sred[0] + sred[1]) + (sred[2] + sred[3]);
         rec->n = M;
         rec->sum = sum;
         rec->mean = sum / (double)rec->n_below;                             // 0 / 0 = NaN: the mean over an empty set
@@ -481,15 +452,8 @@ __device__ __forceinline__ bool thin_row(int x0, int x1, int y, int z, const Clo
                                          const long long* __restrict__ cell_start, const float* __restrict__ spts,
                                          const long long* __restrict__ srank, int* sstate, long long j, long long r, float qx, float qy,
                                          float qz, float dist2, bool& pending) {
-    if (y < 0 || y >= g.ncell[1] || z < 0 || z >= g.ncell[2]) return false;
-    x0 = max(x0, 0);
-    x1 = min(x1, g.ncell[0] - 1);
-    if (x0 > x1) return false;
-    const long long a = lower_bound(cell_keys, 0, n_cells, make_key(x0, y, z));
-    if (a >= n_cells) return false;
-    const long long e = lower_bound(cell_keys, a, min(n_cells, a + (long long)(x1 - x0 + 1)), make_key(x1, y, z) + 1);
-    if (e <= a) return false;
-    const long long k0 = cell_start[a], k1 = min(cell_start[e], g.n_valid);
+    long long k0, k1;
+    if (!row_range(x0, x1, y, z, g, n_cells, cell_keys, cell_start, k0, k1)) return false;
     for (long long k = k0; k < k1; ++k) {
         const float dx = qx - spts[3 * k], dy = qy - spts[3 * k + 1], dz = qz - spts[3 * k + 2];
         const float d2 = (dx * dx + dy * dy) + dz * dz;
@@ -521,14 +485,11 @@ __global__ __launch_bounds__(CE_THREADS) void thin_round_kernel(const CloudGrid*
         if (j >= 0 && j < g.n_valid && j < cap) {
             const float qx = spts[3 * j], qy = spts[3 * j + 1], qz = spts[3 * j + 2];
             const long long r = srank[j];
-            // the point's own cell, by the operations (and the clamp) that made its key
-            const int cx = min(max((int)cell_coord(qx, g.origin[0], g.cell), 0), g.ncell[0] - 1);
-            const int cy = min(max((int)cell_coord(qy, g.origin[1], g.cell), 0), g.ncell[1] - 1);
-            const int cz = min(max((int)cell_coord(qz, g.origin[2], g.cell), 0), g.ncell[2] - 1);
+            const Cell c = own_cell(qx, qy, qz, g.origin, g.cell, g.ncell);       // by the operations (and the clamp) that made its key
             bool removed = false, pending = false;
             for (int dz = -1; dz <= 1 && !removed; ++dz)
                 for (int dy = -1; dy <= 1 && !removed; ++dy)
-                    removed = thin_row(cx - 1, cx + 1, cy + dy, cz + dz, g, g.n_cells, cell_keys, cell_start, spts, srank, sstate, j, r, qx, qy, qz,
+                    removed = thin_row(c.x - 1, c.x + 1, c.y + dy, c.z + dz, g, g.n_cells, cell_keys, cell_start, spts, srank, sstate, j, r, qx, qy, qz,
                                        dist2, pending);
             if (removed) __hip_atomic_store(&sstate[j], TH_REMOVED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else if (!pending) __hip_atomic_store(&sstate[j], TH_KEPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -552,9 +513,6 @@ __global__ __launch_bounds__(CE_THREADS) void thin_keep_kernel(const long long* 
     const long long src = perm[j];
     if (src >= 0 && src < N) keep[src] = sstate[j] == TH_KEPT ? 1 : 0;
 }
-
-inline unsigned blocks_for(long long n, int per) { return (unsigned)mvs::ceil_div(n, (long long)per); }
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace
 
@@ -696,7 +654,7 @@ extern "C" int mvs_cloud_grid_build(const float* pts, int64_t N, const int64_t* 
     const long long* sk = reinterpret_cast<const long long*>(sorted_keys);
     const long long* pm = reinterpret_cast<const long long*>(perm);
     hipLaunchKernelGGL(cloud_heads_count_kernel, dim3((unsigned)nb), dim3(CE_THREADS), 0, s, sk, (long long)N, g, counts);
-    hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(CE_SCAN_THREADS), 0, s, counts, nb, offsets, g, reinterpret_cast<long long*>(cell_start));
+    blk::launch_exclusive_scan_u32(counts, nb, offsets, &g->n_cells, s);
     hipLaunchKernelGGL(cloud_build_kernel, dim3((unsigned)nb), dim3(CE_THREADS), 0, s, pts, (long long)N, sk, pm, g, offsets, sorted_pts,
                        reinterpret_cast<long long*>(cell_keys), reinterpret_cast<long long*>(cell_start));
     return mvs::finish_launch("mvs_cloud_grid_build");

@@ -16,14 +16,9 @@
 
 namespace {
 
-__global__ void geo_prep_kernel(const float* __restrict__ ref_cam /*[n,2,4,4]*/, const float* __restrict__ src_cam /*[n,v,2,4,4]*/,
-                                int n, int v, ViewXf* __restrict__ xf) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * v) return;
-    prep_view(ref_cam + (size_t)(idx / v) * 32, src_cam + (size_t)idx * 32, xf[idx]);
-}
-
-__global__ __launch_bounds__(256) void geo_filter_kernel(const float* __restrict__ ref_depth, const float* __restrict__ src_depth,
+// prep_kernel / geo_filter_dynamic_kernel: the templates of fusion_core.h over SampleViews.  The per-sample geo filter keeps its own body:
+// as an instance of geo_filter_kernel<> it gives the same bits but spills 3 SGPRs where this form spills 1 (it sits at the SGPR limit).
+__global__ __launch_bounds__(256) void geo_filter_sample_kernel(const float* __restrict__ ref_depth, const float* __restrict__ src_depth,
                                                          const float* __restrict__ ref_cam, const ViewXf* __restrict__ xf, int V, int H,
                                                          int W, float dist_thresh, float depth_thresh, float vthresh,
                                                          float* __restrict__ reproj /*[n,v,3,h,w]*/, float* __restrict__ in_range_out,
@@ -85,51 +80,11 @@ __global__ __launch_bounds__(256) void vis_filter_kernel(const float* __restrict
         msum += m;
         dsum += rd * m;
     }
-    if (mask_out) mask_out[(size_t)n * HW + pix] = (msum >= vthresh - 1.1f) ? 1 : 0;
-    if (ave_out) ave_out[(size_t)n * HW + pix] = (dsum + dref) / (msum + 1.0f);
+    write_fused(mask_out, ave_out, nullptr, n, HW, pix, msum >= vthresh - 1.1f, (dsum + dref) / (msum + 1.0f), nullptr, px, py);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Dynamic consistency (fusion.py:116-165, test.py:475-514); first_level / DynAcc / dyn_view are in fusion_core.h.
-__device__ __forceinline__ void write_levels(uint8_t* masks_out, uint8_t* vis_out, size_t nv, size_t HW, size_t pix, int kmin, int V) {
-    if (masks_out)
-        for (int k = 2; k <= V; ++k) masks_out[(nv * (V - 1) + (k - 2)) * HW + pix] = (k >= kmin) ? 1 : 0;
-    if (vis_out) vis_out[nv * HW + pix] = (kmin <= V) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void geo_filter_dynamic_kernel(const float* __restrict__ ref_depth, const float* __restrict__ src_depth,
-                                                                 const ViewXf* __restrict__ xf, int V, int H, int W, float dist_base,
-                                                                 float rel_base, float* __restrict__ reproj, uint8_t* __restrict__ masks_out,
-                                                                 uint8_t* __restrict__ vis_out, uint8_t* __restrict__ geo_out,
-                                                                 float* __restrict__ ave_out, float* __restrict__ points_out) {
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
-    if (x >= W || y >= H) return;
-    const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
-    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-    const float dref = ref_depth[(size_t)n * HW + pix];
-    DynAcc acc;
-    acc.init();
-    for (int v = 0; v < V; ++v) {
-        const V3 r = dyn_view(xf[n * V + v], src_depth + (size_t)(n * V + v) * HW, H, W, px, py, dref);
-        if (reproj) {
-            const size_t o3 = ((size_t)(n * V + v) * 3) * HW + pix;
-            reproj[o3] = r.x; reproj[o3 + HW] = r.y; reproj[o3 + 2 * HW] = r.z;
-        }
-        const int kmin = first_level(r.x, r.y, r.z, px, py, dref, V, dist_base, rel_base);
-        write_levels(masks_out, vis_out, (size_t)(n * V + v), HW, pix, kmin, V);
-        acc.add(kmin, r.z, V);
-    }
-    const float ave = (acc.dsum + dref) / (acc.msum + 1.0f);
-    if (geo_out) geo_out[(size_t)n * HW + pix] = acc.keep(V) ? 1 : 0;
-    if (ave_out) ave_out[(size_t)n * HW + pix] = ave;
-    if (points_out) {
-        const V3 p = fused_point(xf[n * V], px, py, ave);
-        points_out[((size_t)n * 3 + 0) * HW + pix] = p.x;
-        points_out[((size_t)n * 3 + 1) * HW + pix] = p.y;
-        points_out[((size_t)n * 3 + 2) * HW + pix] = p.z;
-    }
-}
-
 // op-level vis_filter_dynamic (fusion.py:153-165) on a materialized reproj_xyd, plus the reduction of test.py:503-511
 __global__ __launch_bounds__(256) void vis_filter_dynamic_kernel(const float* __restrict__ ref_depth, const float* __restrict__ reproj, int V,
                                                                  int H, int W, float dist_base, float rel_base,
@@ -150,8 +105,7 @@ __global__ __launch_bounds__(256) void vis_filter_dynamic_kernel(const float* __
         write_levels(masks_out, vis_out, (size_t)(n * V + v), HW, pix, kmin, V);
         acc.add(kmin, rd, V);
     }
-    if (geo_out) geo_out[(size_t)n * HW + pix] = acc.keep(V) ? 1 : 0;
-    if (ave_out) ave_out[(size_t)n * HW + pix] = (acc.dsum + dref) / (acc.msum + 1.0f);
+    write_fused(geo_out, ave_out, nullptr, n, HW, pix, acc.keep(V), (acc.dsum + dref) / (acc.msum + 1.0f), nullptr, px, py);
 }
 
 // prob_filter, fusion.py:69-77: AND over the C confidence channels of (conf[:, i] > thresh[i]); optionally zeroes a
@@ -203,10 +157,11 @@ extern "C" int mvs_geo_filter_dynamic_fwd(const float* ref_depth, const float* s
     MVS_REQUIRE(dist_base > 0.0f && rel_diff_base > 0.0f, "mvs_geo_filter_dynamic_fwd: bases must be positive");
     hipStream_t s = MVS_STREAM(stream);
     ViewXf* xf = reinterpret_cast<ViewXf*>(workspace);
-    hipLaunchKernelGGL(geo_prep_kernel, dim3(mvs::ceil_div(n * v, 64)), dim3(64), 0, s, ref_cam, src_cams, n, v, xf);
+    const SampleViews vw{v, reproj_xyd, masks, vis_mask};
+    hipLaunchKernelGGL(prep_kernel<SampleViews>, dim3(mvs::ceil_div(n * v, 64)), dim3(64), 0, s, vw, ref_cam, src_cams, n * v, xf);
     dim3 grid(mvs::ceil_div(W, 64), mvs::ceil_div(H, 4), n), block(64, 4);
-    hipLaunchKernelGGL(geo_filter_dynamic_kernel, grid, block, 0, s, ref_depth, src_depths, xf, v, H, W, dist_base, rel_diff_base,
-                       reproj_xyd, masks, vis_mask, geo_mask, ref_depth_ave, points);
+    hipLaunchKernelGGL(geo_filter_dynamic_kernel<SampleViews>, grid, block, 0, s, ref_depth, src_depths, vw, xf, H, W, dist_base,
+                       rel_diff_base, geo_mask, ref_depth_ave, points);
     return mvs::finish_launch("mvs_geo_filter_dynamic_fwd");
 }
 
@@ -233,9 +188,10 @@ extern "C" int mvs_geo_filter_fwd(const float* ref_depth, const float* src_depth
     MVS_REQUIRE(n >= 1 && n <= 65535 && v >= 1 && H >= 2 && W >= 2, "mvs_geo_filter_fwd: bad shape n=%d v=%d H=%d W=%d", n, v, H, W);
     hipStream_t s = MVS_STREAM(stream);
     ViewXf* xf = reinterpret_cast<ViewXf*>(workspace);
-    hipLaunchKernelGGL(geo_prep_kernel, dim3(mvs::ceil_div(n * v, 64)), dim3(64), 0, s, ref_cam, src_cams, n, v, xf);
+    hipLaunchKernelGGL(prep_kernel<SampleViews>, dim3(mvs::ceil_div(n * v, 64)), dim3(64), 0, s, SampleViews{v, nullptr, nullptr, nullptr},
+                       ref_cam, src_cams, n * v, xf);
     dim3 grid(mvs::ceil_div(W, 64), mvs::ceil_div(H, 4), n), block(64, 4);
-    hipLaunchKernelGGL(geo_filter_kernel, grid, block, 0, s, ref_depth, src_depths, ref_cam, xf, v, H, W, img_dist_thresh, depth_thresh,
+    hipLaunchKernelGGL(geo_filter_sample_kernel, grid, block, 0, s, ref_depth, src_depths, ref_cam, xf, v, H, W, img_dist_thresh, depth_thresh,
                        vthresh, reproj_xyd, in_range, masks, mask, ref_depth_ave, points);
     return mvs::finish_launch("mvs_geo_filter_fwd");
 }

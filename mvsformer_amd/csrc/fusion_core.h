@@ -223,4 +223,142 @@ __device__ __forceinline__ V3 dyn_view(const ViewXf& t, const float* __restrict_
     return V3{im.x, im.y, cr.z};
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The filter kernels, written once over a view-addressing policy `Views`: which reference and source maps a grid row
+// (blockIdx.z) filters, where their ViewXf sit, and whether per-view outputs exist.
+//   SampleViews (fusion.hip):   row n = sample n, views = rows n*V + v of src_depth / xf / the cameras [n,2,4,4], [n,v,2,4,4];
+//                               per-view outputs of the dynamic filter on request (the per-sample geo filter: see fusion.hip).
+//   JobViews (pointcloud.hip):  row r = job (ref_idx[r]; src_idx[r, 0..n_src[r])) into stacks of Nv maps and cameras; a row
+//                               whose table entries are inconsistent writes "nothing kept"; no per-view outputs.
+struct SampleViews {
+    static constexpr bool kChecked = false, kPerView = true;
+    int V;
+    float* reproj /*[n,v,3,h,w]*/;
+    uint8_t *level_masks /*[n,v,v-1,h,w]*/, *vis /*[n,v,h,w]*/;
+    __device__ int count(int, int) const { return V; }
+    __device__ int ref(int n) const { return n; }
+    __device__ int slot(int n, int v) const { return n * V + v; }         // the pair's ViewXf
+    __device__ int src(int n, int v) const { return n * V + v; }          // the pair's source map
+    __device__ bool cams(int idx, const float* ref_cam, const float* src_cam, const float*& rc, const float*& sc) const {
+        rc = ref_cam + (size_t)(idx / V) * 32;
+        sc = src_cam + (size_t)idx * 32;
+        return true;
+    }
+};
+
+struct JobViews {
+    static constexpr bool kChecked = true, kPerView = false;
+    int Nv;
+    const int32_t *ref_idx /*[R]*/, *src_idx /*[R,Vmax]*/, *n_src /*[R]*/;
+    int Vmax;
+    // a job's source count as the kernels use it; 0 = the job table is inconsistent and the job writes "nothing kept"
+    __device__ int count(int r, int vmin) const {
+        const int V = n_src[r];
+        if ((unsigned)ref_idx[r] >= (unsigned)Nv || V < vmin || V > Vmax) return 0;
+        for (int v = 0; v < V; ++v)
+            if ((unsigned)src_idx[r * Vmax + v] >= (unsigned)Nv) return 0;
+        return V;
+    }
+    __device__ int ref(int r) const { return ref_idx[r]; }
+    __device__ int slot(int r, int v) const { return r * Vmax + v; }
+    __device__ int src(int r, int v) const { return src_idx[r * Vmax + v]; }
+    __device__ bool cams(int idx, const float* ref_cam, const float* src_cam, const float*& rc, const float*& sc) const {
+        const int r = idx / Vmax, v = idx % Vmax;
+        const int ref = ref_idx[r], s = src_idx[idx];
+        if (v >= n_src[r] || (unsigned)ref >= (unsigned)Nv || (unsigned)s >= (unsigned)Nv) return false;      // padding (-1) or a bad entry
+        rc = ref_cam + (size_t)ref * 32;
+        sc = src_cam + (size_t)s * 32;
+        return true;
+    }
+};
+
+// the end of every filter kernel: keep mask, averaged depth and (points_out != null: t = the row's first ViewXf) the fused point of row n
+__device__ __forceinline__ void write_fused(uint8_t* mask_out, float* ave_out, float* points_out, size_t n, size_t HW, size_t pix, bool keep,
+                                            float ave, const ViewXf* t, float px, float py) {
+    if (mask_out) mask_out[n * HW + pix] = keep ? 1 : 0;
+    if (ave_out) ave_out[n * HW + pix] = ave;
+    if (points_out) {
+        const V3 p = fused_point(*t, px, py, ave);
+        points_out[(n * 3 + 0) * HW + pix] = p.x;
+        points_out[(n * 3 + 1) * HW + pix] = p.y;
+        points_out[(n * 3 + 2) * HW + pix] = p.z;
+    }
+}
+
+// a row whose job table is inconsistent: nothing kept
+__device__ __forceinline__ void write_nothing(uint8_t* mask_out, float* ave_out, float* points_out, size_t n, size_t HW, size_t pix) {
+    if (mask_out) mask_out[n * HW + pix] = 0;
+    if (ave_out) ave_out[n * HW + pix] = 0.0f;
+    if (points_out)
+        for (int c = 0; c < 3; ++c) points_out[(n * 3 + c) * HW + pix] = 0.0f;
+}
+
+// the per-level masks of one view of the dynamic filter (level k passes iff k >= kmin) and its "some level passes" flag
+__device__ __forceinline__ void write_levels(uint8_t* masks_out, uint8_t* vis_out, size_t nv, size_t HW, size_t pix, int kmin, int V) {
+    if (masks_out)
+        for (int k = 2; k <= V; ++k) masks_out[(nv * (V - 1) + (k - 2)) * HW + pix] = (k >= kmin) ? 1 : 0;
+    if (vis_out) vis_out[nv * HW + pix] = (kmin <= V) ? 1 : 0;
+}
+
+// camera algebra, one thread per (row, view) slot
+template <class Views>
+__global__ void prep_kernel(Views vw, const float* __restrict__ ref_cam, const float* __restrict__ src_cam, int slots, ViewXf* __restrict__ xf) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= slots) return;
+    const float *rc, *sc;
+    if (vw.cams(idx, ref_cam, src_cam, rc, sc)) prep_view(rc, sc, xf[idx]);
+}
+
+template <class Views>
+__global__ __launch_bounds__(256) void geo_filter_kernel(Views vw, const float* __restrict__ ref_depth, const float* __restrict__ src_depth,
+                                                         const ViewXf* __restrict__ xf, int H, int W, float dist_thresh, float depth_thresh,
+                                                         float vthresh, uint8_t* __restrict__ mask_out, float* __restrict__ ave_out,
+                                                         float* __restrict__ points_out /*[rows,3,h,w]*/) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
+    if (x >= W || y >= H) return;
+    const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
+    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+    const int V = vw.count(n, 1);
+    if constexpr (Views::kChecked)
+        if (V == 0) { write_nothing(mask_out, ave_out, points_out, n, HW, pix); return; }
+    const float dref = ref_depth[(size_t)vw.ref(n) * HW + pix];
+    float msum = 0.0f, dsum = 0.0f;
+    for (int v = 0; v < V; ++v) {
+        const GeoView g = geo_view(xf[vw.slot(n, v)], src_depth + (size_t)vw.src(n, v) * HW, H, W, px, py, dref, dist_thresh, depth_thresh);
+        msum += g.m;
+        dsum += g.rd * g.m;
+    }
+    write_fused(mask_out, ave_out, points_out, n, HW, pix, msum >= vthresh - 1.1f, (dsum + dref) / (msum + 1.0f), &xf[vw.slot(n, 0)], px, py);
+}
+
+template <class Views>
+__global__ __launch_bounds__(256) void geo_filter_dynamic_kernel(const float* __restrict__ ref_depth, const float* __restrict__ src_depth,
+                                                                 Views vw, const ViewXf* __restrict__ xf, int H, int W, float dist_base,
+                                                                 float rel_base, uint8_t* __restrict__ geo_out, float* __restrict__ ave_out,
+                                                                 float* __restrict__ points_out) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
+    if (x >= W || y >= H) return;
+    const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
+    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+    const int V = vw.count(n, 2);                                            // a job's dy_range = n_src[r] + 1 (test.py:485)
+    if constexpr (Views::kChecked)
+        if (V == 0) { write_nothing(geo_out, ave_out, points_out, n, HW, pix); return; }
+    const float dref = ref_depth[(size_t)vw.ref(n) * HW + pix];
+    DynAcc acc;
+    acc.init();
+    for (int v = 0; v < V; ++v) {
+        const V3 r = dyn_view(xf[vw.slot(n, v)], src_depth + (size_t)vw.src(n, v) * HW, H, W, px, py, dref);
+        const int kmin = first_level(r.x, r.y, r.z, px, py, dref, V, dist_base, rel_base);
+        if constexpr (Views::kPerView) {
+            if (vw.reproj) {
+                const size_t o3 = ((size_t)vw.src(n, v) * 3) * HW + pix;
+                vw.reproj[o3] = r.x; vw.reproj[o3 + HW] = r.y; vw.reproj[o3 + 2 * HW] = r.z;
+            }
+            write_levels(vw.level_masks, vw.vis, (size_t)vw.src(n, v), HW, pix, kmin, V);
+        }
+        acc.add(kmin, r.z, V);
+    }
+    write_fused(geo_out, ave_out, points_out, n, HW, pix, acc.keep(V), (acc.dsum + dref) / (acc.msum + 1.0f), &xf[vw.slot(n, 0)], px, py);
+}
+
 }  // namespace

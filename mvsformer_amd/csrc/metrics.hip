@@ -12,7 +12,7 @@
 // pixel index is therefore shifted by `phase` = the image's distance (in floats) from the 16-byte boundary below it, so that every lane's
 // quad starts ON a boundary; where depth_gt and the mask share that phase the quad is three vector loads (two and a dword for a byte mask),
 // everywhere else - the head and the tail of the image, or maps of different phases - four bounds-checked scalar loads per map.
-#include "common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(MET_THREADS) void depth_metrics_kernel(const float*
                                                                     const void* __restrict__ mask, const float* __restrict__ thr, int K,
                                                                     long long HW, int use_band, float lo, float hi, MetRow* __restrict__ rows) {
     __shared__ double sred[MET_THREADS / 64];
-    __shared__ uint32_t cred[MET_THREADS / 64][MET_NCNT];
+    __shared__ uint32_t cred[MET_NCNT][MET_THREADS / 64];
     const int b = blockIdx.y;
     const float* e_img = est + (size_t)b * HW;
     const float* g_img = gt + (size_t)b * HW;
@@ -80,32 +80,30 @@ __global__ __launch_bounds__(MET_THREADS) void depth_metrics_kernel(const float*
         err[j] = fabsf(ev[j] - gv[j]);                            // fp32, as the reference; used only where val[j] (a select, never a product)
         band[j] = val[j] && (!use_band || (err[j] >= lo && err[j] <= hi));
         s += band[j] ? (double)err[j] : 0.0;
-        cnt[0] += (uint32_t)__popcll(__ballot(val[j]));
-        cnt[1] += (uint32_t)__popcll(__ballot(band[j]));
+        cnt[0] += blk::ballot_count(val[j]);
+        cnt[1] += blk::ballot_count(band[j]);
     }
 #pragma unroll
     for (int k = 0; k < MET_MAXK; ++k) {
         if (k < K) {                                              // block-uniform
             const float t = thr[(size_t)b * K + k];
 #pragma unroll
-            for (int j = 0; j < MET_PPT; ++j) cnt[2 + k] += (uint32_t)__popcll(__ballot(val[j] && err[j] > t));
+            for (int j = 0; j < MET_PPT; ++j) cnt[2 + k] += blk::ballot_count(val[j] && err[j] > t);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    const int wave = threadIdx.x >> 6;
+    blk::block_sum_put(s, sred);
     if ((threadIdx.x & 63) == 0) {
-        sred[wave] = s;
 #pragma unroll
-        for (int c = 0; c < MET_NCNT; ++c) cred[wave][c] = cnt[c];           // every lane of the wavefront holds the same counts
+        for (int c = 0; c < MET_NCNT; ++c) cred[c][threadIdx.x >> 6] = cnt[c];         // every lane of the wavefront holds the same counts
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         MetRow r;
-        r.sum = (sred[0] + sred[1]) + (sred[2] + sred[3]);
-        r.n_valid = cred[0][0] + cred[1][0] + cred[2][0] + cred[3][0];
-        r.n_band = cred[0][1] + cred[1][1] + cred[2][1] + cred[3][1];
+        r.sum = blk::sum4(sred);
+        r.n_valid = blk::sum4(cred[0]);
+        r.n_band = blk::sum4(cred[1]);
 #pragma unroll
-        for (int k = 0; k < MET_MAXK; ++k) r.above[k] = cred[0][2 + k] + cred[1][2 + k] + cred[2][2 + k] + cred[3][2 + k];
+        for (int k = 0; k < MET_MAXK; ++k) r.above[k] = blk::sum4(cred[2 + k]);
         rows[(size_t)b * gridDim.x + blockIdx.x] = r;
     }
 }
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(MET_THREADS) void depth_metrics_kernel(const float*
 __global__ __launch_bounds__(MET_THREADS) void depth_metrics_image_kernel(const MetRow* __restrict__ rows, int nblk, int K, int use_band,
                                                                           int32_t* __restrict__ counts, float* __restrict__ per_image) {
     __shared__ double sred[MET_THREADS / 64];
-    __shared__ unsigned long long cred[MET_THREADS / 64][MET_NCNT];
+    __shared__ unsigned long long cred[MET_NCNT][MET_THREADS / 64];
     const int b = blockIdx.x;
     const MetRow* r = rows + (size_t)b * nblk;
     double s = 0.0;
@@ -128,23 +126,15 @@ __global__ __launch_bounds__(MET_THREADS) void depth_metrics_image_kernel(const 
 #pragma unroll
         for (int k = 0; k < MET_MAXK; ++k) cnt[2 + k] += r[i].above[k];
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o, 64);
+    blk::block_sum_put(s, sred);
 #pragma unroll
-        for (int c = 0; c < MET_NCNT; ++c) cnt[c] += __shfl_down(cnt[c], o, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sred[wave] = s;
-#pragma unroll
-        for (int c = 0; c < MET_NCNT; ++c) cred[wave][c] = cnt[c];
-    }
+    for (int c = 0; c < MET_NCNT; ++c) blk::block_sum_put(cnt[c], cred[c]);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double sum = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+        const double sum = blk::sum4(sred);
         unsigned long long tot[MET_NCNT];
 #pragma unroll
-        for (int c = 0; c < MET_NCNT; ++c) tot[c] = cred[0][c] + cred[1][c] + cred[2][c] + cred[3][c];
+        for (int c = 0; c < MET_NCNT; ++c) tot[c] = blk::sum4(cred[c]);
         const double n = (double)tot[0], nb = (double)tot[1];
         int32_t* co = counts + (size_t)b * (2 + K);
         float* po = per_image + (size_t)b * (1 + K);

@@ -8,12 +8,13 @@
 //      fusion_core.h, the same functions the per-sample kernels of fusion.hip call: bit-identical results.
 //   2. mvs_pointcloud_count: keep = photo[ref_idx[r]] & geo[r]; per 256-pixel block the number kept (__ballot + popcount
 //      per wavefront), per job the integer sums photo / geo / kept (integer atomics: exact, order-free); then ONE block
-//      scans the block counts into 64-bit exclusive offsets (a loop of 8192-element tiles with a running carry).
+//      scans the block counts into 64-bit exclusive offsets (block_ops.h: 8192-element tiles with a running carry).
 //   3. mvs_pointcloud_scatter (after the host has read the total and allocated): lane rank = mbcnt of the ballot + the
 //      wavefront's offset + the block's offset; records are staged in LDS and stored as aligned dwords.
 // No block ever waits on another block: the phases are separate launches on one stream.
 //
 // Output order = numpy boolean indexing per job (row-major over y, x), jobs concatenated (test.py:445-448, :459).
+#include "block_ops.h"
 #include "fusion_core.h"
 
 namespace {
@@ -21,96 +22,7 @@ namespace {
 constexpr int kBlock = 256;            // pixels per compaction block (4 wavefronts)
 constexpr int kRec = 15;               // bytes per vertex: x y z float32 little-endian, r g b uint8
 
-__global__ void scene_prep_kernel(const float* __restrict__ cams /*[Nv,2,4,4]*/, int Nv, const int32_t* __restrict__ ref_idx,
-                                  const int32_t* __restrict__ src_idx, const int32_t* __restrict__ n_src, int R, int Vmax,
-                                  ViewXf* __restrict__ xf /*[R,Vmax]*/) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= R * Vmax) return;
-    const int r = idx / Vmax, v = idx % Vmax;
-    const int ref = ref_idx[r], s = src_idx[idx];
-    if (v >= n_src[r] || (unsigned)ref >= (unsigned)Nv || (unsigned)s >= (unsigned)Nv) return;      // padding (-1) or a bad entry
-    prep_view(cams + (size_t)ref * 32, cams + (size_t)s * 32, xf[idx]);
-}
-
-// a job's source count as the kernels use it; 0 = the job table is inconsistent and the job writes "nothing kept"
-__device__ __forceinline__ int job_views(const int32_t* ref_idx, const int32_t* src_idx, const int32_t* n_src, int r, int Vmax, int Nv,
-                                         int vmin) {
-    const int V = n_src[r];
-    if ((unsigned)ref_idx[r] >= (unsigned)Nv || V < vmin || V > Vmax) return 0;
-    for (int v = 0; v < V; ++v)
-        if ((unsigned)src_idx[r * Vmax + v] >= (unsigned)Nv) return 0;
-    return V;
-}
-
-__device__ __forceinline__ void write_nothing(uint8_t* mask_out, float* ave_out, float* points_out, int r, size_t HW, size_t pix) {
-    if (mask_out) mask_out[(size_t)r * HW + pix] = 0;
-    if (ave_out) ave_out[(size_t)r * HW + pix] = 0.0f;
-    if (points_out)
-        for (int c = 0; c < 3; ++c) points_out[((size_t)r * 3 + c) * HW + pix] = 0.0f;
-}
-
-__global__ __launch_bounds__(256) void geo_filter_scene_kernel(const float* __restrict__ depth_ref, const float* __restrict__ depth_src,
-                                                               int Nv, const int32_t* __restrict__ ref_idx,
-                                                               const int32_t* __restrict__ src_idx, const int32_t* __restrict__ n_src,
-                                                               int Vmax, const ViewXf* __restrict__ xf, int H, int W, float dist_thresh,
-                                                               float depth_thresh, float vthresh, uint8_t* __restrict__ mask_out,
-                                                               float* __restrict__ ave_out, float* __restrict__ points_out) {
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, r = blockIdx.z;
-    if (x >= W || y >= H) return;
-    const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
-    const int V = job_views(ref_idx, src_idx, n_src, r, Vmax, Nv, 1);
-    if (V == 0) { write_nothing(mask_out, ave_out, points_out, r, HW, pix); return; }
-    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-    const float dref = depth_ref[(size_t)ref_idx[r] * HW + pix];
-    float msum = 0.0f, dsum = 0.0f;
-    for (int v = 0; v < V; ++v) {
-        const GeoView g = geo_view(xf[r * Vmax + v], depth_src + (size_t)src_idx[r * Vmax + v] * HW, H, W, px, py, dref, dist_thresh,
-                                   depth_thresh);
-        msum += g.m;
-        dsum += g.rd * g.m;
-    }
-    const float ave = (dsum + dref) / (msum + 1.0f);
-    if (mask_out) mask_out[(size_t)r * HW + pix] = (msum >= vthresh - 1.1f) ? 1 : 0;
-    if (ave_out) ave_out[(size_t)r * HW + pix] = ave;
-    if (points_out) {
-        const V3 p = fused_point(xf[r * Vmax], px, py, ave);
-        points_out[((size_t)r * 3 + 0) * HW + pix] = p.x;
-        points_out[((size_t)r * 3 + 1) * HW + pix] = p.y;
-        points_out[((size_t)r * 3 + 2) * HW + pix] = p.z;
-    }
-}
-
-__global__ __launch_bounds__(256) void geo_filter_dynamic_scene_kernel(const float* __restrict__ depth_ref,
-                                                                       const float* __restrict__ depth_src, int Nv,
-                                                                       const int32_t* __restrict__ ref_idx,
-                                                                       const int32_t* __restrict__ src_idx,
-                                                                       const int32_t* __restrict__ n_src, int Vmax,
-                                                                       const ViewXf* __restrict__ xf, int H, int W, float dist_base,
-                                                                       float rel_base, uint8_t* __restrict__ geo_out,
-                                                                       float* __restrict__ ave_out, float* __restrict__ points_out) {
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, r = blockIdx.z;
-    if (x >= W || y >= H) return;
-    const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
-    const int V = job_views(ref_idx, src_idx, n_src, r, Vmax, Nv, 2);        // dy_range = n_src[r] + 1 (test.py:485), per job
-    if (V == 0) { write_nothing(geo_out, ave_out, points_out, r, HW, pix); return; }
-    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-    const float dref = depth_ref[(size_t)ref_idx[r] * HW + pix];
-    DynAcc acc;
-    acc.init();
-    for (int v = 0; v < V; ++v) {
-        const V3 q = dyn_view(xf[r * Vmax + v], depth_src + (size_t)src_idx[r * Vmax + v] * HW, H, W, px, py, dref);
-        acc.add(first_level(q.x, q.y, q.z, px, py, dref, V, dist_base, rel_base), q.z, V);
-    }
-    const float ave = (acc.dsum + dref) / (acc.msum + 1.0f);
-    if (geo_out) geo_out[(size_t)r * HW + pix] = acc.keep(V) ? 1 : 0;
-    if (ave_out) ave_out[(size_t)r * HW + pix] = ave;
-    if (points_out) {
-        const V3 p = fused_point(xf[r * Vmax], px, py, ave);
-        points_out[((size_t)r * 3 + 0) * HW + pix] = p.x;
-        points_out[((size_t)r * 3 + 1) * HW + pix] = p.y;
-        points_out[((size_t)r * 3 + 2) * HW + pix] = p.z;
-    }
-}
+// the filter kernels are the templates of fusion_core.h over JobViews: row r is job (ref_idx[r]; src_idx[r, 0..n_src[r]))
 
 // ------------------------------------------------------------------------------------------------ compaction
 // workspace: offsets int64 [N + 1] (exclusive scan of the block counts, offsets[N] = total), then counts uint32 [N], N = R * nb
@@ -128,55 +40,13 @@ __global__ __launch_bounds__(kBlock) void pc_count_kernel(const uint8_t* __restr
     }
     __shared__ uint32_t part[3][kBlock / 64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t cp = __popcll(__ballot(p)), cg = __popcll(__ballot(g)), ck = __popcll(__ballot(p && g));
+    const uint32_t cp = blk::ballot_count(p), cg = blk::ballot_count(g), ck = blk::ballot_count(p && g);
     if (lane == 0) { part[0][wave] = cp; part[1][wave] = cg; part[2][wave] = ck; }
     __syncthreads();
     if (threadIdx.x < 3) {
-        uint32_t s = 0;
-        for (int w = 0; w < kBlock / 64; ++w) s += part[threadIdx.x][w];
+        const uint32_t s = blk::sum4(part[threadIdx.x]);
         if (threadIdx.x == 2) counts[(size_t)r * gridDim.x + blockIdx.x] = s;
         if (s) atomicAdd(&stats[r * 3 + threadIdx.x], (unsigned long long)s);
-    }
-}
-
-constexpr int kScanThreads = 1024, kScanItems = 8;
-
-__global__ __launch_bounds__(kScanThreads) void pc_scan_kernel(const uint32_t* __restrict__ counts, long long N, long long* __restrict__ offsets,
-                                                               long long* __restrict__ total) {
-    __shared__ uint32_t wsum[kScanThreads / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    long long carry = 0;
-    for (long long base = 0; base < N; base += (long long)kScanThreads * kScanItems) {
-        const long long i0 = base + (long long)t * kScanItems;
-        uint32_t v[kScanItems], s = 0;
-#pragma unroll
-        for (int j = 0; j < kScanItems; ++j) {
-            v[j] = (i0 + j < N) ? counts[i0 + j] : 0u;
-            s += v[j];
-        }
-        uint32_t inc = s;                                     // inclusive scan over the wavefront; a tile sums to <= 8192 * 256
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += o;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t wbase = 0, tile = 0;
-        for (int w = 0; w < kScanThreads / 64; ++w) {
-            const uint32_t q = wsum[w];
-            wbase += (w < wave) ? q : 0u;
-            tile += q;
-        }
-        long long run = carry + (long long)wbase + (long long)(inc - s);
-#pragma unroll
-        for (int j = 0; j < kScanItems; ++j)
-            if (i0 + j < N) { offsets[i0 + j] = run; run += v[j]; }
-        carry += tile;
-        __syncthreads();                                      // wsum is rewritten by the next tile
-    }
-    if (t == 0) {
-        offsets[N] = carry;
-        if (total) *total = carry;
     }
 }
 
@@ -199,17 +69,11 @@ __global__ __launch_bounds__(kBlock) void pc_scatter_kernel(const uint8_t* __res
     if (pix < HW && (unsigned)ref < (unsigned)Nv) keep = photo[(size_t)ref * HW + pix] != 0 && geo[(size_t)r * HW + pix] != 0;
     __shared__ uint32_t wcnt[kBlock / 64];
     __shared__ uint32_t stage[(kBlock * kRec + 4 + 3) / 4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned long long b = __ballot(keep);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    if (lane == 0) wcnt[wave] = __popcll(b);
+    uint32_t wave_cnt, cnt;
+    const uint32_t rank = blk::ballot_rank(keep, wave_cnt);
+    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = wave_cnt;
     __syncthreads();
-    uint32_t woff = 0, cnt = 0;
-    for (int w = 0; w < kBlock / 64; ++w) {
-        const uint32_t q = wcnt[w];
-        woff += (w < wave) ? q : 0u;
-        cnt += q;
-    }
+    const uint32_t woff = blk::block_rank_offset(wcnt, cnt);
     if (cnt == 0) return;                                                     // uniform over the block
     const long long off = offsets[(size_t)r * gridDim.x + blockIdx.x];
     // never write past what the host allocated, whatever the offsets say
@@ -277,10 +141,11 @@ extern "C" int mvs_geo_filter_scene_fwd(const float* depth_ref, const float* dep
         return rc;
     hipStream_t s = MVS_STREAM(stream);
     ViewXf* xf = reinterpret_cast<ViewXf*>(workspace);
-    hipLaunchKernelGGL(scene_prep_kernel, dim3(mvs::ceil_div(R * Vmax, 64)), dim3(64), 0, s, cams, Nv, ref_idx, src_idx, n_src, R, Vmax, xf);
+    const JobViews vw{Nv, ref_idx, src_idx, n_src, Vmax};
+    hipLaunchKernelGGL(prep_kernel<JobViews>, dim3(mvs::ceil_div(R * Vmax, 64)), dim3(64), 0, s, vw, cams, cams, R * Vmax, xf);
     dim3 grid(mvs::ceil_div(W, 64), mvs::ceil_div(H, 4), R), block(64, 4);
-    hipLaunchKernelGGL(geo_filter_scene_kernel, grid, block, 0, s, depth_ref, depth_src, Nv, ref_idx, src_idx, n_src, Vmax, xf, H, W,
-                       img_dist_thresh, depth_thresh, vthresh, mask, ref_depth_ave, points);
+    hipLaunchKernelGGL(geo_filter_kernel<JobViews>, grid, block, 0, s, vw, depth_ref, depth_src, xf, H, W, img_dist_thresh, depth_thresh,
+                       vthresh, mask, ref_depth_ave, points);
     return mvs::finish_launch("mvs_geo_filter_scene_fwd");
 }
 
@@ -296,10 +161,11 @@ extern "C" int mvs_geo_filter_dynamic_scene_fwd(const float* depth_ref, const fl
     MVS_REQUIRE(dist_base > 0.0f && rel_diff_base > 0.0f, "mvs_geo_filter_dynamic_scene_fwd: bases must be positive");
     hipStream_t s = MVS_STREAM(stream);
     ViewXf* xf = reinterpret_cast<ViewXf*>(workspace);
-    hipLaunchKernelGGL(scene_prep_kernel, dim3(mvs::ceil_div(R * Vmax, 64)), dim3(64), 0, s, cams, Nv, ref_idx, src_idx, n_src, R, Vmax, xf);
+    const JobViews vw{Nv, ref_idx, src_idx, n_src, Vmax};
+    hipLaunchKernelGGL(prep_kernel<JobViews>, dim3(mvs::ceil_div(R * Vmax, 64)), dim3(64), 0, s, vw, cams, cams, R * Vmax, xf);
     dim3 grid(mvs::ceil_div(W, 64), mvs::ceil_div(H, 4), R), block(64, 4);
-    hipLaunchKernelGGL(geo_filter_dynamic_scene_kernel, grid, block, 0, s, depth_ref, depth_src, Nv, ref_idx, src_idx, n_src, Vmax, xf, H, W,
-                       dist_base, rel_diff_base, geo_mask, ref_depth_ave, points);
+    hipLaunchKernelGGL(geo_filter_dynamic_kernel<JobViews>, grid, block, 0, s, depth_ref, depth_src, vw, xf, H, W, dist_base, rel_diff_base,
+                       geo_mask, ref_depth_ave, points);
     return mvs::finish_launch("mvs_geo_filter_dynamic_scene_fwd");
 }
 
@@ -323,7 +189,7 @@ extern "C" int mvs_pointcloud_count(const uint8_t* photo_mask, const uint8_t* ge
     if (hipMemsetAsync(stats, 0, sizeof(int64_t) * 3 * (size_t)R, s) != hipSuccess) return mvs::finish_launch("mvs_pointcloud_count(memset)");
     hipLaunchKernelGGL(pc_count_kernel, dim3((unsigned)nb, R), dim3(kBlock), 0, s, photo_mask, geo_mask, ref_idx, Nv, (size_t)HW, counts,
                        reinterpret_cast<unsigned long long*>(stats));
-    hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, counts, N, offsets, reinterpret_cast<long long*>(total));
+    blk::launch_exclusive_scan_u32(counts, N, offsets, reinterpret_cast<long long*>(total), s);
     return mvs::finish_launch("mvs_pointcloud_count");
 }
 

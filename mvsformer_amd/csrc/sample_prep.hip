@@ -7,7 +7,7 @@
 // sample (resized sizes, offsets, candidate offsets, jitter order and factors) is read from small device tables, so no launch geometry
 // depends on it and a captured graph replays with new tables.  Every source index is clamped into its image: a table with nonsense in it
 // gives nonsense pixels, never an access outside a tensor.
-#include "common.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -335,10 +335,8 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_jitter_stats_kernel(const u
         p = jitter_chain(p, jtab + (size_t)b * JT, 0, true);
         l = (unsigned int)pil_luma(p);
     }
-    for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = l;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(lsum + bv, (unsigned long long)(sred[0] + sred[1] + sred[2] + sred[3]));
+    l = blk::block_sum(l, sred);
+    if (threadIdx.x == 0) atomicAdd(lsum + bv, (unsigned long long)l);
 }
 
 // second launch: the whole chain, then ToTensor, RandomGamma (clip_image=True) and Normalize into NCHW fp32

@@ -360,7 +360,9 @@ def test_source_rules_list_every_included_header_and_find_every_kernel():
 def test_device_helpers_and_the_env_reader_have_one_home():
     """Plain source checks over csrc/: the shared vector types, the buffer-descriptor pieces and ``dpp_add`` are defined in prims.h and nowhere
     else (function bodies included), ``stage_load`` likewise, both forms of ``mfma6`` only in split3.h, and ``getenv`` is spelled only in
-    common.h (``mvs::env_int`` / ``mvs::env_str``).  The public header is part of ``file_digests()`` and of every rule."""
+    common.h (``mvs::env_int`` / ``mvs::env_str``).  The post-processing family likewise: the exclusive scan kernel, ``wave_sum`` and the
+    host helpers ``aligned8`` / ``blocks_for`` only in block_ops.h, the cell-row lookup ``row_range`` only in cloud_eval.hip.  The public
+    header is part of ``file_digests()`` and of every rule."""
     import hashlib
     from mvsformer_amd import _sources
     src = {f: open(os.path.join(_sources.CSRC, f)).read() for f in sorted(os.listdir(_sources.CSRC)) if f.endswith((".hip", ".h"))}
@@ -376,6 +378,11 @@ def test_device_helpers_and_the_env_reader_have_one_home():
         assert homes(fn % name) == {"prims.h": n}, name
     assert homes(fn % "mfma6") == {"split3.h": 2}
     assert homes(r"getenv") == {"common.h": 2}
+    assert homes(r"__global__.*\b\w*scan\w*_kernel\s*\(") == {"block_ops.h": 1}
+    assert homes(fn % "wave_sum") == {"block_ops.h": 1}
+    assert homes(fn % "row_range") == {"cloud_eval.hip": 1}
+    for name in ("aligned8", "blocks_for"):
+        assert homes(r"\binline\s+\w+\s+%s\s*\(" % name) == {"block_ops.h": 1}, name
     digests = _sources.file_digests()
     assert _sources.PUB not in src and "/" in _sources.PUB
     assert digests[_sources.PUB] == hashlib.sha256(open(os.path.join(REPO, "include", "mvs_hip.h"), "rb").read()).hexdigest()[:16]

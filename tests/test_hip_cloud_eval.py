@@ -57,6 +57,27 @@ def test_nn_distance_geometries(dev, name):
     _check_nn(case, ref, dev)
 
 
+@pytest.mark.parametrize("n", [256 * 8192, 256 * 8192 + 1])
+def test_index_at_the_scan_tile_edge(dev, n):
+    """8192 and 8193 blocks of 256 points: the shared exclusive scan (csrc/block_ops.h) fills exactly one tile / starts a second one with a
+    carry.  The number of occupied cells against numpy's fp32 cell rule, and every point finding itself."""
+    from mvsformer_amd import cloud_eval
+    r = np.random.default_rng(n)
+    xyz = r.random((n, 3)) * 100.0
+    xyz[:, 0] = r.permutation(n) * (100.0 / n)                    # 4.8e-5 apart, fp32 spacing below 100 is 7.6e-6: the points are distinct
+    xyz = U.f32(xyz)
+    assert len(np.unique(xyz[:, 0])) == n
+    cell = 1.0                                                    # ~1e6 cells, about two points each
+    c = U.cell_index(xyz, xyz.min(axis=0), cell)
+    n_cells = len(np.unique(c[:, 0] | (c[:, 1] << 21) | (c[:, 2] << 42)))
+    t = _t(xyz, dev)
+    out = cloud_eval.voxel_downsample(t, cell)
+    print(n, "voxels", out.shape[0], "expected", n_cells)
+    assert out.shape[0] == n_cells
+    dist, idx = cloud_eval.nn_distance(t, t, 0.5, cell=cell)
+    assert torch.equal(idx, torch.arange(n, device=idx.device)) and int(torch.count_nonzero(dist)) == 0
+
+
 def _voxel_clouds():
     r = np.random.default_rng(5)
     two = np.concatenate([r.uniform(0.0, 0.9, (129, 3)), r.uniform(0.0, 0.9, (128, 3)) + [1.0, 0.0, 0.0]])[r.permutation(257)]

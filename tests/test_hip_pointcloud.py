@@ -194,6 +194,28 @@ def test_compaction_alone(dev, tmp_path, pattern):
     assert gx.shape == (len(xyz), 3) and np.array_equal(gx.view(np.uint32), xyz.view(np.uint32)) and np.array_equal(gc, rgb)
 
 
+@pytest.mark.parametrize("pattern", ["ones", "rand0.5"])
+@pytest.mark.parametrize("nblocks", [1, 8191, 8192, 8193, 16385])
+def test_compaction_at_the_scan_tile_edge(dev, nblocks, pattern):
+    """One job whose 256-pixel blocks number 1, one below / at / one above the scan's 8192-count tile, and two tiles + 1: the running carry
+    of the shared exclusive scan (csrc/block_ops.h) against numpy boolean indexing, exactly."""
+    from mvsformer_amd import ops
+    h, w = nblocks, 256
+    rng = np.random.default_rng(100 + nblocks)
+    photo = np.ones((1, h, w), bool)
+    geo = np.ones((1, h, w), bool) if pattern == "ones" else rng.random((1, h, w)) < 0.5
+    points = rng.standard_normal((1, 3, h, w)).astype(np.float32)
+    imgs = rng.integers(0, 256, (1, 3, h, w)).astype(np.uint8)
+    xyz, rgb, rec, stats = _expected(photo, geo, [0], points, imgs)
+    table = ops.JobTable([(0, [0])], 1, dev)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    a = ops.pointcloud_compact(table, T(photo), T(geo), T(points), T(imgs))
+    print(nblocks, pattern, "total", a["total"], "expected", len(xyz))
+    assert a["total"] == len(xyz) and np.array_equal(a["stats"], stats)
+    assert a["records"].cpu().numpy().tobytes() == rec
+    assert np.array_equal(a["xyz"].cpu().numpy().view(np.uint32), xyz.view(np.uint32)) and np.array_equal(a["rgb"].cpu().numpy(), rgb)
+
+
 def test_colours_all_levels(dev):
     from mvsformer_amd import ops
     k = np.arange(256, dtype=np.uint8).reshape(16, 16)
