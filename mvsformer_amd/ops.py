@@ -16,7 +16,8 @@ import torch
 
 from . import _lib, switches as sw
 
-VIS_PARAM_FLOATS = 3689
+_H = _lib.DEFINES                                            # the integer macros of include/mvs_hip.h: MVS_<NAME> below
+VIS_PARAM_FLOATS = _H["MVS_VIS_PARAM_FLOATS"]
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -44,6 +45,32 @@ def _opt(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _new(on, *shape, dtype=torch.float32) -> torch.Tensor:
+    """An uninitialised output ``[*shape]`` on the device of ``on`` (a tensor, or the device itself)."""
+    return torch.empty(*shape, device=getattr(on, "device", on), dtype=dtype)
+
+
+_RESIDUAL_MSG = "residual shape %s != output %s"
+
+
+def _chk_residual(residual: Optional[torch.Tensor], shape, dtype=torch.float32, msg: str = _RESIDUAL_MSG) -> None:
+    """The skip tensor a layer adds to its output of ``shape`` has that shape and ``dtype`` (``msg``: where a caller says more)."""
+    if residual is not None:
+        _chk(residual, "residual", dtype)
+        if tuple(residual.shape) != tuple(shape):
+            raise _lib.MvsHipError(msg % (tuple(residual.shape), tuple(shape)))
+
+
+def _packed(entry: str, n: int, ok: bool, msg: str, margs, like: torch.Tensor, dtype, *args) -> torch.Tensor:
+    """Weights re-laid by a pack / prepare entry point: ``n`` elements of ``dtype`` (the entry's size query; <= 0 = not built for this
+    shape), refused with ``msg % margs`` before anything is allocated, else written by ``entry(*args, packed, stream)``."""
+    if not ok or n <= 0:
+        raise _lib.MvsHipError(msg % margs)
+    packed = _new(like, n, dtype=dtype)
+    _call(entry, None, *args, _ptr(packed), _stream())
+    return packed
 
 
 # ----------------------------------------------------------------------------------------------- weights epoch
@@ -145,7 +172,7 @@ def proj_prepare(proj: torch.Tensor) -> torch.Tensor:
     B, V = proj.shape[0], proj.shape[1]
     if proj.shape[2:] != (2, 4, 4) or V < 2:
         raise _lib.MvsHipError("proj must be [B,V>=2,2,4,4], got %s" % (tuple(proj.shape),))
-    rt = torch.empty(B, V - 1, 12, device=proj.device, dtype=torch.float32)
+    rt = _new(proj, B, V - 1, 12)
     _call("mvs_proj_prepare", None, _ptr(proj), B, V, _ptr(rt), _stream())
     return rt
 
@@ -155,7 +182,7 @@ def proj_relative(src_proj: torch.Tensor, ref_proj: torch.Tensor) -> torch.Tenso
     B = src_proj.shape[0]
     if src_proj.shape != (B, 4, 4) or ref_proj.shape != (B, 4, 4):
         raise _lib.MvsHipError("src_proj/ref_proj must be [B,4,4]")
-    rt = torch.empty(B, 12, device=src_proj.device, dtype=torch.float32)
+    rt = _new(src_proj, B, 12)
     _call("mvs_proj_relative", None, _ptr(src_proj), _ptr(ref_proj), B, _ptr(rt), _stream())
     return rt
 
@@ -170,8 +197,8 @@ def warp(src: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, with_mask: bo
         raise _lib.MvsHipError("depth_values must be [B,D,H,W] or [B,D], got %s" % (tuple(depth.shape),))
     if not per_pixel and depth.shape != (B, D):
         raise _lib.MvsHipError("depth_values must be [B,D,H,W] or [B,D], got %s" % (tuple(depth.shape),))
-    warped = torch.empty(B, C, D, H, W, device=src.device, dtype=torch.float32)
-    mask = torch.empty(B, D, H, W, device=src.device, dtype=torch.uint8) if with_mask else None
+    warped = _new(src, B, C, D, H, W)
+    mask = _new(src, B, D, H, W, dtype=torch.uint8) if with_mask else None
     _call("mvs_warp_fwd", None, _ptr(src), _ptr(rt), _ptr(depth), int(per_pixel), B, C, D, H, W, _ptr(warped), _ptr(mask), _stream())
     return warped, (mask.bool() if with_mask else None)
 
@@ -196,7 +223,7 @@ def to_channels_last(feat: torch.Tensor) -> torch.Tensor:
             return cl
     _chk(feat, "features")
     B, V, C, H, W = feat.shape
-    out = torch.empty(B, V, H, W, C, device=feat.device, dtype=torch.float32)
+    out = _new(feat, B, V, H, W, C)
     _call("mvs_nchw_to_nhwc", ("nchw_to_nhwc_kernel<%d>" % C, "bytes", 8.0 * feat.numel()), _ptr(feat), _ptr(out), B * V, C, H * W, _stream())
     return out
 
@@ -216,8 +243,7 @@ def to_channels_last_multi(feats: List[torch.Tensor]) -> List[torch.Tensor]:
     if len(jobs) > 4:
         raise _lib.MvsHipError("to_channels_last_multi: at most four tensors per launch")
     n = len(jobs)
-    bufs = [torch.empty(feats[i].shape[0], feats[i].shape[1], feats[i].shape[3], feats[i].shape[4], feats[i].shape[2],
-                        device=feats[i].device, dtype=torch.float32) for i in jobs]
+    bufs = [_new(feats[i], feats[i].shape[0], feats[i].shape[1], feats[i].shape[3], feats[i].shape[4], feats[i].shape[2]) for i in jobs]
     P = ctypes.c_void_p
     a_in = (P * n)(*[feats[i].data_ptr() for i in jobs])
     a_out = (P * n)(*[b.data_ptr() for b in bufs])
@@ -243,8 +269,8 @@ def _cv_dense_dims(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor):
 
 def _cv_volume(B: int, G: int, D: int, H: int, W: int, device, want_sim_depth: bool):
     """The outputs of a sweep B: ``volume [B,G,D,H,W]`` and ``sim_depth [B,H,W]`` (or None)."""
-    return (torch.empty(B, G, D, H, W, device=device, dtype=torch.float32),
-            torch.empty(B, H, W, device=device, dtype=torch.float32) if want_sim_depth else None)
+    return (_new(device, B, G, D, H, W),
+            _new(device, B, H, W) if want_sim_depth else None)
 
 
 def cv_store_bytes_of(B: int, V: int, C: int, G: int, D: int, H: int, W: int) -> int:
@@ -255,14 +281,14 @@ def cv_store_bytes_of(B: int, V: int, C: int, G: int, D: int, H: int, W: int) ->
 def _cv_corr_out(B: int, V: int, rows: int, W: int, nbytes: int, store: Optional[torch.Tensor], device):
     """The outputs of a sweep A' over ``rows`` reference rows: entropy ``[B,V-1,rows,W]`` and the store (``store`` itself where it holds ``nbytes``)."""
     if store is None or store.numel() * 4 < nbytes:
-        store = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
-    return torch.empty(B, V - 1, rows, W, device=device, dtype=torch.float32), store
+        store = _new(device, nbytes // 4)
+    return _new(device, B, V - 1, rows, W), store
 
 
 def cv_entropy(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None) -> torch.Tensor:
     """``feat`` is channel-last ``[B,V,H,W,C]`` (see :func:`to_channels_last`)."""
     B, V, C, D, H, W = _cv_dense_dims(feat, rt, depth)
-    ent = torch.empty(B, V - 1, H, W, device=feat.device, dtype=torch.float32)
+    ent = _new(feat, B, V - 1, H, W)
     # algorithmic bytes of a sweep over ALL source views: features once + hypotheses once (SURVEY.md §8d); the entropy
     # maps themselves are <1 %
     tag = ("cv_entropy_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
@@ -270,29 +296,30 @@ def cv_entropy(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int
     return ent
 
 
+def _vis_launch(entry: str, kernel: str, entropy: torch.Tensor, *operands) -> torch.Tensor:
+    """The launch of the three forms of the visibility CNN over ``entropy [...,H,W]``; each is credited with the direct form's FLOPs."""
+    H, W = entropy.shape[-2:]
+    N = entropy.numel() // (H * W)
+    out = torch.empty_like(entropy)
+    _call(entry, (kernel, "flops", 2.0 * 3608 * N * H * W), _ptr(entropy), *[_ptr(t) for t in operands], N, H, W, _ptr(out), _stream())
+    return out
+
+
 def vis(entropy: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
     _chk(entropy, "entropy"), _chk(params, "vis params")
     if params.numel() != VIS_PARAM_FLOATS:
         raise _lib.MvsHipError("vis params must hold %d floats" % VIS_PARAM_FLOATS)
-    H, W = entropy.shape[-2:]
-    N = entropy.numel() // (H * W)
-    out = torch.empty_like(entropy)
-    tag = ("vis_kernel", "flops", 2.0 * 3608 * N * H * W)
-    _call("mvs_vis_fwd", tag, _ptr(entropy), _ptr(params), N, H, W, _ptr(out), _stream())
-    return out
+    return _vis_launch("mvs_vis_fwd", "vis_kernel", entropy, params)
 
 
-VIS_WINO_FLOATS = 8192
+VIS_WINO_FLOATS = _H["MVS_VIS_WINO_FLOATS"]
 
 
 def vis_wino_prepare(params: torch.Tensor) -> torch.Tensor:
     """Transform-domain weights of the two 3x3 layers, laid out per MFMA lane, for :func:`vis_wino`."""
     _chk(params, "vis params")
-    if params.numel() != VIS_PARAM_FLOATS:
-        raise _lib.MvsHipError("vis params must hold %d floats" % VIS_PARAM_FLOATS)
-    prepared = torch.empty(VIS_WINO_FLOATS, device=params.device, dtype=torch.float32)
-    _call("mvs_vis_wino_prepare", None, _ptr(params), _ptr(prepared), _stream())
-    return prepared
+    return _packed("mvs_vis_wino_prepare", VIS_WINO_FLOATS, params.numel() == VIS_PARAM_FLOATS, "vis params must hold %d floats", VIS_PARAM_FLOATS,
+                   params, torch.float32, _ptr(params))
 
 
 def vis_wino(entropy: torch.Tensor, params: torch.Tensor, prepared: torch.Tensor) -> torch.Tensor:
@@ -300,25 +327,17 @@ def vis_wino(entropy: torch.Tensor, params: torch.Tensor, prepared: torch.Tensor
     _chk(entropy, "entropy"), _chk(params, "vis params"), _chk(prepared, "prepared vis weights")
     if params.numel() != VIS_PARAM_FLOATS or prepared.numel() != VIS_WINO_FLOATS:
         raise _lib.MvsHipError("vis params / prepared block have the wrong size")
-    H, W = entropy.shape[-2:]
-    N = entropy.numel() // (H * W)
-    out = torch.empty_like(entropy)
-    tag = ("vis_wino_kernel", "flops", 2.0 * 3608 * N * H * W)           # credited with the direct form's FLOPs
-    _call("mvs_vis_wino_fwd", tag, _ptr(entropy), _ptr(params), _ptr(prepared), N, H, W, _ptr(out), _stream())
-    return out
+    return _vis_launch("mvs_vis_wino_fwd", "vis_wino_kernel", entropy, params, prepared)
 
 
-VIS_X3_BYTES = 33792
+VIS_X3_BYTES = _H["MVS_VIS_X3_BYTES"]
 
 
 def vis_x3_prepare(params: torch.Tensor) -> torch.Tensor:
     """The two 3x3 layers' weights as three-term bf16 splits, laid out per MFMA lane, for :func:`vis_x3` (uint8 storage)."""
     _chk(params, "vis params")
-    if params.numel() != VIS_PARAM_FLOATS:
-        raise _lib.MvsHipError("vis params must hold %d floats" % VIS_PARAM_FLOATS)
-    prepared = torch.empty(VIS_X3_BYTES, device=params.device, dtype=torch.uint8)
-    _call("mvs_vis_x3_prepare", None, _ptr(params), _ptr(prepared), _stream())
-    return prepared
+    return _packed("mvs_vis_x3_prepare", VIS_X3_BYTES, params.numel() == VIS_PARAM_FLOATS, "vis params must hold %d floats", VIS_PARAM_FLOATS,
+                   params, torch.uint8, _ptr(params))
 
 
 def vis_x3(entropy: torch.Tensor, params: torch.Tensor, prepared: torch.Tensor) -> torch.Tensor:
@@ -327,12 +346,7 @@ def vis_x3(entropy: torch.Tensor, params: torch.Tensor, prepared: torch.Tensor) 
     _chk(entropy, "entropy"), _chk(params, "vis params")
     if params.numel() != VIS_PARAM_FLOATS or prepared.dtype != torch.uint8 or prepared.numel() != VIS_X3_BYTES or not prepared.is_cuda:
         raise _lib.MvsHipError("vis params / prepared block have the wrong size or type")
-    H, W = entropy.shape[-2:]
-    N = entropy.numel() // (H * W)
-    out = torch.empty_like(entropy)
-    tag = ("vis_x3_kernel", "flops", 2.0 * 3608 * N * H * W)
-    _call("mvs_vis_x3_fwd", tag, _ptr(entropy), _ptr(params), _ptr(prepared), N, H, W, _ptr(out), _stream())
-    return out
+    return _vis_launch("mvs_vis_x3_fwd", "vis_x3_kernel", entropy, params, prepared)
 
 
 def cv_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, G: int,
@@ -345,7 +359,7 @@ def cv_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, weig
     tag = ("cv_aggregate_kernel<%d,%s>" % (C // 4, "true" if want_sim_depth else "false"), "bytes",
            4.0 * B * H * W * (V * C + D + G * D))          # 4*H*W*(V*C + D + G*D)
     if want_bf16:
-        vol16 = torch.empty(B, D, H, W, G, device=feat.device, dtype=torch.bfloat16)
+        vol16 = _new(feat, B, D, H, W, G, dtype=torch.bfloat16)
         _call("mvs_cv_aggregate_fwd_bf16", tag, _ptr(feat), _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W,
               _ptr(vol), _ptr(vol16), _ptr(sim), _cv_flags(exact), _stream())
         return vol, sim, vol16
@@ -453,7 +467,7 @@ def cv_entropy_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torc
     the gathered views."""
     _chk(rt, "rt"), _chk(depth, "depth_values")
     table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_entropy_views", rt)
-    ent = torch.empty(B, V - 1, H, W, device=bank.device, dtype=torch.float32)
+    ent = _new(bank, B, V - 1, H, W)
     tag = ("cv_entropy_views_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
     _call("mvs_cv_entropy_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _cv_flags(exact), _stream())
     return ent
@@ -514,7 +528,7 @@ def cv_tiled_entropy(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, 
     D = depth.shape[1]
     if depth.shape != (B, D, H, W):
         raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, D, H, W), tuple(depth.shape)))
-    ent = torch.empty(B, V - 1, H, W, device=feat.device, dtype=torch.float32)
+    ent = _new(feat, B, V - 1, H, W)
     tag = ("cv_tiled_entropy<%d>" % C, "bytes", 4.0 * B * H * W * (V * C + D))
     _call("mvs_cv_tiled_entropy_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _cv_flags(exact),
           _ptr(stats), _stream())
@@ -536,7 +550,7 @@ def cv_tiled_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor
         if nbytes < 0:
             raise _lib.MvsHipError("mvs_cv_tiled_workspace_bytes: unsupported shape")
         if nbytes > 0:
-            ws = torch.empty(nbytes, device=feat.device, dtype=torch.uint8)
+            ws = _new(feat, nbytes, dtype=torch.uint8)
     tag = ("cv_tiled_aggregate<%d,%s>" % (C, "sim" if want_sim_depth else "nosim"), "bytes", 4.0 * B * H * W * (V * C + D + G * D))
     _call("mvs_cv_tiled_aggregate_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W, _ptr(vol), _ptr(sim),
           _ptr(ws), _cv_flags(exact), _ptr(stats), _stream())
@@ -554,28 +568,40 @@ def conv3d_pack(weight: torch.Tensor, transposed: bool, sd: int = 2) -> torch.Te
         raise _lib.MvsHipError("conv weight must be [*,*,3,3,3], got %s" % (tuple(weight.shape),))
     cin, cout = (weight.shape[0], weight.shape[1]) if transposed else (weight.shape[1], weight.shape[0])
     n = _lib.load().mvs_conv3d_packed_floats(cin, cout, mode)
-    if n <= 0:
-        raise _lib.MvsHipError("unsupported conv channels Cin=%d Cout=%d" % (cin, cout))
-    packed = torch.empty(n, device=weight.device, dtype=torch.float32)
-    _call("mvs_conv3d_pack_weights", None, _ptr(weight), cin, cout, mode, _ptr(packed), _stream())
-    return packed
+    return _packed("mvs_conv3d_pack_weights", n, True, "unsupported conv channels Cin=%d Cout=%d", (cin, cout), weight, torch.float32,
+                   _ptr(weight), cin, cout, mode)
+
+
+def _strided(sd: int, shw: int):
+    """Output-grid rule of a convolution with padding 1 and stride ``(sd, shw, shw)``."""
+    return lambda D, H, W: ((D - 1) // sd + 1, (H - 1) // shw + 1, (W - 1) // shw + 1)
+
+
+def _upsampled(fd: int, fhw: int):
+    """Output-grid rule of a transposed convolution with stride ``(fd, fhw, fhw)``."""
+    return lambda D, H, W: (D * fd, H * fhw, W * fhw)
+
+
+def _conv3d_layer(entry: str, kernel: str, x, wpacked, wdtype, cin, cout, grid, ints, scale, shift, residual, relu, transposed=False,
+                  residual_msg: str = _RESIDUAL_MSG):
+    """The body of every 3-D layer wrapper (convolution -> folded BatchNorm -> ReLU [+ residual]): ``x [B,cin,D,H,W]`` and weights packed as
+    ``wdtype`` -> ``y [B,cout,*grid(D,H,W)]`` by ``entry(x, wpacked, scale, shift, residual, y, B, cin, cout, D, H, W, *ints, relu, stream)``.
+    The timer tag ``kernel`` is credited with the 27 taps of every output voxel, or with ``transposed`` of every input voxel."""
+    _chk(x, "x"), _chk(wpacked, "packed weights", wdtype), _opt(scale, "scale"), _opt(shift, "shift")
+    B, C, D, H, W = x.shape
+    assert C == cin
+    Do, Ho, Wo = grid(D, H, W)
+    y = _new(x, B, cout, Do, Ho, Wo)
+    _chk_residual(residual, y.shape, msg=residual_msg)
+    tag = (kernel, "flops", 2.0 * 27 * cin * cout * B * (D * H * W if transposed else Do * Ho * Wo))
+    _call(entry, tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin, cout, D, H, W, *ints, int(relu), _stream())
+    return y
 
 
 def conv3d(x, wpacked, cin, cout, stride, scale=None, shift=None, residual=None, relu=True, tag=None):
-    _chk(x, "x"), _chk(wpacked, "packed weights"), _opt(scale, "scale"), _opt(shift, "shift")
-    B, C, Di, Hi, Wi = x.shape
-    assert C == cin
     sd, shw = stride
-    Do, Ho, Wo = (Di - 1) // sd + 1, (Hi - 1) // shw + 1, (Wi - 1) // shw + 1
-    y = torch.empty(B, cout, Do, Ho, Wo, device=x.device, dtype=torch.float32)
-    if residual is not None:
-        _chk(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
-    tag = ("conv3d_kernel<%d,%d,%d>" % (_nt(cout), sd, shw), "flops", 2.0 * 27 * cin * cout * B * Do * Ho * Wo)
-    _call("mvs_conv3d_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin, cout,
-          Di, Hi, Wi, sd, shw, int(relu), _stream())
-    return y
+    return _conv3d_layer("mvs_conv3d_fwd", "conv3d_kernel<%d,%d,%d>" % (_nt(cout), sd, shw), x, wpacked, torch.float32, cin, cout,
+                         _strided(sd, shw), (sd, shw), scale, shift, residual, relu)
 
 
 def conv3d_wino_supported(cin: int, cout: int, D: int, H: int, W: int) -> bool:
@@ -587,27 +613,14 @@ def conv3d_wino_pack(weight: torch.Tensor) -> torch.Tensor:
     _chk(weight, "conv weight")
     cout, cin = weight.shape[0], weight.shape[1]
     n = _lib.load().mvs_conv3d_wino_packed_floats(cin, cout)
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or n <= 0:
-        raise _lib.MvsHipError("conv3d_wino_pack: unsupported weight %s" % (tuple(weight.shape),))
-    packed = torch.empty(n, device=weight.device, dtype=torch.float32)
-    _call("mvs_conv3d_wino_pack_weights", None, _ptr(weight), cin, cout, _ptr(packed), _stream())
-    return packed
+    return _packed("mvs_conv3d_wino_pack_weights", n, weight.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3),
+                   "conv3d_wino_pack: unsupported weight %s", (tuple(weight.shape),), weight, torch.float32, _ptr(weight), cin, cout)
 
 
 def conv3d_wino(x, wpacked, cin, cout, scale=None, shift=None, residual=None, relu=True):
-    _chk(x, "x"), _chk(wpacked, "packed weights"), _opt(scale, "scale"), _opt(shift, "shift")
-    B, C, D, H, W = x.shape
-    assert C == cin
-    y = torch.empty(B, cout, D, H, W, device=x.device, dtype=torch.float32)
-    if residual is not None:
-        _chk(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
     # work is credited as the direct convolution's FLOPs (the algorithmic figure), not the 2.25x fewer executed
-    tag = ("wino_conv3d_kernel", "flops", 2.0 * 27 * cin * cout * B * D * H * W)
-    _call("mvs_conv3d_wino_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin, cout, D, H, W,
-          int(relu), _stream())
-    return y
+    return _conv3d_layer("mvs_conv3d_wino_fwd", "wino_conv3d_kernel", x, wpacked, torch.float32, cin, cout, _strided(1, 1), (),
+                         scale, shift, residual, relu)
 
 
 def conv3d_x3_supported(cin: int, cout: int, stride) -> bool:
@@ -621,30 +634,17 @@ def conv3d_x3_pack(weight: torch.Tensor, stride=(1, 1)) -> torch.Tensor:
     cout, cin = weight.shape[0], weight.shape[1]
     sd, shw = int(stride[0]), int(stride[1])
     n = int(_lib.load().mvs_conv3d_x3_packed_bytes(cin, cout, sd, shw))
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or n <= 0:
-        raise _lib.MvsHipError("conv3d_x3_pack: unsupported weight %s / stride %s" % (tuple(weight.shape), (sd, shw)))
-    packed = torch.empty(n, device=weight.device, dtype=torch.uint8)
-    _call("mvs_conv3d_x3_pack_weights", None, _ptr(weight), cin, cout, sd, shw, _ptr(packed), _stream())
-    return packed
+    return _packed("mvs_conv3d_x3_pack_weights", n, weight.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3),
+                   "conv3d_x3_pack: unsupported weight %s / stride %s", (tuple(weight.shape), (sd, shw)), weight, torch.uint8,
+                   _ptr(weight), cin, cout, sd, shw)
 
 
 def conv3d_x3(x, wpacked, cin, cout, stride=(1, 1), scale=None, shift=None, residual=None, relu=True):
     """``Conv3d`` layer (conv, stride (1,s,s) -> folded BatchNorm -> ReLU [+ residual]) on the bf16 matrix cores in 3-term split form:
     fp32 in, fp32 out, fp32-equivalent (include/mvs_hip.h)."""
-    _chk(x, "x"), _chk(wpacked, "packed weights", torch.uint8), _opt(scale, "scale"), _opt(shift, "shift")
-    B, C, D, H, W = x.shape
-    assert C == cin
     sd, shw = int(stride[0]), int(stride[1])
-    Ho, Wo = (H - 1) // shw + 1, (W - 1) // shw + 1
-    y = torch.empty(B, cout, D, Ho, Wo, device=x.device, dtype=torch.float32)
-    if residual is not None:
-        _chk(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
-    tag = ("x3_conv_kernel<%d,%d,s%d>" % (cin, cout, shw), "flops", 2.0 * 27 * cin * cout * B * D * Ho * Wo)
-    _call("mvs_conv3d_x3_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin, cout, D, H, W, sd, shw,
-          int(relu), _stream())
-    return y
+    return _conv3d_layer("mvs_conv3d_x3_fwd", "x3_conv_kernel<%d,%d,s%d>" % (cin, cout, shw), x, wpacked, torch.uint8, cin, cout,
+                         _strided(1, shw), (sd, shw), scale, shift, residual, relu)
 
 
 def deconv3d_x3_supported(cin: int, cout: int, sd: int) -> bool:
@@ -656,44 +656,22 @@ def deconv3d_x3_pack(weight: torch.Tensor, sd: int = 1) -> torch.Tensor:
     _chk(weight, "deconv weight")
     cin, cout = weight.shape[0], weight.shape[1]
     n = int(_lib.load().mvs_deconv3d_x3_packed_bytes(cin, cout, int(sd)))
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or n <= 0:
-        raise _lib.MvsHipError("deconv3d_x3_pack: unsupported weight %s / sd %d" % (tuple(weight.shape), sd))
-    packed = torch.empty(n, device=weight.device, dtype=torch.uint8)
-    _call("mvs_deconv3d_x3_pack_weights", None, _ptr(weight), cin, cout, int(sd), _ptr(packed), _stream())
-    return packed
+    return _packed("mvs_deconv3d_x3_pack_weights", n, weight.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3),
+                   "deconv3d_x3_pack: unsupported weight %s / sd %d", (tuple(weight.shape), sd), weight, torch.uint8,
+                   _ptr(weight), cin, cout, int(sd))
 
 
 def deconv3d_x3(x, wpacked, cin, cout, sd=1, scale=None, shift=None, residual=None, relu=True):
     """Transposed-conv layer (stride (1,2,2)) -> folded BatchNorm -> ReLU [+ residual] in 3-term bf16 split form (include/mvs_hip.h)."""
-    _chk(x, "x"), _chk(wpacked, "packed weights", torch.uint8), _opt(scale, "scale"), _opt(shift, "shift")
-    B, C, D, H, W = x.shape
-    assert C == cin
-    y = torch.empty(B, cout, D, 2 * H, 2 * W, device=x.device, dtype=torch.float32)
-    if residual is not None:
-        _chk(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
-    tag = ("x3_deconv_kernel<%d,%d>" % (cin, cout), "flops", 2.0 * 27 * cin * cout * B * D * H * W)
-    _call("mvs_deconv3d_x3_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin, cout, D, H, W, int(sd),
-          int(relu), _stream())
-    return y
+    return _conv3d_layer("mvs_deconv3d_x3_fwd", "x3_deconv_kernel<%d,%d>" % (cin, cout), x, wpacked, torch.uint8, cin, cout,
+                         _upsampled(1, 2), (int(sd),), scale, shift, residual, relu, transposed=True)
 
 
 def deconv3d(x, wpacked, cin, cout, sd, scale=None, shift=None, residual=None, relu=True, tag=None):
-    _chk(x, "x"), _chk(wpacked, "packed weights"), _opt(scale, "scale"), _opt(shift, "shift")
-    B, C, Di, Hi, Wi = x.shape
-    assert C == cin
-    y = torch.empty(B, cout, Di * sd, Hi * 2, Wi * 2, device=x.device, dtype=torch.float32)
-    if residual is not None:
-        _chk(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s (stage H, W must be divisible by 8%s)" % (
-                tuple(residual.shape), tuple(y.shape), ", D by 8" if sd == 2 else ""))
     name = "deconv3d_s1_kernel<%d>" % cout if (sd == 1 and cout in (8, 16)) else "deconv3d_kernel<%d,%d>" % (_nt(cout), sd)
-    tag = (name, "flops", 2.0 * 27 * cin * cout * B * Di * Hi * Wi)
-    _call("mvs_deconv3d_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin,
-          cout, Di, Hi, Wi, sd, int(relu), _stream())
-    return y
+    return _conv3d_layer("mvs_deconv3d_fwd", name, x, wpacked, torch.float32, cin, cout, _upsampled(sd, 2), (sd,),
+                         scale, shift, residual, relu, transposed=True,
+                         residual_msg=_RESIDUAL_MSG + " (stage H, W must be divisible by 8%s)" % (", D by 8" if sd == 2 else ""))
 
 
 def deconv3d_prob1(x, wpacked, cin, scale, shift, residual, prob_w, prob_b, relu=True):
@@ -702,11 +680,8 @@ def deconv3d_prob1(x, wpacked, cin, scale, shift, residual, prob_w, prob_b, relu
     _opt(scale, "scale"), _opt(shift, "shift")
     B, C, Di, Hi, Wi = x.shape
     assert C == cin
-    if residual is not None:
-        _chk(residual, "residual")
-        if tuple(residual.shape) != (B, 8, Di, 2 * Hi, 2 * Wi):
-            raise _lib.MvsHipError("residual shape %s != %s" % (tuple(residual.shape), (B, 8, Di, 2 * Hi, 2 * Wi)))
-    logits = torch.empty(B, Di, 2 * Hi, 2 * Wi, device=x.device, dtype=torch.float32)
+    _chk_residual(residual, (B, 8, Di, 2 * Hi, 2 * Wi), msg="residual shape %s != %s")
+    logits = _new(x, B, Di, 2 * Hi, 2 * Wi)
     tag = ("deconv3d_s1_kernel<8,prob>", "flops", 2.0 * 27 * cin * 8 * B * Di * Hi * Wi)
     _call("mvs_deconv3d_prob1_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(prob_w), _ptr(prob_b),
           _ptr(logits), B, cin, Di, Hi, Wi, int(relu), _stream())
@@ -722,33 +697,17 @@ def conv3d_small_pack(weight: torch.Tensor, stride: int, transposed: bool) -> to
     _chk(weight, "conv weight")
     cin, cout = (weight.shape[0], weight.shape[1]) if transposed else (weight.shape[1], weight.shape[0])
     n = int(_lib.load().mvs_conv3d_small_packed_bytes(cin, cout, int(stride), int(bool(transposed))))
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or n <= 0:
-        raise _lib.MvsHipError("conv3d_small_pack: unsupported weight %s / stride %d / transposed %s" % (tuple(weight.shape), stride, transposed))
-    packed = torch.empty(n, device=weight.device, dtype=torch.uint8)
-    _call("mvs_conv3d_small_pack_weights", None, _ptr(weight), cin, cout, int(stride), int(bool(transposed)), _ptr(packed), _stream())
-    return packed
+    return _packed("mvs_conv3d_small_pack_weights", n, weight.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3),
+                   "conv3d_small_pack: unsupported weight %s / stride %d / transposed %s", (tuple(weight.shape), stride, transposed), weight,
+                   torch.uint8, _ptr(weight), cin, cout, int(stride), int(bool(transposed)))
 
 
 def conv3d_small(x, wpacked, cin, cout, stride, transposed, scale=None, shift=None, residual=None, relu=True):
     """Small-volume split-form (transposed) convolution layer -> folded BatchNorm -> ReLU [+ residual] (include/mvs_hip.h)."""
-    _chk(x, "x"), _chk(wpacked, "packed weights", torch.uint8), _opt(scale, "scale"), _opt(shift, "shift")
-    B, C, D, H, W = x.shape
-    assert C == cin
     s = int(stride)
-    if transposed:
-        oshape = (B, cout, 2 * D, 2 * H, 2 * W)
-    else:
-        oshape = (B, cout, (D - 1) // s + 1, (H - 1) // s + 1, (W - 1) // s + 1)
-    y = torch.empty(oshape, device=x.device, dtype=torch.float32)
-    if residual is not None:
-        _chk(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
-    flops = 2.0 * 27 * cin * cout * B * (D * H * W if transposed else y[0, 0].numel())
-    tag = ("x3_small_kernel<%s,%d,%d,s%d>" % ("deconv" if transposed else "conv", cin, cout, s), "flops", flops)
-    _call("mvs_conv3d_small_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), B, cin, cout, D, H, W, s,
-          int(bool(transposed)), int(relu), _stream())
-    return y
+    return _conv3d_layer("mvs_conv3d_small_fwd", "x3_small_kernel<%s,%d,%d,s%d>" % ("deconv" if transposed else "conv", cin, cout, s),
+                         x, wpacked, torch.uint8, cin, cout, _upsampled(2, 2) if transposed else _strided(s, s), (s, int(bool(transposed))), scale, shift, residual, relu,
+                         transposed=bool(transposed))
 
 
 def tail_x3_pack(weight: torch.Tensor) -> torch.Tensor:
@@ -756,7 +715,7 @@ def tail_x3_pack(weight: torch.Tensor) -> torch.Tensor:
     _chk(weight, "conv11 weight")
     if tuple(weight.shape) != (16, 8, 3, 3, 3):
         raise _lib.MvsHipError("tail_x3_pack: weight %s is not [16,8,3,3,3]" % (tuple(weight.shape),))
-    packed = torch.empty(int(_lib.load().mvs_tail_x3_packed_bytes()), device=weight.device, dtype=torch.uint8)
+    packed = _new(weight, int(_lib.load().mvs_tail_x3_packed_bytes()), dtype=torch.uint8)
     _call("mvs_tail_x3_pack_weights", None, _ptr(weight), _ptr(packed), _stream())
     return packed
 
@@ -768,11 +727,8 @@ def tail_x3(x, wpacked, scale, shift, residual, prob_w, prob_b, relu=True):
     B, C, D, H, W = x.shape
     if C != 16:
         raise _lib.MvsHipError("tail_x3: %d input channels (built for 16)" % C)
-    if residual is not None:
-        _chk(residual, "residual")
-        if tuple(residual.shape) != (B, 8, D, 2 * H, 2 * W):
-            raise _lib.MvsHipError("residual shape %s != %s" % (tuple(residual.shape), (B, 8, D, 2 * H, 2 * W)))
-    logits = torch.empty(B, D, 2 * H, 2 * W, device=x.device, dtype=torch.float32)
+    _chk_residual(residual, (B, 8, D, 2 * H, 2 * W), msg="residual shape %s != %s")
+    logits = _new(x, B, D, 2 * H, 2 * W)
     tag = ("x3_tail_kernel<16,8,prob>", "flops", 2.0 * 27 * 16 * 8 * B * D * H * W)
     _call("mvs_tail_x3_fwd", tag, _ptr(x), _ptr(wpacked), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(prob_w), _ptr(prob_b),
           _ptr(logits), B, D, H, W, int(relu), _stream())
@@ -782,7 +738,7 @@ def tail_x3(x, wpacked, scale, shift, residual, prob_w, prob_b, relu=True):
 def prob3(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     _chk(x, "x"), _chk(w, "prob weight")
     B, C, D, H, W = x.shape
-    out = torch.empty(B, D, H, W, device=x.device, dtype=torch.float32)
+    out = _new(x, B, D, H, W)
     _call("mvs_prob3_fwd", ("prob3_kernel", "flops", 2.0 * 27 * C * B * D * H * W), _ptr(x), _ptr(w), B, C, D, H, W, _ptr(out), _stream())
     return out
 
@@ -793,14 +749,14 @@ def head(depth_values: torch.Tensor, tmp: float, training: bool, logits: Optiona
     _chk(depth_values, "depth_values")
     B, D, H, W = depth_values.shape
     dev = depth_values.device
-    prob = torch.empty(B, D, H, W, device=dev, dtype=torch.float32)
-    depth = torch.empty(B, H, W, device=dev, dtype=torch.float32)
-    conf = torch.empty(B, H, W, device=dev, dtype=torch.float32)
+    prob = _new(dev, B, D, H, W)
+    depth = _new(dev, B, H, W)
+    conf = _new(dev, B, H, W)
     if x8 is not None:
         _chk(x8, "x8"), _chk(w1, "prob.weight"), _chk(b1, "prob.bias")
         if x8.shape[0] != B or tuple(x8.shape[2:]) != (D, H, W):
             raise _lib.MvsHipError("x8 %s does not match depth_values %s" % (tuple(x8.shape), tuple(depth_values.shape)))
-        pre = torch.empty(B, D, H, W, device=dev, dtype=torch.float32)
+        pre = _new(dev, B, D, H, W)
         _call("mvs_head_fwd", None, None, _ptr(x8), _ptr(w1), _ptr(b1), x8.shape[1], _ptr(depth_values), float(tmp), int(training),
               B, D, H, W, _ptr(pre), _ptr(prob), _ptr(depth), _ptr(conf), _stream())
     else:
@@ -819,7 +775,7 @@ def depth_regression(p: torch.Tensor, depth_values: torch.Tensor) -> torch.Tenso
     per_pixel = depth_values.dim() == 4
     if (per_pixel and depth_values.shape != p.shape) or (not per_pixel and depth_values.shape != (B, D)):
         raise _lib.MvsHipError("depth_values %s does not match p %s" % (tuple(depth_values.shape), tuple(p.shape)))
-    out = torch.empty(B, H, W, device=p.device, dtype=torch.float32)
+    out = _new(p, B, H, W)
     _call("mvs_depth_regression", None, _ptr(p), _ptr(depth_values), int(per_pixel), B, D, H, W, _ptr(out), _stream())
     return out
 
@@ -827,7 +783,7 @@ def depth_regression(p: torch.Tensor, depth_values: torch.Tensor) -> torch.Tenso
 def conf_regression(p: torch.Tensor, n: int) -> torch.Tensor:
     _chk(p, "p")
     B, D, H, W = p.shape
-    out = torch.empty(B, H, W, device=p.device, dtype=torch.float32)
+    out = _new(p, B, H, W)
     _call("mvs_conf_regression", None, _ptr(p), int(n), B, D, H, W, _ptr(out), _stream())
     return out
 
@@ -838,8 +794,8 @@ def mixup_head(p: torch.Tensor, depth_values: torch.Tensor):
     if p.shape != depth_values.shape or p.dim() != 4:
         raise _lib.MvsHipError("mixup_head: p %s / depth_values %s must both be [B,D,H,W]" % (tuple(p.shape), tuple(depth_values.shape)))
     B, D, H, W = p.shape
-    depth = torch.empty(B, H, W, device=p.device, dtype=torch.float32)
-    conf = torch.empty(B, H, W, device=p.device, dtype=torch.float32)
+    depth = _new(p, B, H, W)
+    conf = _new(p, B, H, W)
     _call("mvs_mixup_head", None, _ptr(p), _ptr(depth_values), B, D, H, W, _ptr(depth), _ptr(conf), _stream())
     return depth, conf
 
@@ -847,17 +803,21 @@ def mixup_head(p: torch.Tensor, depth_values: torch.Tensor):
 def prob1(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     _chk(x, "x"), _chk(w, "prob.weight")
     B, C, D, H, W = x.shape
-    out = torch.empty(B, 1, D, H, W, device=x.device, dtype=torch.float32)
+    out = _new(x, B, 1, D, H, W)
     _call("mvs_prob1_fwd", None, _ptr(x), _ptr(w), _ptr(bias), B, C, D * H * W, _ptr(out), _stream())
     return out
 
 
-def init_inverse_range(depth_range: torch.Tensor, ndepths: int, H: int, W: int) -> torch.Tensor:
+def _init_range(entry: str, depth_range: torch.Tensor, ndepths: int, H: int, W: int) -> torch.Tensor:
     _chk(depth_range, "depth_values")
     B, N = depth_range.shape
-    hyp = torch.empty(B, ndepths, H, W, device=depth_range.device, dtype=torch.float32)
-    _call("mvs_init_inverse_range", None, _ptr(depth_range), N, B, ndepths, H, W, _ptr(hyp), _stream())
+    hyp = _new(depth_range, B, ndepths, H, W)
+    _call(entry, None, _ptr(depth_range), N, B, ndepths, H, W, _ptr(hyp), _stream())
     return hyp
+
+
+def init_inverse_range(depth_range: torch.Tensor, ndepths: int, H: int, W: int) -> torch.Tensor:
+    return _init_range("mvs_init_inverse_range", depth_range, ndepths, H, W)
 
 
 def schedule_inverse_range(prev_depth: torch.Tensor, prev_hyp: torch.Tensor, ndepths: int, split_itv: float, H: int, W: int):
@@ -866,18 +826,14 @@ def schedule_inverse_range(prev_depth: torch.Tensor, prev_hyp: torch.Tensor, nde
     if prev_depth.shape != (B, Hl, Wl) or (Hl, Wl) != (H // 2, W // 2):
         raise _lib.MvsHipError("schedule_inverse_range: previous stage %s / %s is not half of (%d,%d)" % (
             tuple(prev_depth.shape), tuple(prev_hyp.shape), H, W))
-    hyp = torch.empty(B, ndepths, H, W, device=prev_depth.device, dtype=torch.float32)
+    hyp = _new(prev_depth, B, ndepths, H, W)
     _call("mvs_schedule_inverse_range", None, _ptr(prev_depth), _ptr(prev_hyp), Dp, float(split_itv), B, ndepths, H, W, _ptr(hyp), _stream())
     return hyp
 
 
 def init_range(depth_range: torch.Tensor, ndepths: int, H: int, W: int) -> torch.Tensor:
     """Linear-depth hypotheses of stage 1 (reference module.py:622-630): ``[B,ndepths,H,W]`` ascending from ``depth_range[:,0]`` to ``[:,-1]``."""
-    _chk(depth_range, "depth_values")
-    B, N = depth_range.shape
-    hyp = torch.empty(B, ndepths, H, W, device=depth_range.device, dtype=torch.float32)
-    _call("mvs_init_range", None, _ptr(depth_range), N, B, ndepths, H, W, _ptr(hyp), _stream())
-    return hyp
+    return _init_range("mvs_init_range", depth_range, ndepths, H, W)
 
 
 def schedule_range(prev_depth: torch.Tensor, depth_interval: torch.Tensor, ndepths: int, ratio: float, H: int, W: int) -> torch.Tensor:
@@ -888,7 +844,7 @@ def schedule_range(prev_depth: torch.Tensor, depth_interval: torch.Tensor, ndept
         raise _lib.MvsHipError("schedule_range: previous stage %s / interval %s is not half of (%d,%d) with one interval per sample" % (
             tuple(prev_depth.shape), tuple(depth_interval.shape), H, W))
     B = prev_depth.shape[0]
-    hyp = torch.empty(B, ndepths, H, W, device=prev_depth.device, dtype=torch.float32)
+    hyp = _new(prev_depth, B, ndepths, H, W)
     _call("mvs_schedule_range", None, _ptr(prev_depth), _ptr(depth_interval), float(ratio), B, ndepths, H, W, _ptr(hyp), _stream())
     return hyp
 
@@ -911,8 +867,8 @@ def reg_head_fwd(pre: torch.Tensor, depth_values: torch.Tensor, want_conf: bool 
     """Regression training head (reference mvsformer_model.py:111,138) -> (prob_volume, depth, max-probability confidence or None)."""
     B, D, H, W = _head_train_args(pre, depth_values, "prob_volume_pre")
     prob = torch.empty_like(pre)
-    depth = torch.empty(B, H, W, device=pre.device, dtype=torch.float32)
-    conf = torch.empty(B, H, W, device=pre.device, dtype=torch.float32) if want_conf else None
+    depth = _new(pre, B, H, W)
+    conf = _new(pre, B, H, W) if want_conf else None
     _call("mvs_reg_head_fwd", None, _ptr(pre), _ptr(depth_values), B, D, H, W, _ptr(prob), _ptr(depth), _ptr(conf), _stream())
     return prob, depth, conf
 
@@ -930,9 +886,9 @@ def mixup_train_fwd(pre: torch.Tensor, depth_values: torch.Tensor):
     """'mixup_ce' training head (reference mvsformer_model.py:111,126-136) -> (prob_volume, depth, confidence, winning pair index int32 [B,H,W])."""
     B, D, H, W = _head_train_args(pre, depth_values, "prob_volume_pre")
     prob = torch.empty_like(pre)
-    depth = torch.empty(B, H, W, device=pre.device, dtype=torch.float32)
-    conf = torch.empty(B, H, W, device=pre.device, dtype=torch.float32)
-    pair = torch.empty(B, H, W, device=pre.device, dtype=torch.int32)
+    depth = _new(pre, B, H, W)
+    conf = _new(pre, B, H, W)
+    pair = _new(pre, B, H, W, dtype=torch.int32)
     _call("mvs_mixup_train_fwd", None, _ptr(pre), _ptr(depth_values), B, D, H, W, _ptr(prob), _ptr(depth), _ptr(conf), _ptr(pair), _stream())
     return prob, depth, conf, pair
 
@@ -974,7 +930,7 @@ def conf_stack(confs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     if H % 8 or W % 8 or any(tuple(cs[k].shape) != (H >> (3 - k), W >> (3 - k)) for k in range(4)):
         raise _lib.MvsHipError("conf_stack: stage maps %s are not H/8, H/4, H/2, H of a multiple-of-8 size" % ([tuple(c.shape) for c in cs],))
     if out is None:
-        out = torch.empty(4, H, W, device=cs[3].device, dtype=torch.float32)
+        out = _new(cs[3], 4, H, W)
     _chk(out, "confidence record")
     if tuple(out.shape) != (4, H, W):
         raise _lib.MvsHipError("conf_stack: out must be [4,%d,%d], got %s" % (H, W, tuple(out.shape)))
@@ -988,7 +944,7 @@ def _reduce_ws(fn: str, device, *shape) -> torch.Tensor:
     nbytes = getattr(_lib.load(), fn)(*shape)
     if nbytes < 0:
         raise _lib.MvsHipError("%s%r: unsupported shape" % (fn, shape))
-    return torch.empty(max(int(nbytes) // 4, 1), device=device, dtype=torch.float32)
+    return _new(device, max(int(nbytes) // 4, 1))
 
 
 def bn_stats(x: torch.Tensor) -> torch.Tensor:
@@ -996,7 +952,7 @@ def bn_stats(x: torch.Tensor) -> torch.Tensor:
     _chk(x, "x")
     B, C = x.shape[0], x.shape[1]
     N = x.numel() // (B * C)
-    sums = torch.empty(2 * C, device=x.device, dtype=torch.float64)
+    sums = _new(x, 2 * C, dtype=torch.float64)
     ws = _reduce_ws("mvs_bn_reduce_workspace_bytes", x.device, B, C, N)
     _call("mvs_bn_stats", None, _ptr(x), B, C, N, _ptr(sums), _ptr(ws), _stream())
     return sums
@@ -1006,7 +962,7 @@ def _bn_finalize(entry, dims, sums, gamma, beta, running_mean, running_var, mome
     """The body of both finalize calls: ``dims`` = the entry point's channel arguments, ``(C,)`` or ``(C, groups)``."""
     _chk(sums, "sums", dtype=torch.float64), _opt(gamma, "bn.weight"), _opt(beta, "bn.bias"), _opt(running_mean, "bn.running_mean")
     _opt(running_var, "bn.running_var"), _opt(count_dev, "count_dev")
-    scale, shift, mean, invstd = (torch.empty(sums.numel() // 2, device=sums.device, dtype=torch.float32) for _ in range(4))
+    scale, shift, mean, invstd = (_new(sums, sums.numel() // 2) for _ in range(4))
     if running_mean is not None:
         bump_weights_epoch()                                 # running statistics are written through raw pointers
     _call(entry, None, _ptr(sums), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), float(count),
@@ -1038,7 +994,7 @@ def bn_bwd_reduce(dy, x, scale, shift, mean, invstd, relu):
     _chk(dy, "dy"), _chk(x, "x")
     B, C = x.shape[0], x.shape[1]
     N = x.numel() // (B * C)
-    sums = torch.empty(2 * C, device=x.device, dtype=torch.float32)
+    sums = _new(x, 2 * C)
     ws = _reduce_ws("mvs_bn_reduce_workspace_bytes", x.device, B, C, N)
     _call("mvs_bn_bwd_reduce", None, _ptr(dy), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), int(relu), B, C, N,
           _ptr(sums), _ptr(ws), _stream())
@@ -1085,7 +1041,7 @@ def cv_aggregate_bwd(feat_cl, rt, depth, weight, volume, gvolume, G: int, stats:
         own = mode == "own"
         window = sw.text("MVS_CV_BWD_WINDOW")
         wxl, wy = (int(v) for v in (("5,20" if own else "6,24") if window is None else window).split(","))
-        part = torch.empty((C // 8,) + tuple(weight.shape), device=weight.device, dtype=torch.float32)
+        part = _new(weight, (C // 8,) + tuple(weight.shape))
         fn = "mvs_cv_aggregate_bwd_own" if own else "mvs_cv_aggregate_bwd_lds"
         _call(fn, "cv_aggregate_bwd_%s_kernel<%d>" % (mode, C), _ptr(feat_cl), _ptr(rt), _ptr(depth), _ptr(weight),
               _ptr(volume), _ptr(gvolume), B, V, C, G, D, H, W, _ptr(dfeat), _ptr(part), wxl, wy, _ptr(stats), _stream())
@@ -1099,7 +1055,7 @@ def cv_aggregate_bwd(feat_cl, rt, depth, weight, volume, gvolume, G: int, stats:
 def to_channels_first(feat_cl: torch.Tensor) -> torch.Tensor:
     _chk(feat_cl, "features")
     B, V, H, W, C = feat_cl.shape
-    out = torch.empty(B, V, C, H, W, device=feat_cl.device, dtype=torch.float32)
+    out = _new(feat_cl, B, V, C, H, W)
     _call("mvs_nhwc_to_nchw", None, _ptr(feat_cl), _ptr(out), B * V, C, H * W, _stream())
     return out
 
@@ -1147,7 +1103,7 @@ def geo_filter(ref_depth, srcs_depth, ref_cam, srcs_cam, img_dist_thresh: float 
     shapes = dict(reproj_xyd=(n, v, 3, h, w), in_range=(n, v, 1, h, w), masks=(n, v, 1, h, w), mask=(n, 1, h, w),
                   ref_depth_ave=(n, 1, h, w), points=(n, 3, h, w))
     out = {k: torch.empty(shapes[k], device=dev, dtype=torch.uint8 if k == "mask" else torch.float32) for k in want}
-    ws = torch.empty(_lib.load().mvs_geo_filter_workspace_bytes(n, v), device=dev, dtype=torch.uint8)
+    ws = _new(dev, _lib.load().mvs_geo_filter_workspace_bytes(n, v), dtype=torch.uint8)
     algo = 4.0 * n * h * w * (1 + v + sum({"reproj_xyd": 3 * v, "in_range": v, "masks": v, "mask": 0.25, "ref_depth_ave": 1,
                                             "points": 3}[k] for k in want))
     _call("mvs_geo_filter_fwd", ("geo_filter", "bytes", algo), _ptr(ref_depth), _ptr(srcs_depth), _ptr(ref_cam), _ptr(srcs_cam), n, v, h,
@@ -1166,9 +1122,9 @@ def vis_filter(ref_depth, reproj_xyd, in_range, masks_in, img_dist_thresh, depth
         if t is not None:
             _chk(t, name)
     dev = ref_depth.device
-    masks = torch.empty(n, v, 1, h, w, device=dev, dtype=torch.float32) if (want_masks and masks_in is None) else None
-    mask = torch.empty(n, 1, h, w, device=dev, dtype=torch.uint8) if masks_in is None else None
-    ave = torch.empty(n, 1, h, w, device=dev, dtype=torch.float32) if want_ave else None
+    masks = _new(dev, n, v, 1, h, w) if (want_masks and masks_in is None) else None
+    mask = _new(dev, n, 1, h, w, dtype=torch.uint8) if masks_in is None else None
+    ave = _new(dev, n, 1, h, w) if want_ave else None
     _call("mvs_vis_filter_fwd", "vis_filter", _ptr(ref_depth), _ptr(reproj_xyd), _ptr(in_range), _ptr(masks_in), n, v, h, w,
           float(img_dist_thresh), float(depth_thresh), float(vthresh), _ptr(masks), _ptr(mask), _ptr(ave), _stream())
     return masks, (mask.view(torch.bool) if mask is not None else None), ave
@@ -1184,7 +1140,7 @@ def prob_filter(conf: torch.Tensor, thresh, depth_inplace: Optional[torch.Tensor
     if conf.shape[1] != C:
         conf = conf[:, :C].contiguous()
     HW = conf.numel() // (n * C)
-    mask = torch.empty((n, 1) + tuple(conf.shape[2:]), device=conf.device, dtype=torch.uint8)
+    mask = _new(conf, (n, 1) + tuple(conf.shape[2:]), dtype=torch.uint8)
     if depth_inplace is not None:
         _chk(depth_inplace, "depth")
         if depth_inplace.numel() != n * HW:
@@ -1207,7 +1163,7 @@ def geo_filter_dynamic(ref_depth, srcs_depth, ref_cam, srcs_cam, dist_base: floa
                   ref_depth_ave=(n, 1, h, w), points=(n, 3, h, w))
     isbool = ("masks", "vis_mask", "geo_mask")
     out = {k: torch.empty(shapes[k], device=dev, dtype=torch.uint8 if k in isbool else torch.float32) for k in want}
-    ws = torch.empty(_lib.load().mvs_geo_filter_workspace_bytes(n, v), device=dev, dtype=torch.uint8)
+    ws = _new(dev, _lib.load().mvs_geo_filter_workspace_bytes(n, v), dtype=torch.uint8)
     algo = n * h * w * (4.0 * (1 + v) + sum({"reproj_xyd": 12 * v, "masks": v * (v - 1), "vis_mask": v, "geo_mask": 1,
                                              "ref_depth_ave": 4, "points": 12}[k] for k in want))
     _call("mvs_geo_filter_dynamic_fwd", ("geo_filter_dynamic", "bytes", algo), _ptr(ref_depth), _ptr(srcs_depth), _ptr(ref_cam),
@@ -1275,7 +1231,7 @@ def geo_filter_scene(table: JobTable, depth_ref, depth_src, cams, img_dist_thres
     dev, R, V = depth_ref.device, table.R, table.Vmax
     shapes = dict(mask=(R, h, w), ref_depth_ave=(R, h, w), points=(R, 3, h, w))
     out = {k: torch.empty(shapes[k], device=dev, dtype=torch.uint8 if k == "mask" else torch.float32) for k in want}
-    ws = torch.empty(_lib.load().mvs_geo_filter_scene_workspace_bytes(R, V), device=dev, dtype=torch.uint8)
+    ws = _new(dev, _lib.load().mvs_geo_filter_scene_workspace_bytes(R, V), dtype=torch.uint8)
     algo = 4.0 * h * w * sum(1 + n for n in table.n_src_host) + h * w * R * sum({"mask": 1, "ref_depth_ave": 4, "points": 12}[k] for k in want)
     _call("mvs_geo_filter_scene_fwd", ("geo_filter_scene", "bytes", algo), _ptr(depth_ref), _ptr(depth_src), _ptr(cams), nv,
           _ptr(table.ref_idx), _ptr(table.src_idx), _ptr(table.n_src), R, V, h, w, float(img_dist_thresh), float(depth_thresh),
@@ -1295,7 +1251,7 @@ def geo_filter_dynamic_scene(table: JobTable, depth_ref, depth_src, cams, dist_b
     dev, R, V = depth_ref.device, table.R, table.Vmax
     shapes = dict(geo_mask=(R, h, w), ref_depth_ave=(R, h, w), points=(R, 3, h, w))
     out = {k: torch.empty(shapes[k], device=dev, dtype=torch.uint8 if k == "geo_mask" else torch.float32) for k in want}
-    ws = torch.empty(_lib.load().mvs_geo_filter_scene_workspace_bytes(R, V), device=dev, dtype=torch.uint8)
+    ws = _new(dev, _lib.load().mvs_geo_filter_scene_workspace_bytes(R, V), dtype=torch.uint8)
     algo = 4.0 * h * w * sum(1 + n for n in table.n_src_host) + h * w * R * sum({"geo_mask": 1, "ref_depth_ave": 4, "points": 12}[k]
                                                                                  for k in want)
     _call("mvs_geo_filter_dynamic_scene_fwd", ("geo_filter_dynamic_scene", "bytes", algo), _ptr(depth_ref), _ptr(depth_src), _ptr(cams),
@@ -1328,8 +1284,8 @@ def pointcloud_compact(table: JobTable, photo_mask, geo_mask, points, images=Non
         if images.shape != (nv, 3, h, w):
             raise _lib.MvsHipError("pointcloud_compact: images must be [%d,3,%d,%d], got %s" % (nv, h, w, tuple(images.shape)))
     dev, lib = points.device, _lib.load()
-    ws = torch.empty(lib.mvs_pointcloud_workspace_bytes(R, h, w) // 8 + 1, device=dev, dtype=torch.int64)
-    meta = torch.empty(1 + 3 * R, device=dev, dtype=torch.int64)            # total, then stats [R,3]: one copy to the host
+    ws = _new(dev, lib.mvs_pointcloud_workspace_bytes(R, h, w) // 8 + 1, dtype=torch.int64)
+    meta = _new(dev, 1 + 3 * R, dtype=torch.int64)            # total, then stats [R,3]: one copy to the host
     _call("mvs_pointcloud_count", ("pointcloud_count", "bytes", 2.0 * R * h * w), _ptr(photo_mask), _ptr(geo_mask), _ptr(table.ref_idx), nv,
           R, h, w, _ptr(ws), meta.data_ptr() + 8, meta.data_ptr(), _stream())
     meta_h = meta.cpu()
@@ -1370,10 +1326,10 @@ def gipuma_fuse_scene(depth, tables, table: Optional[JobTable] = None, disp_thre
     else:
         R, V, n_pairs = nv, nv - 1, nv * (nv - 1)
     dev = depth.device
-    out = dict(used=torch.empty((nv, h, w), device=dev, dtype=torch.uint8), keep=torch.empty((R, h, w), device=dev, dtype=torch.uint8),
-               points=torch.empty((R, 3, h, w), device=dev, dtype=torch.float32))
+    out = dict(used=_new(dev, (nv, h, w), dtype=torch.uint8), keep=_new(dev, (R, h, w), dtype=torch.uint8),
+               points=_new(dev, (R, 3, h, w)))
     if want_count:
-        out["count"] = torch.empty((R, h, w), device=dev, dtype=torch.uint8)
+        out["count"] = _new(dev, (R, h, w), dtype=torch.uint8)
     algo = h * w * (4.0 * n_pairs + R * (5.0 + 1.0 + 12.0 + (1.0 if want_count else 0.0)) + nv)
     _call("mvs_gipuma_fuse_scene", ("gipuma_fuse_scene", "bytes", algo), _ptr(depth), _ptr(B), _ptr(c), _ptr(A), _ptr(b), _ptr(fb), nv,
           *([_ptr(table.ref_idx), _ptr(table.src_idx), _ptr(table.n_src)] if table is not None else [None, None, None]), R, V, h, w,
@@ -1394,11 +1350,11 @@ def ce_loss(logits, depth_values, depth_gt, mask, inverse_depth: bool, weight: f
         raise _lib.MvsHipError("ce_loss: shapes %s %s %s %s" % (tuple(logits.shape), tuple(depth_values.shape), tuple(depth_gt.shape),
                                                                tuple(mask.shape)))
     dev = logits.device
-    acc = torch.empty(_lib.load().mvs_ce_loss_acc_floats(B, H * W), device=dev, dtype=torch.float32)
-    loss = torch.empty((), device=dev, dtype=torch.float32)
+    acc = _new(dev, _lib.load().mvs_ce_loss_acc_floats(B, H * W))
+    loss = _new(dev, ())
     grad = torch.empty_like(logits) if want_grad else None
-    valid = torch.empty(B, H, W, device=dev, dtype=torch.uint8) if want_index else None
-    index = torch.empty(B, H, W, device=dev, dtype=torch.int32) if want_index else None
+    valid = _new(dev, B, H, W, dtype=torch.uint8) if want_index else None
+    index = _new(dev, B, H, W, dtype=torch.int32) if want_index else None
     algo = 4.0 * B * H * W * (2 * D + 2 + (D if want_grad else 0))
     _call("mvs_ce_loss_fwd", ("ce_loss", "bytes", algo), _ptr(logits), _ptr(depth_values), _ptr(depth_gt), _ptr(mask), B, D, H * W,
           int(inverse_depth), float(weight), _ptr(grad), _ptr(acc), _ptr(loss), _ptr(valid), _ptr(index), _stream())
@@ -1415,8 +1371,8 @@ def mixup_ce_loss(logits, depth_values, depth_gt, mask, inverse_depth: bool, wei
         raise _lib.MvsHipError("mixup_ce_loss: shapes %s %s %s %s" % (tuple(logits.shape), tuple(depth_values.shape), tuple(depth_gt.shape),
                                                                      tuple(mask.shape)))
     dev = logits.device
-    acc = torch.empty(_lib.load().mvs_ce_loss_acc_floats(B, H * W), device=dev, dtype=torch.float32)
-    loss = torch.empty((), device=dev, dtype=torch.float32)
+    acc = _new(dev, _lib.load().mvs_ce_loss_acc_floats(B, H * W))
+    loss = _new(dev, ())
     grad = torch.empty_like(logits) if want_grad else None
     algo = 4.0 * B * H * W * (2 * D + 2 + (D if want_grad else 0))
     _call("mvs_mixup_ce_loss_fwd", ("mixup_ce_loss", "bytes", algo), _ptr(logits), _ptr(depth_values), _ptr(depth_gt), _ptr(mask), B, D, H * W,
@@ -1434,8 +1390,8 @@ def reg_loss(depth, depth_gt, mask, interval, depth_values=None, inverse_depth: 
             (depth_values is not None and (depth_values.shape[0] != B or tuple(depth_values.shape[2:]) != (H, W))):
         raise _lib.MvsHipError("reg_loss: shapes %s %s %s %s" % (tuple(depth.shape), tuple(depth_gt.shape), tuple(mask.shape), tuple(interval.shape)))
     dev = depth.device
-    acc = torch.empty(_lib.load().mvs_ce_loss_acc_floats(B, H * W), device=dev, dtype=torch.float32)
-    loss = torch.empty((), device=dev, dtype=torch.float32)
+    acc = _new(dev, _lib.load().mvs_ce_loss_acc_floats(B, H * W))
+    loss = _new(dev, ())
     grad = torch.empty_like(depth) if want_grad else None
     _call("mvs_reg_loss_fwd", "reg_loss", _ptr(depth), _ptr(depth_gt), _ptr(mask), _ptr(depth_values), _ptr(interval), B, D, H * W,
           int(inverse_depth), float(weight), _ptr(grad), _ptr(acc), _ptr(loss), _stream())
@@ -1450,8 +1406,8 @@ def was_loss(prob, depth_values, depth_gt, mask, ot_iter: int = 10, ot_eps: floa
     if depth_values.shape != prob.shape or depth_gt.shape != (B, H, W) or mask.shape != (B, H, W):
         raise _lib.MvsHipError("was_loss: shapes %s %s %s %s" % (tuple(prob.shape), tuple(depth_values.shape), tuple(depth_gt.shape), tuple(mask.shape)))
     dev = prob.device
-    acc = torch.empty(_lib.load().mvs_was_loss_acc_floats(B, H * W), device=dev, dtype=torch.float32)
-    loss = torch.empty((), device=dev, dtype=torch.float32)
+    acc = _new(dev, _lib.load().mvs_was_loss_acc_floats(B, H * W))
+    loss = _new(dev, ())
     grad = torch.empty_like(prob) if want_grad else None
     _call("mvs_was_loss_fwd", "was_loss", _ptr(prob), _ptr(depth_values), _ptr(depth_gt), _ptr(mask), B, D, H * W, int(ot_iter), float(ot_eps), float(weight),
           _ptr(grad), _ptr(acc), _ptr(loss), _stream())
@@ -1467,8 +1423,8 @@ def ce_loss_bwd_scale(grad, acc, gout, weight: float) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------- depth metrics (utils.py:119-182)
-DEPTH_METRICS_BLOCK_PIXELS = 1024                            # MVS_DEPTH_METRICS_BLOCK_PIXELS: pixels one block of the first launch covers
-DEPTH_METRICS_MAX_K = 8                                      # MVS_DEPTH_METRICS_MAX_K
+DEPTH_METRICS_BLOCK_PIXELS = _H["MVS_DEPTH_METRICS_BLOCK_PIXELS"]        # pixels one block of the first launch covers
+DEPTH_METRICS_MAX_K = _H["MVS_DEPTH_METRICS_MAX_K"]
 
 
 def depth_metrics(depth_est, depth_gt, mask, thresholds=None, band=None, meter_sums=None, meter_count=None, meter_n: float = 1.0):
@@ -1500,10 +1456,10 @@ def depth_metrics(depth_est, depth_gt, mask, thresholds=None, band=None, meter_s
     nacc = _lib.load().mvs_depth_metrics_acc_floats(B, H * W)
     if nacc < 0:
         raise _lib.MvsHipError("depth_metrics: bad shape %s" % (tuple(depth_est.shape),))
-    acc = torch.empty(nacc, device=dev, dtype=torch.float32)
-    counts = torch.empty(B, 2 + K, device=dev, dtype=torch.int32)
-    per_image = torch.empty(B, 1 + K, device=dev, dtype=torch.float32)
-    batch = torch.empty(1 + K, device=dev, dtype=torch.float32)
+    acc = _new(dev, nacc)
+    counts = _new(dev, B, 2 + K, dtype=torch.int32)
+    per_image = _new(dev, B, 1 + K)
+    batch = _new(dev, 1 + K)
     lo, hi = (float(band[0]), float(band[1])) if band is not None else (0.0, 0.0)
     algo = float(B * H * W) * (8 + (1 if byte else 4))
     _call("mvs_depth_metrics", ("depth_metrics", "bytes", algo), _ptr(depth_est), _ptr(depth_gt), _ptr(mask), int(byte), _ptr(thresholds if K else None),
@@ -1513,11 +1469,11 @@ def depth_metrics(depth_est, depth_gt, mask, thresholds=None, band=None, meter_s
 
 
 # ------------------------------------------------------------------------------------- point-cloud evaluation (csrc/cloud_eval.hip)
-CLOUD_GRID_RECORD_BYTES = 128                                # MVS_CLOUD_GRID_RECORD_BYTES
-CLOUD_SCORE_RECORD_BYTES = 128                               # MVS_CLOUD_SCORE_RECORD_BYTES
-CLOUD_MAX_AXIS_CELLS = 1 << 21                               # MVS_CLOUD_MAX_AXIS_CELLS
-CLOUD_MAX_SHELLS = 32                                        # MVS_CLOUD_MAX_SHELLS
-CLOUD_SCORE_MAX_K = 8                                        # MVS_CLOUD_SCORE_MAX_K
+CLOUD_GRID_RECORD_BYTES = _H["MVS_CLOUD_GRID_RECORD_BYTES"]
+CLOUD_SCORE_RECORD_BYTES = _H["MVS_CLOUD_SCORE_RECORD_BYTES"]
+CLOUD_MAX_AXIS_CELLS = _H["MVS_CLOUD_MAX_AXIS_CELLS"]
+CLOUD_MAX_SHELLS = _H["MVS_CLOUD_MAX_SHELLS"]
+CLOUD_SCORE_MAX_K = _H["MVS_CLOUD_SCORE_MAX_K"]
 
 
 def _chk_cloud(t, name: str) -> torch.Tensor:
@@ -1531,7 +1487,7 @@ def cloud_bounds(pts):
     """``pts [N,3]`` (N >= 1) -> ``(grid record (device), bounds: 6 floats on the host (min xyz, max xyz over the finite points), number of
     non-finite points)``.  One host synchronisation: 32 bytes."""
     _chk_cloud(pts, "pts")
-    grid = torch.empty(CLOUD_GRID_RECORD_BYTES // 8, device=pts.device, dtype=torch.int64)
+    grid = _new(pts, CLOUD_GRID_RECORD_BYTES // 8, dtype=torch.int64)
     bounds, bad = (ctypes.c_float * 6)(), ctypes.c_int64(0)
     _call("mvs_cloud_bounds", ("cloud_bounds", "bytes", 12.0 * pts.shape[0]), _ptr(pts), pts.shape[0], _ptr(grid), ctypes.addressof(bounds),
           ctypes.addressof(bad), _stream())
@@ -1542,7 +1498,7 @@ def cloud_grid_keys(pts, cell: float, grid, bounds, n_bad: int) -> torch.Tensor:
     """The int64 cell key of every point (non-finite points: the largest key); refuses a bad ``cell`` or an axis of 2^21 cells or more
     before launching anything."""
     _chk_cloud(pts, "pts"), _chk(grid, "grid", torch.int64)
-    keys = torch.empty(pts.shape[0], device=pts.device, dtype=torch.int64)
+    keys = _new(pts, pts.shape[0], dtype=torch.int64)
     b = (ctypes.c_float * 6)(*bounds)
     _call("mvs_cloud_grid_keys", ("cloud_grid_keys", "bytes", 20.0 * pts.shape[0]), _ptr(pts), pts.shape[0], float(cell), ctypes.addressof(b),
           int(n_bad), _ptr(grid), _ptr(keys), _stream())
@@ -1555,10 +1511,10 @@ def cloud_grid_build(pts, sorted_keys, perm, grid, want_sorted: bool = True):
     n, dev = pts.shape[0], pts.device
     if sorted_keys.shape != (n,) or perm.shape != (n,):
         raise _lib.MvsHipError("cloud_grid_build: %d points, keys %s, perm %s" % (n, tuple(sorted_keys.shape), tuple(perm.shape)))
-    ws = torch.empty(_lib.load().mvs_cloud_grid_workspace_bytes(n) // 8 + 1, device=dev, dtype=torch.int64)
-    spts = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_sorted else None
-    cell_keys = torch.empty(n, device=dev, dtype=torch.int64)
-    cell_start = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    ws = _new(dev, _lib.load().mvs_cloud_grid_workspace_bytes(n) // 8 + 1, dtype=torch.int64)
+    spts = _new(dev, n, 3) if want_sorted else None
+    cell_keys = _new(dev, n, dtype=torch.int64)
+    cell_start = _new(dev, n + 1, dtype=torch.int64)
     _call("mvs_cloud_grid_build", ("cloud_grid_build", "bytes", (24.0 + (24.0 if want_sorted else 0.0)) * n), _ptr(pts), n, _ptr(sorted_keys),
           _ptr(perm), _ptr(grid), _ptr(ws), _ptr(spts), _ptr(cell_keys), _ptr(cell_start), _stream())
     return spts, cell_keys, cell_start
@@ -1566,7 +1522,7 @@ def cloud_grid_build(pts, sorted_keys, perm, grid, want_sorted: bool = True):
 
 def cloud_query_keys(queries, grid) -> torch.Tensor:
     _chk_cloud(queries, "queries"), _chk(grid, "grid", torch.int64)
-    keys = torch.empty(queries.shape[0], device=queries.device, dtype=torch.int64)
+    keys = _new(queries, queries.shape[0], dtype=torch.int64)
     _call("mvs_cloud_query_keys", ("cloud_query_keys", "bytes", 20.0 * queries.shape[0]), _ptr(queries), queries.shape[0], _ptr(grid), _ptr(keys),
           _stream())
     return keys
@@ -1582,8 +1538,8 @@ def cloud_nn_query(queries, query_perm, grid, cell: float, sorted_pts, perm, cel
         raise _lib.MvsHipError("cloud_nn_query: query_perm must hold %d entries" % m)
     if perm.shape != (n,) or cell_keys.shape != (n,) or cell_start.shape != (n + 1,):
         raise _lib.MvsHipError("cloud_nn_query: the index arrays do not belong to %d points" % n)
-    dist = torch.empty(m, device=queries.device, dtype=torch.float32)
-    idx = torch.empty(m, device=queries.device, dtype=torch.int64)
+    dist = _new(queries, m)
+    idx = _new(queries, m, dtype=torch.int64)
     _call("mvs_cloud_nn_query", "cloud_nn_query", _ptr(queries), m, _ptr(query_perm), _ptr(grid), float(cell), _ptr(sorted_pts), _ptr(perm),
           _ptr(cell_keys), _ptr(cell_start), n, float(max_dist), _ptr(dist), _ptr(idx), _stream())
     return dist, idx
@@ -1603,7 +1559,7 @@ def cloud_voxel_write(attr, perm, grid, cell_start, count: int) -> torch.Tensor:
     n = attr.shape[0]
     if perm.shape != (n,) or cell_start.shape != (n + 1,):
         raise _lib.MvsHipError("cloud_voxel_write: the index arrays do not belong to %d points" % n)
-    out = torch.empty(count, 3, device=attr.device, dtype=torch.float32)
+    out = _new(attr, count, 3)
     _call("mvs_cloud_voxel_downsample_write", ("cloud_voxel_write", "bytes", 20.0 * n + 12.0 * count), _ptr(attr), n, _ptr(perm), _ptr(grid),
           _ptr(cell_start), int(count), _ptr(out), _stream())
     return out
@@ -1619,19 +1575,19 @@ def cloud_score(dist, max_dist: float, taus=(), record=None) -> torch.Tensor:
     if len(taus) > CLOUD_SCORE_MAX_K:
         raise _lib.MvsHipError("cloud_score: %d thresholds, at most %d are built" % (len(taus), CLOUD_SCORE_MAX_K))
     if record is None:
-        record = torch.empty(CLOUD_SCORE_RECORD_BYTES // 8, device=dist.device, dtype=torch.int64)
+        record = _new(dist, CLOUD_SCORE_RECORD_BYTES // 8, dtype=torch.int64)
     _chk(record, "record", torch.int64)
     if record.numel() != CLOUD_SCORE_RECORD_BYTES // 8:
         raise _lib.MvsHipError("cloud_score: the record holds %d int64" % (CLOUD_SCORE_RECORD_BYTES // 8))
     m = dist.shape[0]
-    ws = torch.empty(_lib.load().mvs_cloud_score_workspace_bytes(m) // 8, device=dist.device, dtype=torch.float64)
+    ws = _new(dist, _lib.load().mvs_cloud_score_workspace_bytes(m) // 8, dtype=torch.float64)
     th = (ctypes.c_float * max(1, len(taus)))(*taus)
     _call("mvs_cloud_score", ("cloud_score", "bytes", 4.0 * m), _ptr(dist) if m else None, m, float(max_dist), ctypes.addressof(th), len(taus),
           _ptr(ws), _ptr(record), _stream())
     return record
 
 
-GREEDY_THIN_BATCH = 4                                        # MVS_GREEDY_THIN_BATCH
+GREEDY_THIN_BATCH = _H["MVS_GREEDY_THIN_BATCH"]
 
 
 def greedy_thin(order, grid, dist: float, sorted_pts, perm, cell_keys, cell_start):
@@ -1643,8 +1599,8 @@ def greedy_thin(order, grid, dist: float, sorted_pts, perm, cell_keys, cell_star
     n = sorted_pts.shape[0]
     if order.shape != (n,) or perm.shape != (n,) or cell_keys.shape != (n,) or cell_start.shape != (n + 1,):
         raise _lib.MvsHipError("greedy_thin: order and the index arrays do not belong to %d points" % n)
-    ws = torch.empty(_lib.load().mvs_greedy_thin_workspace_bytes(n) // 8, device=order.device, dtype=torch.int64)
-    keep = torch.empty(n, device=order.device, dtype=torch.uint8)
+    ws = _new(order, _lib.load().mvs_greedy_thin_workspace_bytes(n) // 8, dtype=torch.int64)
+    keep = _new(order, n, dtype=torch.uint8)
     rounds = ctypes.c_int64(0)
     _call("mvs_greedy_thin", "cloud_greedy_thin", n, _ptr(order), _ptr(grid), float(dist), _ptr(sorted_pts), _ptr(perm), _ptr(cell_keys),
           _ptr(cell_start), _ptr(ws), _ptr(keep), ctypes.addressof(rounds), _stream())
@@ -1652,9 +1608,9 @@ def greedy_thin(order, grid, dist: float, sorted_pts, perm, cell_keys, cell_star
 
 
 # --------------------------------------------------------------------------------------------- cloud alignment (csrc/cloud_align.hip)
-ALIGN_CROP_MAX_K = 64                                        # MVS_ALIGN_CROP_MAX_K
-ALIGN_PAIR_RECORD_BYTES = 192                                # MVS_ALIGN_PAIR_RECORD_BYTES
-ALIGN_PAIR_MAX_ROWS = 1024                                   # MVS_ALIGN_PAIR_MAX_ROWS
+ALIGN_CROP_MAX_K = _H["MVS_ALIGN_CROP_MAX_K"]
+ALIGN_PAIR_RECORD_BYTES = _H["MVS_ALIGN_PAIR_RECORD_BYTES"]
+ALIGN_PAIR_MAX_ROWS = _H["MVS_ALIGN_PAIR_MAX_ROWS"]
 
 
 def align_transform(pts, srt) -> torch.Tensor:
@@ -1665,7 +1621,7 @@ def align_transform(pts, srt) -> torch.Tensor:
     if len(srt) != 12:
         raise _lib.MvsHipError("align_transform: 12 numbers (3x3 row-major, then t), got %d" % len(srt))
     n = pts.shape[0]
-    out = torch.empty(n, 3, device=pts.device, dtype=torch.float32)
+    out = _new(pts, n, 3)
     a = (ctypes.c_double * 12)(*srt)
     _call("mvs_align_transform", ("align_transform", "bytes", 24.0 * n), _ptr(pts) if n else None, n, ctypes.addressof(a), _ptr(out) if n else None,
           _stream())
@@ -1680,7 +1636,7 @@ def align_crop_polygon(pts, axis: int, axis_min: float, axis_max: float, polygon
     if len(uv) > ALIGN_CROP_MAX_K:
         raise _lib.MvsHipError("align_crop_polygon: %d polygon vertices, at most %d are built" % (len(uv), ALIGN_CROP_MAX_K))
     n = pts.shape[0]
-    mask = torch.empty(n, device=pts.device, dtype=torch.uint8)
+    mask = _new(pts, n, dtype=torch.uint8)
     poly = (ctypes.c_double * max(2, 2 * len(uv)))(*[c for p in uv for c in p])
     _call("mvs_align_crop_polygon", ("align_crop_polygon", "bytes", 13.0 * n), _ptr(pts) if n else None, n, int(axis), float(axis_min),
           float(axis_max), ctypes.addressof(poly), len(uv), _ptr(mask) if n else None, _stream())
@@ -1695,11 +1651,11 @@ def align_pair_sums(src, dst, idx, dist, origin, record=None) -> torch.Tensor:
     if idx.shape != (m,) or dist.shape != (m,):
         raise _lib.MvsHipError("align_pair_sums: idx %s and dist %s must be [%d]" % (tuple(idx.shape), tuple(dist.shape), m))
     if record is None:
-        record = torch.empty(ALIGN_PAIR_RECORD_BYTES // 8, device=src.device, dtype=torch.int64)
+        record = _new(src, ALIGN_PAIR_RECORD_BYTES // 8, dtype=torch.int64)
     _chk(record, "record", torch.int64)
     if record.numel() != ALIGN_PAIR_RECORD_BYTES // 8:
         raise _lib.MvsHipError("align_pair_sums: the record holds %d int64" % (ALIGN_PAIR_RECORD_BYTES // 8))
-    ws = torch.empty(_lib.load().mvs_align_pair_sums_workspace_bytes(m) // 8, device=src.device, dtype=torch.float64)
+    ws = _new(src, _lib.load().mvs_align_pair_sums_workspace_bytes(m) // 8, dtype=torch.float64)
     o = (ctypes.c_double * 3)(*[float(v) for v in origin])
     _call("mvs_align_pair_sums", ("align_pair_sums", "bytes", 36.0 * m), _ptr(src) if m else None, m, _ptr(dst) if n else None, n,
           _ptr(idx) if m else None, _ptr(dist) if m else None, ctypes.addressof(o), _ptr(ws), _ptr(record), _stream())
@@ -1709,7 +1665,7 @@ def align_pair_sums(src, dst, idx, dist, origin, record=None) -> torch.Tensor:
 def bf16_embed_ch0(x: torch.Tensor) -> torch.Tensor:
     """fp32 ``[...]`` -> bf16 ``[..., 8]`` with the value in channel 0, zeros elsewhere (one launch instead of a fill and a strided copy)."""
     _chk(x, "x")
-    out = torch.empty(tuple(x.shape) + (8,), device=x.device, dtype=torch.bfloat16)
+    out = _new(x, tuple(x.shape) + (8,), dtype=torch.bfloat16)
     _call("mvs_bf16_embed_ch0", "bf16_embed_ch0", _ptr(x), _ptr(out), x.numel(), _stream())
     return out
 
@@ -1723,7 +1679,7 @@ def bf16_from_f32(x: torch.Tensor) -> torch.Tensor:
     """fp32 ``[B,C,D,H,W]`` -> bf16 channel-last ``[B,D,H,W,C]``."""
     _chk(x, "x")
     B, C = x.shape[0], x.shape[1]
-    y = torch.empty((B,) + tuple(x.shape[2:]) + (C,), device=x.device, dtype=torch.bfloat16)
+    y = _new(x, (B,) + tuple(x.shape[2:]) + (C,), dtype=torch.bfloat16)
     _call("mvs_bf16_from_f32_ncdhw", "bf16_from_f32", _ptr(x), _ptr(y), B, C, x.numel() // (B * C), _stream())
     return y
 
@@ -1732,7 +1688,7 @@ def bf16_to_f32(x: torch.Tensor) -> torch.Tensor:
     """bf16 channel-last ``[B,D,H,W,C]`` -> fp32 ``[B,C,D,H,W]``."""
     _chk16(x, "x")
     B, C = x.shape[0], x.shape[-1]
-    y = torch.empty((B, C) + tuple(x.shape[1:-1]), device=x.device, dtype=torch.float32)
+    y = _new(x, (B, C) + tuple(x.shape[1:-1]))
     _call("mvs_bf16_to_f32_ncdhw", "bf16_to_f32", _ptr(x), _ptr(y), B, C, x.numel() // (B * C), _stream())
     return y
 
@@ -1758,7 +1714,7 @@ def bf16_pack(weight: torch.Tensor, src: int, cin: int, cout: int) -> torch.Tens
     _chk(weight, "conv weight")
     if _taps_of(weight) != 27:
         raise _lib.MvsHipError("bf16_pack: 3x3x3 weights only (2-D kernels are packed through a PackTable)")
-    packed = torch.empty(bf16_packed_elems(cin, cout), device=weight.device, dtype=torch.bfloat16)
+    packed = _new(weight, bf16_packed_elems(cin, cout), dtype=torch.bfloat16)
     _call("mvs_bf16_pack_weights", None, _ptr(weight), weight.shape[0], weight.shape[1], int(src), cout, cin, _ptr(packed), _stream())
     return packed
 
@@ -1768,7 +1724,7 @@ def bf16_pack2(weight: torch.Tensor, a, b):
     _chk(weight, "conv weight")
     if _taps_of(weight) != 27:
         raise _lib.MvsHipError("bf16_pack2: 3x3x3 weights only (2-D kernels are packed through a PackTable)")
-    outs = [torch.empty(bf16_packed_elems(cin, cout), device=weight.device, dtype=torch.bfloat16) for _, cin, cout in (a, b)]
+    outs = [_new(weight, bf16_packed_elems(cin, cout), dtype=torch.bfloat16) for _, cin, cout in (a, b)]
     _call("mvs_bf16_pack_weights2", "mvs_bf16_pack_weights", _ptr(weight), weight.shape[0], weight.shape[1], int(a[0]), a[2], a[1],
           _ptr(outs[0]), int(b[0]), b[2], b[1], _ptr(outs[1]), _stream())
     return outs[0], outs[1]
@@ -1795,7 +1751,7 @@ class PackTable:
         host = (ctypes.c_uint8 * nbytes)()
         for i, (w, src, cin, cout) in enumerate(jobs):
             taps = _taps_of(w)
-            out = torch.empty(bf16_packed_elems(cin, cout, taps), device=dev, dtype=torch.bfloat16)
+            out = _new(dev, bf16_packed_elems(cin, cout, taps), dtype=torch.bfloat16)
             self.outs.append(out)
             _lib.check(lib.mvs_bf16_pack_table_fill(host, n, i, _ptr(w), w.shape[0], w.shape[1], int(src), cout, cin, taps, _ptr(out)),
                        "mvs_bf16_pack_table_fill")
@@ -1827,7 +1783,7 @@ def _bf16_conv_io(x, cin, cout, gather: int, stride, taps: int = 27):
         Do, Ho, Wo = (Di - 1) // sd + 1, (Hi - 1) // shw + 1, (Wi - 1) // shw + 1
     else:
         Do, Ho, Wo = Di * sd, Hi * shw, Wi * shw
-    y = torch.empty(B, Do, Ho, Wo, cout, device=x.device, dtype=torch.bfloat16)
+    y = _new(x, B, Do, Ho, Wo, cout, dtype=torch.bfloat16)
     return B, Di, Hi, Wi, Do, Ho, Wo, y, 2.0 * taps * cin * cout * B * (Do * Ho * Wo if gather == 0 else Di * Hi * Wi)
 
 
@@ -1841,10 +1797,7 @@ def bf16_conv3d(x, wpacked, cin, cout, gather: int, stride, scale=None, shift=No
     ``taps`` = 9: a 2-D kernel (no epilogue arguments then)."""
     _chk16(x, "x"), _chk16(wpacked, "packed weights"), _opt(scale, "scale"), _opt(shift, "shift")
     B, Di, Hi, Wi, Do, Ho, Wo, y, flops = _bf16_conv_io(x, cin, cout, gather, stride, taps)
-    if residual is not None:
-        _chk16(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
+    _chk_residual(residual, y.shape, torch.bfloat16)
     tag = _bf16_conv_tag("bf16_conv_kernel", cin, cout, gather, stride, taps, flops)
     if taps != 27:
         assert scale is None and shift is None and residual is None and not relu
@@ -1869,7 +1822,7 @@ def bf16_conv3d_bnbwd(x, wpacked, cin, cout, gather: int, stride, bn_y, bn4, rel
         _chk16(addend, "addend")
         if tuple(addend.shape) != tuple(y.shape):
             raise _lib.MvsHipError("bf16_conv3d_bnbwd: addend %s does not match the gradient %s" % (tuple(addend.shape), tuple(y.shape)))
-    sums = torch.empty(2 * groups * cout, device=x.device, dtype=torch.float32)
+    sums = _new(x, 2 * groups * cout)
     ws = _reduce_ws("mvs_bf16_conv3d_bn_fwd_workspace_bytes", x.device, B, cout, Do, Ho, Wo)
     tag = _bf16_conv_tag("bf16_conv_kernel", cin, cout, gather, stride, taps, flops)
     _call("mvs_bf16_conv3d_bnbwd", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), *stride, int(taps), _ptr(bn_y),
@@ -1884,7 +1837,7 @@ def bf16_conv3d_stats(x, wpacked, cin, cout, gather: int, stride, groups: int = 
     B, Di, Hi, Wi, Do, Ho, Wo, y, flops = _bf16_conv_io(x, cin, cout, gather, stride)
     if B % groups:
         raise _lib.MvsHipError("grouped statistics: batch %d is not a multiple of %d groups" % (B, groups))
-    sums = torch.empty(2 * groups * cout, device=x.device, dtype=torch.float64)
+    sums = _new(x, 2 * groups * cout, dtype=torch.float64)
     ws = _reduce_ws("mvs_bf16_conv3d_stats_workspace_bytes", x.device, B, cout, Do, Ho, Wo)
     tag = _bf16_conv_tag("bf16_conv_kernel", cin, cout, gather, stride, 27, flops)
     _call("mvs_bf16_conv3d_stats", tag, _ptr(x), _ptr(wpacked), _ptr(y), B, cin, cout, Di, Hi, Wi, int(gather), *stride, int(groups),
@@ -1899,11 +1852,11 @@ def bf16_conv3d_wgrad(A: torch.Tensor, Bt: torch.Tensor, stride, taps: int = 27,
     N, Dp, Hp, Wp, CA = A.shape
     _, Db, Hb, Wb, CB = Bt.shape
     cb_out = CB if cb_out is None else int(cb_out)
-    dW = torch.empty((CA, cb_out, 3, 3, 3) if taps == 27 else (CA, cb_out, 3, 3), device=A.device, dtype=torch.float32)
+    dW = _new(A, (CA, cb_out, 3, 3, 3) if taps == 27 else (CA, cb_out, 3, 3))
     nws = _lib.load().mvs_bf16_conv3d_wgrad_workspace_bytes(N, CA, CB, Dp, Hp, Wp)
     if nws <= 0:
         raise _lib.MvsHipError("bf16 wgrad: channels must be 8/16/32/64 (CA=%d CB=%d)" % (CA, CB))
-    ws = torch.empty(nws, device=A.device, dtype=torch.uint8)
+    ws = _new(A, nws, dtype=torch.uint8)
     name = "bf16_wgrad_kernel" if not sw.flag("MVS_TAG_SHAPES") else \
         "bf16_wgrad<%d,%d,s%d%d,%dx%dx%dx%d>" % (CA, CB, stride[0], stride[1], N, Dp, Hp, Wp)
     tag = (name, "flops", 2.0 * taps * CA * CB * N * Dp * Hp * Wp)
@@ -1942,7 +1895,7 @@ def bf16_wgrad_group(jobs) -> None:
     if nws <= 0:
         raise _lib.MvsHipError("bf16_wgrad_group: a job's channels / stride / taps are not built")
     dev = jobs[0][0].device
-    ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+    ws = _new(dev, nws, dtype=torch.uint8)
     _call("mvs_bf16_wgrad_group", ("bf16_wgrad_kernel", "flops", flops), ptr, len(jobs), _ptr(ws), int(nws), _stream())
 
 
@@ -1951,7 +1904,7 @@ def bf16_head_fwd(x: torch.Tensor, w: Optional[torch.Tensor], bias: Optional[tor
     _chk16(x, "x"), _opt(w, "w"), _opt(bias, "bias")
     if x.shape[-1] != 8:
         raise _lib.MvsHipError("bf16 head: 8 input channels, got %d" % x.shape[-1])
-    out = torch.empty(x.shape[:-1], device=x.device, dtype=torch.float32)
+    out = _new(x, x.shape[:-1])
     _call("mvs_bf16_head_fwd", "bf16_head_fwd", _ptr(x), _ptr(w), _ptr(bias), int(sigmoid), out.numel(), _ptr(out), _stream())
     return out
 
@@ -1963,8 +1916,8 @@ def bf16_head_bwd(x: torch.Tensor, w: Optional[torch.Tensor], y: Optional[torch.
     dx = torch.empty_like(x)
     dwb = ws = None
     if w is not None:
-        dwb = torch.empty(9, device=x.device, dtype=torch.float32)
-        ws = torch.empty(max(1, _lib.load().mvs_bf16_head_bwd_workspace_bytes(N) // 4), device=x.device, dtype=torch.float32)
+        dwb = _new(x, 9)
+        ws = _new(x, max(1, _lib.load().mvs_bf16_head_bwd_workspace_bytes(N) // 4))
     _call("mvs_bf16_head_bwd", "bf16_head_bwd", _ptr(x), _ptr(w), _ptr(y), _ptr(dout), N, _ptr(dx), _ptr(dwb), _ptr(ws), _stream())
     return dx, dwb
 
@@ -1983,7 +1936,7 @@ def bf16_bn_stats(x: torch.Tensor, groups: int = 1) -> torch.Tensor:
     """-> ``sums [2*groups*C]`` (fp64): [sum | sum of squares] per (group, channel)."""
     _chk16(x, "x")
     C, R, rps = _bf16_bn_shape(x, groups)
-    sums = torch.empty(2 * groups * C, device=x.device, dtype=torch.float64)
+    sums = _new(x, 2 * groups * C, dtype=torch.float64)
     ws = _reduce_ws("mvs_bf16_bn_reduce_workspace_bytes", x.device, C, R, groups, rps)
     _call("mvs_bf16_bn_stats", "bf16_bn_stats", _ptr(x), C, R, groups, rps, _ptr(sums), _ptr(ws), _stream())
     return sums
@@ -1998,7 +1951,7 @@ def bf16_bn_train_fwd(x, residual, relu, gamma, beta, running_mean, running_var,
         _chk(num_batches_tracked, "bn.num_batches_tracked", dtype=torch.int64)
     C, R, rps = _bf16_bn_shape(x, groups)
     y = torch.empty_like(x)
-    st = torch.empty(5, groups * C, device=x.device, dtype=torch.float32)      # scale | shift | mean | invstd | gamma per (group, channel)
+    st = _new(x, 5, groups * C)      # scale | shift | mean | invstd | gamma per (group, channel)
     ws = _reduce_ws("mvs_bf16_bn_reduce_workspace_bytes", x.device, C, R, groups, rps)
     if running_mean is not None:
         bump_weights_epoch()                                 # running statistics are written through raw pointers
@@ -2021,7 +1974,7 @@ def bf16_affine_act(x, scale, shift, residual, relu, groups: int = 1):
 def bf16_bn_bwd_reduce(dy, x, scale, shift, mean, invstd, relu, groups: int = 1):
     _chk16(dy, "dy"), _chk16(x, "x")
     C, R, rps = _bf16_bn_shape(x, groups)
-    sums = torch.empty(2 * groups * C, device=x.device, dtype=torch.float32)
+    sums = _new(x, 2 * groups * C)
     ws = _reduce_ws("mvs_bf16_bn_reduce_workspace_bytes", x.device, C, R, groups, rps)
     _call("mvs_bf16_bn_bwd_reduce", "bf16_bn_bwd_reduce", _ptr(dy), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), int(relu), C,
           R, groups, rps, _ptr(sums), _ptr(ws), _stream())
@@ -2038,13 +1991,10 @@ def bf16_conv3d_bn_fwd(x, wpacked, cin, cout, gather: int, stride, residual, rel
     if B % groups:
         raise _lib.MvsHipError("grouped statistics: batch %d is not a multiple of %d groups" % (B, groups))
     z = torch.empty_like(y)
-    if residual is not None:
-        _chk16(residual, "residual")
-        if residual.shape != y.shape:
-            raise _lib.MvsHipError("residual shape %s != output %s" % (tuple(residual.shape), tuple(y.shape)))
+    _chk_residual(residual, y.shape, torch.bfloat16)
     if num_batches_tracked is not None:
         _chk(num_batches_tracked, "bn.num_batches_tracked", dtype=torch.int64)
-    st = torch.empty(5, groups * cout, device=x.device, dtype=torch.float32)
+    st = _new(x, 5, groups * cout)
     ws = _reduce_ws("mvs_bf16_conv3d_bn_fwd_workspace_bytes", x.device, B, cout, Do, Ho, Wo)
     tag = _bf16_conv_tag("bf16_conv_bn_fwd", cin, cout, gather, stride, taps, flops)
     if running_mean is not None:
@@ -2062,7 +2012,7 @@ def bf16_bn_bwd_apply(dy, x, scale, shift, mean, invstd, gamma, sums, count, rel
     C, R, rps = _bf16_bn_shape(x, groups)
     dx = torch.empty_like(x)
     if want_dgb:
-        dgb = torch.empty(2 * C, device=x.device, dtype=torch.float32)
+        dgb = _new(x, 2 * C)
         _call("mvs_bf16_bn_bwd_apply_dgb", "bf16_bn_bwd_apply", _ptr(dy), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _ptr(gamma),
               _ptr(sums), float(count), _ptr(count_dev), int(relu), C, R, groups, rps, _ptr(dx), _ptr(dgb), _stream())
         return dx, dgb
@@ -2081,7 +2031,7 @@ def fpn_pack_weights(w: torch.Tensor) -> torch.Tensor:
     Cout = w.shape[0]
     if w.shape[1:] != (FPN_CH, 3, 3) or Cout not in (8, 16, 32):
         raise _lib.MvsHipError("fpn 3x3 weight must be [8|16|32,64,3,3], got %s" % (tuple(w.shape),))
-    packed = torch.empty(int(_lib.load().mvs_fpn_packed_floats(Cout)), device=w.device, dtype=torch.float32)
+    packed = _new(w, int(_lib.load().mvs_fpn_packed_floats(Cout)))
     _call("mvs_fpn_pack_weights", None, _ptr(w), Cout, _ptr(packed), _stream())
     return packed
 
@@ -2092,7 +2042,7 @@ def fpn_out0(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, shift: torch
     N, C, h, wd = x.shape
     if C != FPN_CH or w.numel() != FPN_CH * FPN_CH or scale.numel() != FPN_CH or shift.numel() != FPN_CH:
         raise _lib.MvsHipError("fpn_out0: expects 64 channels, got x %s w %s" % (tuple(x.shape), tuple(w.shape)))
-    out = torch.empty(N, h, wd, FPN_CH, device=x.device, dtype=torch.float32)
+    out = _new(x, N, h, wd, FPN_CH)
     tag = ("fpn_out0_kernel", "flops", 2.0 * FPN_CH * FPN_CH * N * h * wd)
     _call("mvs_fpn_out0", tag, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), N, h, wd, _ptr(out), _stream())
     return out
@@ -2114,8 +2064,8 @@ def fpn_level(intra_prev: torch.Tensor, lateral: torch.Tensor, w_inner_p: torch.
         raise _lib.MvsHipError("fpn_level: Ck=%d / packed weights of %d floats are not a supported pair" % (Ck, packed.numel()))
     intra = None
     if want_intra:                                           # ``intra_nhwc``: [N,2h,2w,64] memory (what ``fpn_level_cp`` reads), else the reference's [N,64,2h,2w]
-        intra = torch.empty((N, 2 * h, 2 * w, FPN_CH) if intra_nhwc else (N, FPN_CH, 2 * h, 2 * w), device=lateral.device, dtype=torch.float32)
-    out = torch.empty(N, 2 * h, 2 * w, Ck, device=lateral.device, dtype=torch.float32)
+        intra = _new(lateral, (N, 2 * h, 2 * w, FPN_CH) if intra_nhwc else (N, FPN_CH, 2 * h, 2 * w))
+    out = _new(lateral, N, 2 * h, 2 * w, Ck)
     tag = ("fpn_level_kernel<%d>" % Ck, "flops", 2.0 * FPN_CH * Ck * 10 * N * 4 * h * w)
     _call("mvs_fpn_level_layout", tag, _ptr(intra_prev), _ptr(lateral), _ptr(w_inner_p), _ptr(b_inner), _ptr(packed), _ptr(scale), _ptr(shift),
           N, Ck, h, w, _ptr(intra), 1 if (want_intra and intra_nhwc) else 0, _ptr(out), _stream())
@@ -2127,11 +2077,8 @@ def fpn_level_x3s_prepare(w3: torch.Tensor, scale: torch.Tensor) -> torch.Tensor
     _chk(w3, "fpn 3x3 weight"), _chk(scale, "scale")
     Ck = w3.shape[0]
     n = int(_lib.load().mvs_fpn_level_x3s_prepared_bytes(Ck))
-    if n <= 0 or w3.shape != (Ck, FPN_CH, 3, 3) or scale.numel() != Ck:
-        raise _lib.MvsHipError("fpn_level_x3s_prepare: unsupported weight %s" % (tuple(w3.shape),))
-    prepared = torch.empty(n, device=w3.device, dtype=torch.uint8)
-    _call("mvs_fpn_level_x3s_prepare", None, _ptr(w3.contiguous()), _ptr(scale), Ck, _ptr(prepared), _stream())
-    return prepared
+    return _packed("mvs_fpn_level_x3s_prepare", n, w3.shape == (Ck, FPN_CH, 3, 3) and scale.numel() == Ck,
+                   "fpn_level_x3s_prepare: unsupported weight %s", (tuple(w3.shape),), w3, torch.uint8, _ptr(w3.contiguous()), _ptr(scale), Ck)
 
 
 def fpn_level_x3s(intra_prev: torch.Tensor, lateral: torch.Tensor, w_inner_p: torch.Tensor, b_inner: torch.Tensor, prepared: torch.Tensor,
@@ -2147,8 +2094,8 @@ def fpn_level_x3s(intra_prev: torch.Tensor, lateral: torch.Tensor, w_inner_p: to
         raise _lib.MvsHipError("fpn_level_x3s: prepared weights do not match Ck=%d" % Ck)
     intra = None
     if want_intra:
-        intra = torch.empty((N, 2 * h, 2 * w, FPN_CH) if intra_nhwc else (N, FPN_CH, 2 * h, 2 * w), device=lateral.device, dtype=torch.float32)
-    out = torch.empty(N, 2 * h, 2 * w, Ck, device=lateral.device, dtype=torch.float32)
+        intra = _new(lateral, (N, 2 * h, 2 * w, FPN_CH) if intra_nhwc else (N, FPN_CH, 2 * h, 2 * w))
+    out = _new(lateral, N, 2 * h, 2 * w, Ck)
     tag = ("fpn_level_x3s_kernel<%d>" % Ck, "flops", 2.0 * FPN_CH * Ck * 10 * N * 4 * h * w)
     _call("mvs_fpn_level_x3s", tag, _ptr(intra_prev), _ptr(lateral), _ptr(w_inner_p), _ptr(b_inner), _ptr(prepared), _ptr(shift), N, Ck, h, w,
           _ptr(intra), 1 if (want_intra and intra_nhwc) else 0, _ptr(out), _stream())
@@ -2169,9 +2116,9 @@ def fpn_level_x3_prepare(w3: torch.Tensor, w_inner: torch.Tensor, b_inner: torch
     resp = torch.einsum("ochw,c->ohw", w3d, b_inner.double()).reshape(Ck, 9) * scale.double()[:, None]    # scale * bias response per tap
     shift_x = (shift.double() + resp.sum(1)).float().contiguous()
     border = resp.t().float().contiguous()                                                  # [9][Ck]
-    prepared = torch.empty(n, device=w3.device, dtype=torch.uint8)
+    prepared = _new(w3, n, dtype=torch.uint8)
     _call("mvs_fpn_level_x3_prepare", None, _ptr(w3.contiguous()), _ptr(wc), _ptr(scale), Ck, _ptr(prepared), _stream())
-    prepared_cp = torch.empty(int(_lib.load().mvs_fpn_level_cp_prepared_bytes(Ck)), device=w3.device, dtype=torch.uint8)
+    prepared_cp = _new(w3, int(_lib.load().mvs_fpn_level_cp_prepared_bytes(Ck)), dtype=torch.uint8)
     _call("mvs_fpn_level_cp_prepare", None, _ptr(w3.contiguous()), _ptr(wc), _ptr(scale), Ck, _ptr(prepared_cp), _stream())
     return prepared, shift_x, border, prepared_cp
 
@@ -2186,7 +2133,7 @@ def fpn_level_x3(intra_prev: torch.Tensor, lateral: torch.Tensor, prepared: torc
         raise _lib.MvsHipError("fpn_level_x3: intra_prev %s needs a lateral [N,Ck,2h,2w], got %s" % (tuple(intra_prev.shape), tuple(lateral.shape)))
     if prepared.numel() != int(_lib.load().mvs_fpn_level_x3_prepared_bytes(Ck)) or shift_x.numel() != Ck or border.numel() != 9 * Ck:
         raise _lib.MvsHipError("fpn_level_x3: operands do not match Ck=%d" % Ck)
-    out = torch.empty(N, 2 * h, 2 * w, Ck, device=lateral.device, dtype=torch.float32)
+    out = _new(lateral, N, 2 * h, 2 * w, Ck)
     tag = ("fpn8_x3_kernel", "flops", 2.0 * FPN_CH * Ck * 10 * N * 4 * h * w)
     _call("mvs_fpn_level_x3", tag, _ptr(intra_prev), _ptr(lateral), _ptr(prepared), _ptr(shift_x), _ptr(border), N, Ck, h, w, _ptr(out), _stream())
     return out
@@ -2202,7 +2149,7 @@ def fpn_level_cp(intra_prev_cl: torch.Tensor, lateral_cl: torch.Tensor, prepared
         raise _lib.MvsHipError("fpn_level_cp: intra_prev [N,h,w,64] %s needs a lateral [N,2h,2w,Ck], got %s" % (tuple(intra_prev_cl.shape), tuple(lateral_cl.shape)))
     if prepared_cp.numel() != int(_lib.load().mvs_fpn_level_cp_prepared_bytes(Ck)) or shift_x.numel() != Ck or border.numel() != 9 * Ck:
         raise _lib.MvsHipError("fpn_level_cp: operands do not match Ck=%d" % Ck)
-    out = torch.empty(N, 2 * h, 2 * w, Ck, device=lateral_cl.device, dtype=torch.float32)
+    out = _new(lateral_cl, N, 2 * h, 2 * w, Ck)
     tag = ("fpn8_cp_kernel", "flops", 2.0 * FPN_CH * Ck * 10 * N * 4 * h * w)
     _call("mvs_fpn_level_cp", tag, _ptr(intra_prev_cl), _ptr(lateral_cl), _ptr(prepared_cp), _ptr(shift_x), _ptr(border), N, Ck, h, w, _ptr(out), _stream())
     return out
@@ -2216,11 +2163,9 @@ def fpn_v2_tail_prepare(w_up: torch.Tensor, fold_up, w_out: torch.Tensor, fold_o
         _chk(t, "scale / shift")
     Cin, Cmid, Cout = w_up.shape[0], w_up.shape[1], w_out.shape[0]
     n = int(_lib.load().mvs_fpn_v2_tail_prepared_bytes(Cin, Cmid, Cout))
-    if n <= 0 or w_up.shape != (Cin, Cmid, 4, 4) or w_out.shape != (Cout, Cmid, 3, 3) or fold_up[0].numel() != Cmid or fold_out[0].numel() != Cout:
-        raise _lib.MvsHipError("fpn_v2_tail_prepare: unsupported weights %s, %s" % (tuple(w_up.shape), tuple(w_out.shape)))
-    prepared = torch.empty(n, device=w_up.device, dtype=torch.uint8)
-    _call("mvs_fpn_v2_tail_prepare", None, _ptr(w_up.contiguous()), _ptr(fold_up[0]), _ptr(w_out.contiguous()), _ptr(fold_out[0]), Cin, Cmid, Cout,
-          _ptr(prepared), _stream())
+    ok = w_up.shape == (Cin, Cmid, 4, 4) and w_out.shape == (Cout, Cmid, 3, 3) and fold_up[0].numel() == Cmid and fold_out[0].numel() == Cout
+    prepared = _packed("mvs_fpn_v2_tail_prepare", n, ok, "fpn_v2_tail_prepare: unsupported weights %s, %s", (tuple(w_up.shape), tuple(w_out.shape)),
+                       w_up, torch.uint8, _ptr(w_up.contiguous()), _ptr(fold_up[0]), _ptr(w_out.contiguous()), _ptr(fold_out[0]), Cin, Cmid, Cout)
     return prepared, fold_up[1].contiguous(), fold_out[1].contiguous(), (Cin, Cmid, Cout)
 
 
@@ -2234,7 +2179,7 @@ def fpn_v2_tail(out3_cl: torch.Tensor, conv01_cl: torch.Tensor, prepared: torch.
         raise _lib.MvsHipError("fpn_v2_tail: out3 [N,h,w,%d] %s needs conv01 [N,2h,2w,%d], got %s" % (Cin, tuple(out3_cl.shape), Cmid, tuple(conv01_cl.shape)))
     if prepared.numel() != int(_lib.load().mvs_fpn_v2_tail_prepared_bytes(Cin, Cmid, Cout)) or shift_up.numel() != Cmid or shift_out.numel() != Cout:
         raise _lib.MvsHipError("fpn_v2_tail: operands do not match %d -> %d -> %d channels" % chans)
-    out = torch.empty(N, 2 * h, 2 * w, Cout, device=out3_cl.device, dtype=torch.float32)
+    out = _new(out3_cl, N, 2 * h, 2 * w, Cout)
     tag = ("fpn_v2_tail_kernel", "flops", 2.0 * (4 * Cin * Cmid + 9 * Cmid * Cout) * N * 4 * h * w)
     _call("mvs_fpn_v2_tail", tag, _ptr(out3_cl), _ptr(conv01_cl), _ptr(prepared), _ptr(shift_up), _ptr(shift_out), N, Cin, Cmid, Cout, h, w, _ptr(out),
           _stream())
@@ -2251,11 +2196,8 @@ def conv2d_x3s_prepare(w: torch.Tensor, scale: torch.Tensor, stride: int) -> tor
     _chk(w, "conv2d weight"), _chk(scale, "scale")
     Cout, Cin, K, K2 = w.shape
     n = int(_lib.load().mvs_conv2d_x3s_prepared_bytes(Cin, Cout, K, stride)) if K == K2 else -1
-    if n <= 0 or scale.numel() != Cout:
-        raise _lib.MvsHipError("conv2d_x3s_prepare: %s stride %d is not a layer of the FPN encoder below full resolution" % (tuple(w.shape), stride))
-    prepared = torch.empty(n, device=w.device, dtype=torch.uint8)
-    _call("mvs_conv2d_x3s_prepare", None, _ptr(w), _ptr(scale), Cin, Cout, K, stride, _ptr(prepared), _stream())
-    return prepared
+    return _packed("mvs_conv2d_x3s_prepare", n, scale.numel() == Cout, "conv2d_x3s_prepare: %s stride %d is not a layer of the FPN encoder below full resolution",
+                   (tuple(w.shape), stride), w, torch.uint8, _ptr(w), _ptr(scale), Cin, Cout, K, stride)
 
 
 def conv2d_x3s_bn_lrelu(x: torch.Tensor, prepared: torch.Tensor, shift: torch.Tensor, Cout: int, K: int, stride: int, slope: float, x_nhwc: bool = False) -> torch.Tensor:
@@ -2268,7 +2210,7 @@ def conv2d_x3s_bn_lrelu(x: torch.Tensor, prepared: torch.Tensor, shift: torch.Te
     if prepared.numel() != int(_lib.load().mvs_conv2d_x3s_prepared_bytes(Cin, Cout, K, stride)) or shift.numel() != Cout:
         raise _lib.MvsHipError("conv2d_x3s_bn_lrelu: operands do not match (Cin,Cout,K,stride)=(%d,%d,%d,%d)" % (Cin, Cout, K, stride))
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    y = torch.empty(N, Cout, Ho, Wo, device=x.device, dtype=torch.float32)
+    y = _new(x, N, Cout, Ho, Wo)
     tag = ("conv2d_x3s_kernel<%d,%d,%d,%d>" % (Cin, Cout, K, stride), "flops", 2.0 * K * K * Cin * Cout * N * Ho * Wo)
     _call("mvs_conv2d_x3s_bn_lrelu", tag, _ptr(x), 1 if x_nhwc else 0, _ptr(prepared), _ptr(shift), N, Cin, Cout, K, stride, H, W, float(slope), _ptr(y), _stream())
     return y
@@ -2283,11 +2225,8 @@ def conv2d_x3_prepare(w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     _chk(w, "conv2d weight"), _chk(scale, "scale")
     Cout, Cin, K, K2 = w.shape
     n = int(_lib.load().mvs_conv2d_x3_prepared_bytes(Cin, Cout, K)) if K == K2 else -1
-    if n <= 0 or scale.numel() != Cout:
-        raise _lib.MvsHipError("conv2d_x3_prepare: %s is not conv00 / conv01 of the FPN encoder" % (tuple(w.shape),))
-    prepared = torch.empty(n, device=w.device, dtype=torch.uint8)
-    _call("mvs_conv2d_x3_prepare", None, _ptr(w), _ptr(scale), Cin, Cout, K, _ptr(prepared), _stream())
-    return prepared
+    return _packed("mvs_conv2d_x3_prepare", n, scale.numel() == Cout, "conv2d_x3_prepare: %s is not conv00 / conv01 of the FPN encoder", (tuple(w.shape),),
+                   w, torch.uint8, _ptr(w), _ptr(scale), Cin, Cout, K)
 
 
 def conv2d_x3_bn_lrelu(x: torch.Tensor, prepared: torch.Tensor, shift: torch.Tensor, Cout: int, K: int, slope: float, x_nhwc: bool = False,
@@ -2301,8 +2240,8 @@ def conv2d_x3_bn_lrelu(x: torch.Tensor, prepared: torch.Tensor, shift: torch.Ten
         N, Cin, H, W = x.shape
     if prepared.numel() != int(_lib.load().mvs_conv2d_x3_prepared_bytes(Cin, Cout, K)) or shift.numel() != Cout or out not in ("nchw", "nhwc", "both"):
         raise _lib.MvsHipError("conv2d_x3_bn_lrelu: operands do not match (Cin,Cout,K)=(%d,%d,%d) / out=%r" % (Cin, Cout, K, out))
-    y = torch.empty(N, Cout, H, W, device=x.device, dtype=torch.float32) if out != "nhwc" else None
-    ycl = torch.empty(N, H, W, Cout, device=x.device, dtype=torch.float32) if out != "nchw" else None
+    y = _new(x, N, Cout, H, W) if out != "nhwc" else None
+    ycl = _new(x, N, H, W, Cout) if out != "nchw" else None
     tag = ("enc_x3_kernel<%d,%d,%d>" % (Cin, Cout, K), "flops", 2.0 * K * K * Cin * Cout * N * H * W)
     _call("mvs_conv2d_x3_bn_lrelu_layout", tag, _ptr(x), 1 if x_nhwc else 0, _ptr(prepared), _ptr(shift), N, Cin, Cout, K, 1, H, W, float(slope),
           _ptr(y), _ptr(ycl), _stream())
@@ -2314,11 +2253,8 @@ def conv2d_pack_weights(w: torch.Tensor) -> torch.Tensor:
     _chk(w, "conv2d weight")
     Cout, Cin, K, K2 = w.shape
     n = int(_lib.load().mvs_conv2d_packed_floats(Cin, Cout, K)) if K == K2 else -1
-    if n <= 0:
-        raise _lib.MvsHipError("conv2d weight %s is not an FPN encoder layer shape" % (tuple(w.shape),))
-    packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    _call("mvs_conv2d_pack_weights", None, _ptr(w), Cin, Cout, K, _ptr(packed), _stream())
-    return packed
+    return _packed("mvs_conv2d_pack_weights", n, True, "conv2d weight %s is not an FPN encoder layer shape", (tuple(w.shape),), w, torch.float32,
+                   _ptr(w), Cin, Cout, K)
 
 
 def conv2d_bn_lrelu(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, cout: int, k: int, stride: int,
@@ -2329,7 +2265,7 @@ def conv2d_bn_lrelu(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, 
     if scale.numel() != cout or shift.numel() != cout or packed.numel() != int(_lib.load().mvs_conv2d_packed_floats(Cin, cout, k)):
         raise _lib.MvsHipError("conv2d_bn_lrelu: parameter sizes do not match (Cin,Cout,K)=(%d,%d,%d)" % (Cin, cout, k))
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    y = torch.empty(N, cout, Ho, Wo, device=x.device, dtype=torch.float32)
+    y = _new(x, N, cout, Ho, Wo)
     tag = ("conv2d_kernel<%d,%d,%d,%d>" % (Cin, cout, k, stride), "flops", 2.0 * k * k * Cin * cout * N * Ho * Wo)
     _call("mvs_conv2d_bn_lrelu", tag, _ptr(x), _ptr(packed), _ptr(scale), _ptr(shift), N, Cin, cout, k, stride, H, W, float(slope), _ptr(y),
           _stream())
@@ -2360,7 +2296,7 @@ def attention_x3(qkv: torch.Tensor, vt: torch.Tensor, heads: int, scale: float) 
     C = C3 // 3
     if vt.dim() != 4 or vt.shape[0] != B or vt.shape[1] != heads or vt.shape[2] * heads != C or not vt.is_contiguous():
         raise _lib.MvsHipError("attention_x3: vt %s for qkv %s, %d heads" % (tuple(vt.shape), tuple(qkv.shape), heads))
-    out = torch.empty(B, N, C, device=qkv.device, dtype=torch.float32)
+    out = _new(qkv, B, N, C)
     _call("mvs_attention_x3", ("x3_attention", "flops", 4.0 * B * heads * N * N * (C // heads)), _ptr(qkv), _ptr(vt), _ptr(out), B, N, heads,
           C // heads, int(vt.shape[3]), float(scale), _stream())
     return out
@@ -2397,7 +2333,7 @@ def bicubic_resize(x: torch.Tensor, Ho: int, Wo: int, rscale_h: float, rscale_w:
     """ATen's ``upsample_bicubic2d`` (align_corners=False) of ``[..., H, W]``; ``rscale`` = in / out, or 1 / scale_factor."""
     _chk(x, "x")
     H, W = x.shape[-2:]
-    out = torch.empty(tuple(x.shape[:-2]) + (Ho, Wo), device=x.device, dtype=torch.float32)
+    out = _new(x, tuple(x.shape[:-2]) + (Ho, Wo))
     _call("mvs_bicubic_resize", "bicubic_resize", _ptr(x), _ptr(out), x.numel() // (H * W), H, W, Ho, Wo, float(rscale_h), float(rscale_w), _stream())
     return out
 
@@ -2408,7 +2344,7 @@ def layernorm_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, ep
     _chk(x, "x"), _chk(gamma, "gamma"), _chk(beta, "beta")
     rows = x.numel() // x.shape[-1]
     y = torch.empty_like(x)
-    mean, rstd = (torch.empty(rows, device=x.device, dtype=torch.float32) for _ in range(2))
+    mean, rstd = (_new(x, rows) for _ in range(2))
     _call("mvs_layernorm_stats", "layernorm_stats", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), rows, x.shape[-1], float(eps),
           _stream())
     return y, mean, rstd
@@ -2434,8 +2370,8 @@ def colsum(dy: torch.Tensor, x: Optional[torch.Tensor] = None, mean: Optional[to
     n = getattr(_lib.load(), "mvs_colsum_workspace_floats")(rows, C, int(x is not None))
     if n < 0:
         raise _lib.MvsHipError("colsum: bad shape %s" % (tuple(dy.shape),))
-    ws = torch.empty(int(n), device=dy.device, dtype=torch.float32)
-    out = torch.empty(C * (2 if x is not None else 1), device=dy.device, dtype=torch.float32)
+    ws = _new(dy, int(n))
+    out = _new(dy, C * (2 if x is not None else 1))
     _call("mvs_colsum", "colsum", _ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), rows, C, _ptr(out), _ptr(ws), _stream())
     return out
 
@@ -2479,9 +2415,9 @@ def attention_train_fwd_flash(qkv: torch.Tensor, heads: int, scale: float, want_
     C = C3 // 3
     if C * 3 != C3 or heads < 1 or C % heads:
         raise _lib.MvsHipError("attention_train_fwd_flash: qkv %s for %d heads" % (tuple(qkv.shape), heads))
-    out = torch.empty(B, N, C, device=qkv.device, dtype=torch.float32)
-    lse = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32)
-    cls_row = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32) if want_cls else None
+    out = _new(qkv, B, N, C)
+    lse = _new(qkv, B, heads, N)
+    cls_row = _new(qkv, B, heads, N) if want_cls else None
     _call("mvs_attention_train_fwd_flash", "flash_train_fwd", _ptr(qkv), _ptr(out), _ptr(lse), _ptr(cls_row), B, N, heads, C // heads, float(scale),
           _stream())
     return (out, lse, cls_row) if want_cls else (out, lse)
@@ -2501,8 +2437,8 @@ def attention_train_bwd_flash(qkv: torch.Tensor, out: torch.Tensor, lse: torch.T
     n = getattr(_lib.load(), "mvs_attention_train_flash_workspace_bytes")(B, N, heads)
     if n < 0:
         raise _lib.MvsHipError("attention_train_bwd_flash: bad shape %s" % (tuple(qkv.shape),))
-    ws = torch.empty(int(n) // 4, device=qkv.device, dtype=torch.float32)
-    dqkv = torch.empty(B, N, C3, device=qkv.device, dtype=torch.float32)
+    ws = _new(qkv, int(n) // 4)
+    dqkv = _new(qkv, B, N, C3)
     _call("mvs_attention_train_bwd_flash", "flash_train_bwd", _ptr(qkv), _ptr(out), _ptr(lse), _ptr(dout), _ptr(da_cls), _ptr(dqkv), _ptr(ws), B, N,
           heads, C // heads, float(scale), _stream())
     return dqkv
@@ -2513,8 +2449,8 @@ def bicubic_resize_bwd(dout: torch.Tensor, H: int, W: int, rscale_h: float, rsca
     _chk(dout, "dout")
     Ho, Wo = dout.shape[-2:]
     planes = dout.numel() // (Ho * Wo)
-    din = torch.empty(tuple(dout.shape[:-2]) + (H, W), device=dout.device, dtype=torch.float32)
-    tmp = torch.empty(planes * Ho * W, device=dout.device, dtype=torch.float32)
+    din = _new(dout, tuple(dout.shape[:-2]) + (H, W))
+    tmp = _new(dout, planes * Ho * W)
     _call("mvs_bicubic_resize_bwd", "bicubic_bwd", _ptr(dout), _ptr(din), _ptr(tmp), planes, H, W, Ho, Wo, float(rscale_h), float(rscale_w), _stream())
     return din
 
@@ -2577,7 +2513,7 @@ def conv_x3p(X: Packed, W: Packed, mode: int, images: int, H: int, Wd: int, N: i
 
 
 def x3p_unpack(p: Packed) -> torch.Tensor:
-    x = torch.empty(p.rows, p.K, device=p.buf.device, dtype=torch.float32)
+    x = _new(p.buf, p.rows, p.K)
     _call("mvs_x3p_unpack", "x3p_unpack", p.ptr(), _ptr(x), p.rows, p.K, p.K, p.rows_alloc, _stream())
     return x
 
@@ -2613,9 +2549,9 @@ class QkvPacked:
     def __init__(self, images: int, heads: int, Np: int, device):
         self.images, self.heads, self.Np = images, heads, Np
         n = images * heads * (Np // 16) * 2 * 3072
-        self.q = torch.empty(n, device=device, dtype=torch.uint8)
-        self.k = torch.empty(n, device=device, dtype=torch.uint8)
-        self.vt = torch.empty(n, device=device, dtype=torch.uint8)
+        self.q = _new(device, n, dtype=torch.uint8)
+        self.k = _new(device, n, dtype=torch.uint8)
+        self.vt = _new(device, n, dtype=torch.uint8)
 
 
 def gemm_x3p_qkv(A: Packed, W: Packed, bias: Optional[torch.Tensor], images: int, Np: int, heads: int, scale: float, out: Optional[QkvPacked] = None) -> QkvPacked:
@@ -2644,7 +2580,7 @@ def attention_x3p(qkv: QkvPacked, N: int, out: Optional[Packed] = None) -> Packe
 
 def cls_attention_x3p(qkv: QkvPacked, N: int) -> torch.Tensor:
     """``[images, heads, N]``: the CLS query's attention row per head."""
-    att = torch.empty(qkv.images, qkv.heads, N, device=qkv.q.device, dtype=torch.float32)
+    att = _new(qkv.q, qkv.images, qkv.heads, N)
     _call("mvs_cls_attention_x3p", "x3p_cls_attention", qkv.q.data_ptr(), qkv.k.data_ptr(), _ptr(att), qkv.images, N, qkv.Np, qkv.heads, _stream())
     return att
 
@@ -2659,7 +2595,7 @@ def conv2d_fwd_x3(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int) -> to
     N, Cin, H, W = x.shape
     Cout, _, KS, _ = w.shape
     Ho, Wo = _conv2d_out(H, W, KS, stride, pad)
-    y = torch.empty(N, Cout, Ho, Wo, device=x.device, dtype=torch.float32)
+    y = _new(x, N, Cout, Ho, Wo)
     _call("mvs_conv2d_gemm_x3", ("x3_conv2d_fwd", "flops", 2.0 * N * Cout * Cin * KS * KS * Ho * Wo), 1, _ptr(w), _ptr(x), _ptr(y), N, Cin, Cout, H, W,
           Ho, Wo, KS, stride, pad, 0, _stream())
     return y
@@ -2671,7 +2607,7 @@ def conv2d_dgrad_x3(dy: torch.Tensor, w: torch.Tensor, stride: int, pad: int, H:
     N, Cout, Ho, Wo = dy.shape
     Cin, KS = w.shape[1], w.shape[2]
     wt = w.permute(1, 0, 2, 3).contiguous()                 # [Cin][Cout*KS*KS]
-    dx = torch.empty(N, Cin, H, W, device=dy.device, dtype=torch.float32)
+    dx = _new(dy, N, Cin, H, W)
     _call("mvs_conv2d_gemm_x3", ("x3_conv2d_dgrad", "flops", 2.0 * N * Cout * Cin * KS * KS * Ho * Wo), 2, _ptr(wt), _ptr(dy), _ptr(dx), N, Cin, Cout,
           H, W, Ho, Wo, KS, stride, pad, 0, _stream())
     return dx
@@ -2689,10 +2625,10 @@ def conv2d_wgrad_x3(dy: torch.Tensor, x: torch.Tensor, KS: int, stride: int, pad
     ksplit = max(32, ((K + want - 1) // want + 31) // 32 * 32)
     nsplit = (K + ksplit - 1) // ksplit
     n = Cout * Cin * KS * KS
-    part = torch.empty(N * nsplit, n, device=x.device, dtype=torch.float32)
+    part = _new(x, N * nsplit, n)
     _call("mvs_conv2d_gemm_x3", ("x3_conv2d_wgrad", "flops", 2.0 * N * Cout * Cin * KS * KS * Ho * Wo), 3, _ptr(dy), _ptr(x), _ptr(part), N, Cin, Cout,
           H, W, Ho, Wo, KS, stride, pad, ksplit, _stream())
-    dw = torch.empty(Cout, Cin, KS, KS, device=x.device, dtype=torch.float32)
+    dw = _new(x, Cout, Cin, KS, KS)
     _call("mvs_partials_reduce", "partials_reduce", _ptr(part), N * nsplit, n, _ptr(dw), _stream())
     return dw
 
@@ -2711,7 +2647,7 @@ def upsample2x_add(x: torch.Tensor, lateral: Optional[torch.Tensor]) -> torch.Te
     """``F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True) (+ lateral)``, fp32 NCHW."""
     _chk(x, "x"), _opt(lateral, "lateral")
     N, C, h, w = x.shape
-    y = torch.empty(N, C, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
+    y = _new(x, N, C, 2 * h, 2 * w)
     _call("mvs_upsample2x_add", "upsample2x_add", _ptr(x), _ptr(lateral), _ptr(y), N * C, h, w, _stream())
     return y
 
@@ -2719,14 +2655,14 @@ def upsample2x_add(x: torch.Tensor, lateral: Optional[torch.Tensor]) -> torch.Te
 def upsample2x_bwd(dy: torch.Tensor) -> torch.Tensor:
     _chk(dy, "dy")
     N, C, H, W = dy.shape
-    dx = torch.empty(N, C, H // 2, W // 2, device=dy.device, dtype=torch.float32)
+    dx = _new(dy, N, C, H // 2, W // 2)
     _call("mvs_upsample2x_bwd", "upsample2x_bwd", _ptr(dy), _ptr(dx), N * C, H // 2, W // 2, _stream())
     return dx
 
 
 # ------------------------------------------------------------------------------------- sample preparation (csrc/sample_prep.hip)
-PREP_VIEW_INTS = 8                                           # MVS_PREP_VIEW_INTS
-PREP_JITTER_INTS = 16                                        # MVS_PREP_JITTER_INTS
+PREP_VIEW_INTS = _H["MVS_PREP_VIEW_INTS"]
+PREP_JITTER_INTS = _H["MVS_PREP_JITTER_INTS"]
 
 
 def _chk_prep_tables(ptab, chosen, B, V):
@@ -2744,7 +2680,7 @@ def prep_accept(mask_raw, ptab, cand, crop_hw, require_positive=True, chosen=Non
     B, H0, W0 = mask_raw.shape
     V, K = ptab.shape[1], cand.shape[1]
     if chosen is None:
-        chosen = torch.empty(B, 4, device=mask_raw.device, dtype=torch.int32)
+        chosen = _new(mask_raw, B, 4, dtype=torch.int32)
     _chk_prep_tables(ptab, chosen, B, V)
     h, w = crop_hw
     _call("mvs_prep_accept", "prep_accept", _ptr(mask_raw), _ptr(ptab), _ptr(cand), B, V, H0, W0, int(h), int(w), K, int(bool(require_positive)),
@@ -2792,7 +2728,7 @@ def prep_area_crop(imgs, ptab, chosen, crop_hw):
     B, V, H0, W0, _ = imgs.shape
     _chk_prep_tables(ptab, chosen, B, V)
     h, w = int(crop_hw[0]), int(crop_hw[1])
-    out = torch.empty(B, V, h, w, 3, device=imgs.device, dtype=torch.uint8)
+    out = _new(imgs, B, V, h, w, 3, dtype=torch.uint8)
     _call("mvs_prep_area_crop", ("prep_area_crop", "bytes", float(B * V * h * w * 3) * 2), _ptr(imgs), _ptr(ptab), _ptr(chosen), B, V, H0, W0, h, w,
           _ptr(out), _stream())
     return out
@@ -2811,7 +2747,7 @@ def prep_jitter_tail(img, jtab=None, has_contrast=True, want_u8=False):
         if tuple(jtab.shape) != (B, PREP_JITTER_INTS):
             raise _lib.MvsHipError("prep_jitter_tail: jtab must be [%d,%d], got %s" % (B, PREP_JITTER_INTS, tuple(jtab.shape)))
     dev = img.device
-    lsum = torch.empty(B, V, device=dev, dtype=torch.int64) if augment and has_contrast else None
+    lsum = _new(dev, B, V, dtype=torch.int64) if augment and has_contrast else None
     out = torch.empty(B, V, 3, h, w, device=dev)
     u8 = torch.empty_like(img) if want_u8 else None
     _call("mvs_prep_jitter_tail", ("prep_jitter_tail", "bytes", float(B * V * h * w * 3) * 5), _ptr(img), _ptr(jtab), B, V, h, w, int(augment),
@@ -2827,7 +2763,7 @@ def prep_eval_resize(src, out_hw, pad_rows=0, want="f32"):
         raise _lib.MvsHipError("prep_eval_resize: src must be [V,H0,W0,3], got %s (want=%r)" % (tuple(src.shape), want))
     V, H0, W0, _ = src.shape
     H, W = int(out_hw[0]), int(out_hw[1])
-    u8 = torch.empty(V, H, W, 3, device=src.device, dtype=torch.uint8) if want != "f32" else None
+    u8 = _new(src, V, H, W, 3, dtype=torch.uint8) if want != "f32" else None
     f32 = torch.empty(V, 3, H, W, device=src.device) if want != "u8" else None
     _call("mvs_prep_eval_resize", ("prep_eval_resize", "bytes", float(V * H * W * 3) * 5), _ptr(src), V, H0, W0, H, W, int(pad_rows), _ptr(u8),
           _ptr(f32), _stream())

@@ -30,6 +30,55 @@ def test_header_matches_ctypes_table():
     assert set(names) == set(_lib.SIGNATURES), set(names) ^ set(_lib.SIGNATURES)
     for n, (_, args) in _lib.SIGNATURES.items():
         assert protos[n] == len(args), (n, protos[n], len(args))
+    # the table is parsed from the header: pin its size and rows that exercise every type, so this is no comparison of a parser with itself
+    from ctypes import c_char_p, c_double as Dbl, c_float, c_int as I, c_int64 as L, c_void_p as P
+    sig = _lib.SIGNATURES
+    assert len(sig) == 224
+    assert sig["mvs_last_error"] == (c_char_p, [])
+    assert sig["mvs_x3p_bytes"] == (L, [L, I])
+    assert sig["mvs_cloud_bounds"] == (I, [P, L, P, P, P, P])
+    assert sig["mvs_bn_finalize"][1][5:8] == [c_float, c_float, Dbl]
+    assert sig["mvs_align_crop_polygon"] == (I, [P, L, I, Dbl, Dbl, P, I, P, P])
+
+
+def test_header_parser_refuses_unknown_types_and_ignores_comments():
+    from ctypes import c_float, c_int, c_int64, c_void_p
+    from mvsformer_amd import _lib
+    with pytest.raises(TypeError, match="mvs_x"):
+        _lib.parse_header("int mvs_x(long double a);")
+    with pytest.raises(TypeError, match="mvs_y"):
+        _lib.parse_header("unsigned mvs_y(int a);")
+    with pytest.raises(TypeError):
+        _lib.parse_header("int (*mvs_callback)(int a);")
+    text = ("#define MVS_N 7\n#define MVS_NEG (-3)\n"
+            "/* call it as mvs_z(x, n); never twice */\n"
+            "int mvs_z(const float* x, /* rows); */ int64_t n,   // a trailing note);\n"
+            "          float eps, mvs_stream_t stream);\n")
+    sigs, defines = _lib.parse_header(text)
+    assert sigs == {"mvs_z": (c_int, [c_void_p, c_int64, c_float, c_void_p])}
+    assert defines == {"MVS_N": 7, "MVS_NEG": -3}
+
+
+def test_python_constants_are_the_header_macros():
+    """Every ``MVS_<NAME>`` integer macro that ``_lib`` or ``ops`` mirrors as ``<NAME>`` has the header's value (read here with the test's
+    own regex), the mirrored set is the expected one, and a few are pinned as literals."""
+    from mvsformer_amd import _lib, ops
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    macros = {k: int(v) for k, v in re.findall(r"^#define\s+MVS_(\w+)\s+\(?(-?\d+)\)?\s*$", src, flags=re.M)}
+    mirrored = {}
+    for name, value in macros.items():
+        for mod in (_lib, ops):
+            if hasattr(mod, name):
+                assert getattr(mod, name) == value, (mod.__name__, name)
+                mirrored[name] = mod.__name__.rsplit(".", 1)[1]
+    assert mirrored == dict({n: "ops" for n in (
+        "VIS_PARAM_FLOATS", "VIS_WINO_FLOATS", "VIS_X3_BYTES", "DEPTH_METRICS_BLOCK_PIXELS", "DEPTH_METRICS_MAX_K", "CLOUD_GRID_RECORD_BYTES",
+        "CLOUD_SCORE_RECORD_BYTES", "CLOUD_MAX_AXIS_CELLS", "CLOUD_MAX_SHELLS", "CLOUD_SCORE_MAX_K", "GREEDY_THIN_BATCH", "ALIGN_CROP_MAX_K",
+        "ALIGN_PAIR_RECORD_BYTES", "ALIGN_PAIR_MAX_ROWS", "PREP_VIEW_INTS", "PREP_JITTER_INTS")}, ABI_VERSION="_lib", ADAM_HYPER_STRIDE="_lib")
+    assert _lib.ABI_VERSION == 51
+    assert ops.VIS_PARAM_FLOATS == 3689
+    assert ops.CLOUD_MAX_AXIS_CELLS == 2097152
+    assert ops.ALIGN_PAIR_RECORD_BYTES == 192
 
 
 def test_library_exports_every_symbol():
