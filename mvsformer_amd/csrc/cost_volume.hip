@@ -782,7 +782,8 @@ struct TransposeJobs {
     long long HW[4];
     int C[4], vec[4], start[5], n;
 };
-__device__ __forceinline__ int tp_of(int C) { return C <= 16 ? 256 : (C == 32 ? 128 : 64); }
+// tile pixels of a transpose of C channels (8-16 KB of LDS per block whatever C); the host entries size their grids with it
+__host__ __device__ __forceinline__ constexpr int tp_of(int C) { return C <= 16 ? 256 : (C == 32 ? 128 : 64); }
 __global__ __launch_bounds__(256) void nchw_to_nhwc_multi_kernel(const TransposeJobs jobs) {
     __shared__ __attribute__((aligned(16))) float tile[64 * 68];          // the largest of the four tile shapes (17 KB)
     int j = 0;
@@ -799,10 +800,16 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_multi_kernel(const Transpose
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// host side.  Every sweep entry checks in one order - null pointers, check_shapes, the entry's own limits (rows, LDS, alignment, grid), the view
+// table of a bank - and launches nothing before all of them passed.
+// ---------------------------------------------------------------------------------------------------------
+constexpr bool c_is_built(int C) { return C == 8 || C == 16 || C == 32 || C == 64; }     // the channel counts the sweeps and the transposes are instantiated for
+
 int check_shapes(const char* who, int B, int V, int C, int Gin, int D, int H, int W) {
     MVS_REQUIRE(B >= 1 && V >= 2 && D >= 1 && H >= 1 && W >= 1, "%s: bad shape B=%d V=%d D=%d H=%d W=%d", who, B, V, D, H, W);
     MVS_REQUIRE(Gin == G, "%s: only G=8 correlation groups are built (got %d)", who, Gin);
-    MVS_REQUIRE(C == 8 || C == 16 || C == 32 || C == 64, "%s: C must be 8, 16, 32 or 64 (got %d)", who, C);
+    MVS_REQUIRE(c_is_built(C), "%s: C must be 8, 16, 32 or 64 (got %d)", who, C);
     MVS_REQUIRE((int64_t)B * (V - 1) <= 65535 && H <= 65535, "%s: grid limits exceeded", who);
     MVS_REQUIRE((int64_t)C * H * W * 4 < ((int64_t)1 << 32), "%s: one view's feature block exceeds the 4 GiB buffer range", who);
     return MVS_OK;
@@ -821,22 +828,52 @@ int fill_view_table(const char* who, const int* view_idx, int B, int V, int N, V
     }
     return MVS_OK;
 }
+// what a bank entry hands its launcher instead of a table: the launcher fills the table after its other checks (null: feat is dense [B,V,H,W,C])
+struct BankViews { const int* view_idx; int N; };
+
+// The host plan of a sweep launch: gx blocks of pixels_per_block pixels along a row, times `rows` rows, times z (samples, or samples x source views), as a
+// 1-D grid rounded up to a multiple of 8 for xcd_block (which drops the blocks from `total` on); NW wavefronts per block.
+struct SweepGrid { int gx, total; dim3 grid, block; };
+int sweep_grid(const char* who, int W, int rows, int64_t z, int pixels_per_block, SweepGrid* g) {
+    g->gx = mvs::ceil_div(W, pixels_per_block);
+    const int64_t total64 = (int64_t)g->gx * rows * z;
+    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "%s: too many blocks", who);
+    g->total = (int)total64;
+    g->grid = dim3((unsigned)(((g->total + 7) / 8) * 8));
+    g->block = dim3(64 * NW);
+    return MVS_OK;
+}
+
+// Runtime choice -> template arguments, once for the three sweeps: f(integral_constant<int, LPP>, bool_constant<flag>..., [ViewTable]) is called with the one of
+// LPPS that equals LPP, the flags in the order given and - when feat is a bank - the table as a trailing argument, so f's `auto... view` is the kernel's VT pack
+// and f names its kernel once.
+template <class F> void with_flags(F&& f) { f(); }
+template <class F, class... Bs> void with_flags(F&& f, bool b, Bs... rest) {
+    auto next = [&](auto c) { with_flags([&](auto... cs) { f(c, cs...); }, rest...); };
+    if (b) next(std::true_type{}); else next(std::false_type{});
+}
+template <int... LPPS, class F, class... Bs> void sweep_dispatch(int LPP, const ViewTable* views, F&& f, Bs... flags) {
+    with_flags([&](auto... fl) {
+        auto one = [&](auto lpp) { if (views) f(lpp, fl..., *views); else f(lpp, fl...); };
+        (void)((LPP == LPPS && (one(std::integral_constant<int, LPPS>{}), true)) || ...);
+    }, flags...);
+}
 
 }  // namespace
 
 extern "C" int mvs_nchw_to_nhwc(const float* in, float* out, int N, int C, int64_t HW, mvs_stream_t stream) {
     MVS_REQUIRE(in && out, "mvs_nchw_to_nhwc: null pointer");
     MVS_REQUIRE(N >= 1 && N <= 65535 && HW >= 1, "mvs_nchw_to_nhwc: bad shape N=%d HW=%lld", N, (long long)HW);
-    MVS_REQUIRE(C == 8 || C == 16 || C == 32 || C == 64, "mvs_nchw_to_nhwc: C must be 8, 16, 32 or 64 (got %d)", C);
+    MVS_REQUIRE(c_is_built(C), "mvs_nchw_to_nhwc: C must be 8, 16, 32 or 64 (got %d)", C);
     hipStream_t s = MVS_STREAM(stream);
     const int vec_ok = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) & 15) == 0);
-#define MVS_LAUNCH_T(CC, TP) \
-    hipLaunchKernelGGL((nchw_to_nhwc_kernel<CC, TP>), dim3((unsigned)((HW + TP - 1) / TP), N), dim3(256), 0, s, in, out, (size_t)HW, vec_ok)
-    switch (C) {                                             // 8-16 KB of LDS per block whatever C
-        case 8: MVS_LAUNCH_T(8, 256); break;
-        case 16: MVS_LAUNCH_T(16, 256); break;
-        case 32: MVS_LAUNCH_T(32, 128); break;
-        default: MVS_LAUNCH_T(64, 64); break;
+    const dim3 grid((unsigned)((HW + tp_of(C) - 1) / tp_of(C)), N);
+#define MVS_LAUNCH_T(CC) hipLaunchKernelGGL((nchw_to_nhwc_kernel<CC, tp_of(CC)>), grid, dim3(256), 0, s, in, out, (size_t)HW, vec_ok)
+    switch (C) {
+        case 8: MVS_LAUNCH_T(8); break;
+        case 16: MVS_LAUNCH_T(16); break;
+        case 32: MVS_LAUNCH_T(32); break;
+        default: MVS_LAUNCH_T(64); break;
     }
 #undef MVS_LAUNCH_T
     return mvs::finish_launch("mvs_nchw_to_nhwc");
@@ -851,8 +888,8 @@ extern "C" int mvs_nchw_to_nhwc_multi(const float* const* in, float* const* out,
     jobs.start[0] = 0;
     for (int j = 0; j < njobs; ++j) {
         MVS_REQUIRE(in[j] && out[j] && N[j] >= 1 && HW[j] >= 1, "mvs_nchw_to_nhwc_multi: job %d: bad shape", j);
-        MVS_REQUIRE(C[j] == 8 || C[j] == 16 || C[j] == 32 || C[j] == 64, "mvs_nchw_to_nhwc_multi: C must be 8, 16, 32 or 64 (got %d)", C[j]);
-        const int tp = C[j] <= 16 ? 256 : (C[j] == 32 ? 128 : 64);
+        MVS_REQUIRE(c_is_built(C[j]), "mvs_nchw_to_nhwc_multi: C must be 8, 16, 32 or 64 (got %d)", C[j]);
+        const int tp = tp_of(C[j]);
         const int64_t blocks = (int64_t)N[j] * ((HW[j] + tp - 1) / tp);
         MVS_REQUIRE(jobs.start[j] + blocks < ((int64_t)1 << 31), "mvs_nchw_to_nhwc_multi: too many tiles");
         jobs.in[j] = in[j], jobs.out[j] = out[j], jobs.HW[j] = HW[j], jobs.C[j] = C[j];
@@ -863,147 +900,77 @@ extern "C" int mvs_nchw_to_nhwc_multi(const float* const* in, float* const* out,
     return mvs::finish_launch("mvs_nchw_to_nhwc_multi");
 }
 
+namespace {
+// Sweep A.  `bank`: feat is a bank [N,H,W,C] and view v of sample b is block view_idx[b*V + v] (HOST array, column 0 = the reference view).
+int entropy_launch(const char* who, const float* feat, const float* rt, const float* depth, int B, int V, int C, int Gin, int D, int H, int W, float* entropy,
+                   int flags, mvs_stream_t stream, const BankViews* bank = nullptr) {
+    MVS_REQUIRE(feat && rt && depth && entropy, "%s: null pointer", who);
+    if (int rc = check_shapes(who, B, V, C, Gin, D, H, W)) return rc;
+    const int LPP = C / 4, PPW = 64 / LPP;
+    const size_t lds = (size_t)NW * 128 * 32 + (size_t)NW * PPW * D * sizeof(float);
+    MVS_REQUIRE(lds <= 64 * 1024, "%s: D=%d with C=%d needs %zu bytes of LDS (> 64 KiB)", who, D, C, lds);
+    SweepGrid g;
+    if (int rc = sweep_grid(who, W, H, (int64_t)B * (V - 1), NW * PPW, &g)) return rc;
+    ViewTable table;
+    if (bank) if (int rc = fill_view_table(who, bank->view_idx, B, V, bank->N, &table)) return rc;
+    hipStream_t s = MVS_STREAM(stream);
+    sweep_dispatch<2, 4, 8, 16>(LPP, bank ? &table : nullptr, [&](auto lpp, auto fast, auto... view) {
+        hipLaunchKernelGGL((cv_entropy_kernel<decltype(lpp)::value, decltype(fast)::value, decltype(view)...>), g.grid, g.block, lds, s, feat, rt, depth, V, D, H, W,
+                           entropy, g.gx, g.total, view...);
+    }, !(flags & 1));
+    return mvs::finish_launch(who);
+}
+
+// Sweep B.  volume16 (dense entries only; the bank entry has none and passes null): the volume ALSO as bf16 channel-last [B,D,H,W,G].
+int aggregate_launch(const char* who, const float* feat, const float* rt, const float* depth, const float* weight, int B, int V, int C, int Gin, int D, int H, int W,
+                     float* volume, void* volume16, float* sim_depth, int flags, mvs_stream_t stream, const BankViews* bank = nullptr) {
+    MVS_REQUIRE(feat && rt && depth && weight && volume, "%s: null pointer", who);
+    if (int rc = check_shapes(who, B, V, C, Gin, D, H, W)) return rc;
+    const int LPP = C / 4, PPW = 64 / LPP;
+    const size_t lds = (size_t)NW * 128 * 32;
+    SweepGrid g;
+    if (int rc = sweep_grid(who, W, H, B, NW * PPW, &g)) return rc;
+    ViewTable table;
+    if (bank) if (int rc = fill_view_table(who, bank->view_idx, B, V, bank->N, &table)) return rc;
+    hipStream_t s = MVS_STREAM(stream);
+    __bf16* vol16 = reinterpret_cast<__bf16*>(volume16);
+    sweep_dispatch<2, 4, 8, 16>(LPP, bank ? &table : nullptr, [&](auto lpp, auto sim, auto fast, auto... view) {
+        hipLaunchKernelGGL((cv_aggregate_kernel<decltype(lpp)::value, decltype(sim)::value, decltype(fast)::value, decltype(view)...>), g.grid, g.block, lds, s, feat,
+                           rt, depth, weight, V, D, H, W, volume, sim_depth, g.gx, g.total, view..., vol16);
+    }, sim_depth != nullptr, !(flags & 1));
+    return mvs::finish_launch(who);
+}
+}  // namespace
+
 extern "C" int mvs_cv_entropy_fwd(const float* feat, const float* rt, const float* depth, int B, int V, int C, int Gin, int D,
                                   int H, int W, float* entropy, int flags, mvs_stream_t stream) {
-    MVS_REQUIRE(feat && rt && depth && entropy, "mvs_cv_entropy_fwd: null pointer");
-    if (int rc = check_shapes("mvs_cv_entropy_fwd", B, V, C, Gin, D, H, W)) return rc;
-    const int LPP = C / 4, PPW = 64 / LPP;
-    const size_t lds = (size_t)NW * 128 * 32 + (size_t)NW * PPW * D * sizeof(float);
-    MVS_REQUIRE(lds <= 64 * 1024, "mvs_cv_entropy_fwd: D=%d with C=%d needs %zu bytes of LDS (> 64 KiB)", D, C, lds);
-    const int gx = mvs::ceil_div(W, NW * PPW);
-    const int64_t total64 = (int64_t)gx * H * B * (V - 1);
-    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "mvs_cv_entropy_fwd: too many blocks");
-    const int total = (int)total64;
-    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
-    hipStream_t s = MVS_STREAM(stream);
-    const bool fast = !(flags & 1);
-#define MVS_LAUNCH_ENT(L)                                                                                                       \
-    if (fast) hipLaunchKernelGGL((cv_entropy_kernel<L, true>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, gx, total); \
-    else hipLaunchKernelGGL((cv_entropy_kernel<L, false>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, gx, total)
-    switch (LPP) {
-        case 2: MVS_LAUNCH_ENT(2); break;
-        case 4: MVS_LAUNCH_ENT(4); break;
-        case 8: MVS_LAUNCH_ENT(8); break;
-        default: MVS_LAUNCH_ENT(16); break;
-    }
-#undef MVS_LAUNCH_ENT
-    return mvs::finish_launch("mvs_cv_entropy_fwd");
+    return entropy_launch("mvs_cv_entropy_fwd", feat, rt, depth, B, V, C, Gin, D, H, W, entropy, flags, stream);
 }
 
-// the same over a bank [N,H,W,C]: view v of sample b is bank block view_idx[b*V + v] (HOST array, column 0 = the reference view)
 extern "C" int mvs_cv_entropy_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, int B, int V, int C,
                                         int Gin, int D, int H, int W, float* entropy, int flags, mvs_stream_t stream) {
-    MVS_REQUIRE(bank && rt && depth && entropy, "mvs_cv_entropy_fwd_views: null pointer");
-    if (int rc = check_shapes("mvs_cv_entropy_fwd_views", B, V, C, Gin, D, H, W)) return rc;
-    ViewTable views;
-    if (int rc = fill_view_table("mvs_cv_entropy_fwd_views", view_idx, B, V, N, &views)) return rc;
-    const int LPP = C / 4, PPW = 64 / LPP;
-    const size_t lds = (size_t)NW * 128 * 32 + (size_t)NW * PPW * D * sizeof(float);
-    MVS_REQUIRE(lds <= 64 * 1024, "mvs_cv_entropy_fwd_views: D=%d with C=%d needs %zu bytes of LDS (> 64 KiB)", D, C, lds);
-    const int gx = mvs::ceil_div(W, NW * PPW);
-    const int64_t total64 = (int64_t)gx * H * B * (V - 1);
-    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "mvs_cv_entropy_fwd_views: too many blocks");
-    const int total = (int)total64;
-    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
-    hipStream_t s = MVS_STREAM(stream);
-    const bool fast = !(flags & 1);
-#define MVS_LAUNCH_ENT(L)                                                                                                                          \
-    if (fast) hipLaunchKernelGGL((cv_entropy_kernel<L, true, ViewTable>), grid, block, lds, s, bank, rt, depth, V, D, H, W, entropy, gx, total, views); \
-    else hipLaunchKernelGGL((cv_entropy_kernel<L, false, ViewTable>), grid, block, lds, s, bank, rt, depth, V, D, H, W, entropy, gx, total, views)
-    switch (LPP) {
-        case 2: MVS_LAUNCH_ENT(2); break;
-        case 4: MVS_LAUNCH_ENT(4); break;
-        case 8: MVS_LAUNCH_ENT(8); break;
-        default: MVS_LAUNCH_ENT(16); break;
-    }
-#undef MVS_LAUNCH_ENT
-    return mvs::finish_launch("mvs_cv_entropy_fwd_views");
+    const BankViews views{view_idx, N};
+    return entropy_launch("mvs_cv_entropy_fwd_views", bank, rt, depth, B, V, C, Gin, D, H, W, entropy, flags, stream, &views);
 }
-
-static int cv_aggregate_impl(const float* feat, const float* rt, const float* depth, const float* weight, int B, int V, int C, int Gin, int D, int H,
-                             int W, float* volume, void* volume16, float* sim_depth, int flags, mvs_stream_t stream);
 
 extern "C" int mvs_cv_aggregate_fwd(const float* feat, const float* rt, const float* depth, const float* weight, int B, int V,
                                     int C, int Gin, int D, int H, int W, float* volume, float* sim_depth, int flags,
                                     mvs_stream_t stream) {
-    return cv_aggregate_impl(feat, rt, depth, weight, B, V, C, Gin, D, H, W, volume, nullptr, sim_depth, flags, stream);
+    return aggregate_launch("mvs_cv_aggregate_fwd", feat, rt, depth, weight, B, V, C, Gin, D, H, W, volume, nullptr, sim_depth, flags, stream);
 }
 
-// the same + volume16: the volume ALSO as bf16 channel-last [B,D,H,W,G] (device bf16), the layout the bf16 training regularizer reads
+// the same + volume16, the layout the bf16 training regularizer reads
 extern "C" int mvs_cv_aggregate_fwd_bf16(const float* feat, const float* rt, const float* depth, const float* weight, int B, int V, int C, int Gin,
                                          int D, int H, int W, float* volume, void* volume16, float* sim_depth, int flags, mvs_stream_t stream) {
     MVS_REQUIRE(volume16, "mvs_cv_aggregate_fwd_bf16: null volume16");
-    return cv_aggregate_impl(feat, rt, depth, weight, B, V, C, Gin, D, H, W, volume, volume16, sim_depth, flags, stream);
-}
-
-static int cv_aggregate_impl(const float* feat, const float* rt, const float* depth, const float* weight, int B, int V, int C, int Gin, int D, int H,
-                             int W, float* volume, void* volume16, float* sim_depth, int flags, mvs_stream_t stream) {
-    __bf16* vol16 = reinterpret_cast<__bf16*>(volume16);
-    MVS_REQUIRE(feat && rt && depth && weight && volume, "mvs_cv_aggregate_fwd: null pointer");
-    if (int rc = check_shapes("mvs_cv_aggregate_fwd", B, V, C, Gin, D, H, W)) return rc;
-    const int LPP = C / 4, PPW = 64 / LPP;
-    const int gx = mvs::ceil_div(W, NW * PPW);
-    const int64_t total64 = (int64_t)gx * H * B;
-    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "mvs_cv_aggregate_fwd: too many blocks");
-    const int total = (int)total64;
-    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
-    hipStream_t s = MVS_STREAM(stream);
-    const size_t lds = (size_t)NW * 128 * 32;
-    const bool fast = !(flags & 1);
-#define MVS_LAUNCH_AGG2(L, SIMV, FASTV)                                                                                  \
-    hipLaunchKernelGGL((cv_aggregate_kernel<L, SIMV, FASTV>), grid, block, lds, s, feat, rt, depth, weight, V, D, H, W, volume, \
-                       sim_depth, gx, total, vol16)
-#define MVS_LAUNCH_AGG(L)                                                              \
-    if (sim_depth) {                                                                   \
-        if (fast) MVS_LAUNCH_AGG2(L, true, true); else MVS_LAUNCH_AGG2(L, true, false);   \
-    } else {                                                                           \
-        if (fast) MVS_LAUNCH_AGG2(L, false, true); else MVS_LAUNCH_AGG2(L, false, false); \
-    }
-    switch (LPP) {
-        case 2: MVS_LAUNCH_AGG(2); break;
-        case 4: MVS_LAUNCH_AGG(4); break;
-        case 8: MVS_LAUNCH_AGG(8); break;
-        default: MVS_LAUNCH_AGG(16); break;
-    }
-#undef MVS_LAUNCH_AGG
-#undef MVS_LAUNCH_AGG2
-    return mvs::finish_launch("mvs_cv_aggregate_fwd");
+    return aggregate_launch("mvs_cv_aggregate_fwd_bf16", feat, rt, depth, weight, B, V, C, Gin, D, H, W, volume, volume16, sim_depth, flags, stream);
 }
 
 extern "C" int mvs_cv_aggregate_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, const float* weight,
                                           int B, int V, int C, int Gin, int D, int H, int W, float* volume, float* sim_depth, int flags,
                                           mvs_stream_t stream) {
-    MVS_REQUIRE(bank && rt && depth && weight && volume, "mvs_cv_aggregate_fwd_views: null pointer");
-    if (int rc = check_shapes("mvs_cv_aggregate_fwd_views", B, V, C, Gin, D, H, W)) return rc;
-    ViewTable views;
-    if (int rc = fill_view_table("mvs_cv_aggregate_fwd_views", view_idx, B, V, N, &views)) return rc;
-    const int LPP = C / 4, PPW = 64 / LPP;
-    const int gx = mvs::ceil_div(W, NW * PPW);
-    const int64_t total64 = (int64_t)gx * H * B;
-    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "mvs_cv_aggregate_fwd_views: too many blocks");
-    const int total = (int)total64;
-    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
-    hipStream_t s = MVS_STREAM(stream);
-    const size_t lds = (size_t)NW * 128 * 32;
-    const bool fast = !(flags & 1);
-#define MVS_LAUNCH_AGG2(L, SIMV, FASTV)                                                                                                   \
-    hipLaunchKernelGGL((cv_aggregate_kernel<L, SIMV, FASTV, ViewTable>), grid, block, lds, s, bank, rt, depth, weight, V, D, H, W, volume, \
-                       sim_depth, gx, total, views, (__bf16*)nullptr)
-#define MVS_LAUNCH_AGG(L)                                                              \
-    if (sim_depth) {                                                                   \
-        if (fast) MVS_LAUNCH_AGG2(L, true, true); else MVS_LAUNCH_AGG2(L, true, false);   \
-    } else {                                                                           \
-        if (fast) MVS_LAUNCH_AGG2(L, false, true); else MVS_LAUNCH_AGG2(L, false, false); \
-    }
-    switch (LPP) {
-        case 2: MVS_LAUNCH_AGG(2); break;
-        case 4: MVS_LAUNCH_AGG(4); break;
-        case 8: MVS_LAUNCH_AGG(8); break;
-        default: MVS_LAUNCH_AGG(16); break;
-    }
-#undef MVS_LAUNCH_AGG
-#undef MVS_LAUNCH_AGG2
-    return mvs::finish_launch("mvs_cv_aggregate_fwd_views");
+    const BankViews views{view_idx, N};
+    return aggregate_launch("mvs_cv_aggregate_fwd_views", bank, rt, depth, weight, B, V, C, Gin, D, H, W, volume, nullptr, sim_depth, flags, stream, &views);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1031,7 +998,7 @@ extern "C" int64_t mvs_cv_corr_store_bytes(int B, int V, int C, int Gin, int D, 
 
 namespace {
 int corr_launch(const char* who, const float* feat, const float* rt, const float* depth, int B, int V, int C, int Gin, int D, int H, int W, int y0, int Hs,
-                float* entropy, void* store, int flags, mvs_stream_t stream, const ViewTable* views = nullptr) {
+                float* entropy, void* store, int flags, mvs_stream_t stream, const BankViews* bank = nullptr) {
     MVS_REQUIRE(feat && rt && depth && entropy && store, "%s: null pointer", who);
     if (int rc = check_shapes(who, B, V, C, Gin, D, H, W)) return rc;
     MVS_REQUIRE(C == 32 || C == 64, "%s: the stored-correlation sweeps are built for C = 32 and C = 64 (got %d)", who, C);
@@ -1043,25 +1010,15 @@ int corr_launch(const char* who, const float* feat, const float* rt, const float
     const StoreLayout l = store_layout(B, V, C, D, Hs, W);
     float* corr = static_cast<float*>(store);
     float* simv = corr + l.corr_floats;
-    const int gx = mvs::ceil_div(W, NW * PPW);
-    const int64_t total64 = (int64_t)gx * Hs * B * (V - 1);
-    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "%s: too many blocks", who);
-    const int total = (int)total64;
-    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
+    SweepGrid g;
+    if (int rc = sweep_grid(who, W, Hs, (int64_t)B * (V - 1), NW * PPW, &g)) return rc;
+    ViewTable table;
+    if (bank) if (int rc = fill_view_table(who, bank->view_idx, B, V, bank->N, &table)) return rc;
     hipStream_t s = MVS_STREAM(stream);
-    const bool fast = !(flags & 1);
-#define MVS_LAUNCH_CORR(L)                                                                                                                          \
-    if (fast) hipLaunchKernelGGL((cv_corr_kernel<L, true>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, y0, Hs); \
-    else hipLaunchKernelGGL((cv_corr_kernel<L, false>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, y0, Hs)
-#define MVS_LAUNCH_CORR_VIEWS(L)                                                                                                                     \
-    if (fast) hipLaunchKernelGGL((cv_corr_kernel<L, true, ViewTable>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, \
-                                 y0, Hs, *views);                                                                                                      \
-    else hipLaunchKernelGGL((cv_corr_kernel<L, false, ViewTable>), grid, block, lds, s, feat, rt, depth, V, D, H, W, entropy, corr, simv, gx, total, y0, Hs, *views)
-    if (views) {                                            // feat is a bank [N,H,W,C]
-        if (LPP == 16) { MVS_LAUNCH_CORR_VIEWS(16); } else { MVS_LAUNCH_CORR_VIEWS(8); }
-    } else if (LPP == 16) { MVS_LAUNCH_CORR(16); } else { MVS_LAUNCH_CORR(8); }
-#undef MVS_LAUNCH_CORR_VIEWS
-#undef MVS_LAUNCH_CORR
+    sweep_dispatch<8, 16>(LPP, bank ? &table : nullptr, [&](auto lpp, auto fast, auto... view) {
+        hipLaunchKernelGGL((cv_corr_kernel<decltype(lpp)::value, decltype(fast)::value, decltype(view)...>), g.grid, g.block, lds, s, feat, rt, depth, V, D, H, W, entropy,
+                           corr, simv, g.gx, g.total, y0, Hs, view...);
+    }, !(flags & 1));
     return mvs::finish_launch(who);
 }
 
@@ -1075,14 +1032,11 @@ int merge_launch(const char* who, const void* store, const float* depth, const f
     const StoreLayout l = store_layout(B, V, C, D, Hs, W);
     const float* corr = static_cast<const float*>(store);
     const float* simv = corr + l.corr_floats;
-    const int gx = mvs::ceil_div(l.XG, NW);
-    const int64_t total64 = (int64_t)gx * nrows * B;
-    MVS_REQUIRE(total64 < ((int64_t)1 << 30), "%s: too many blocks", who);
-    const int total = (int)total64;
-    dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(64 * NW);
+    SweepGrid g;                                            // along a row: the XG tile groups of the store, one per wavefront
+    if (int rc = sweep_grid(who, l.XG, nrows, B, NW, &g)) return rc;
     hipStream_t s = MVS_STREAM(stream);
-    if (l.TPX == 4) hipLaunchKernelGGL((cv_merge_kernel<4>), grid, block, 0, s, corr, simv, depth, weight, V, D, H, W, volume, sim_depth, gx, total, y0, Hs, r_lo, nrows);
-    else hipLaunchKernelGGL((cv_merge_kernel<8>), grid, block, 0, s, corr, simv, depth, weight, V, D, H, W, volume, sim_depth, gx, total, y0, Hs, r_lo, nrows);
+    if (l.TPX == 4) hipLaunchKernelGGL((cv_merge_kernel<4>), g.grid, g.block, 0, s, corr, simv, depth, weight, V, D, H, W, volume, sim_depth, g.gx, g.total, y0, Hs, r_lo, nrows);
+    else hipLaunchKernelGGL((cv_merge_kernel<8>), g.grid, g.block, 0, s, corr, simv, depth, weight, V, D, H, W, volume, sim_depth, g.gx, g.total, y0, Hs, r_lo, nrows);
     return mvs::finish_launch(who);
 }
 }  // namespace
@@ -1099,9 +1053,7 @@ extern "C" int mvs_cv_corr_rows_fwd(const float* feat, const float* rt, const fl
 
 extern "C" int mvs_cv_corr_rows_fwd_views(const float* bank, const int* view_idx, int N, const float* rt, const float* depth, int B, int V, int C, int Gin,
                                           int D, int H, int W, int y0, int rows, float* entropy, void* store, int flags, mvs_stream_t stream) {
-    MVS_REQUIRE(B >= 1 && V >= 2, "mvs_cv_corr_rows_fwd_views: bad shape B=%d V=%d", B, V);
-    ViewTable views;
-    if (int rc = fill_view_table("mvs_cv_corr_rows_fwd_views", view_idx, B, V, N, &views)) return rc;
+    const BankViews views{view_idx, N};
     return corr_launch("mvs_cv_corr_rows_fwd_views", bank, rt, depth, B, V, C, Gin, D, H, W, y0, rows, entropy, store, flags, stream, &views);
 }
 

@@ -24,14 +24,15 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def _chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
+def _chk(t: torch.Tensor, name: str, dtype=torch.float32, cur: Optional[int] = None) -> torch.Tensor:
+    """``cur``: ``torch.cuda.current_device()`` where the caller has read it already (a wrapper that checks several tensors asks once)."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise _lib.MvsHipError("%s must be a GPU tensor: the MI355X HIP path is the only implementation (no CPU fallback)" % name)
     if t.dtype != dtype:
         raise _lib.MvsHipError("%s must be %s, got %s" % (name, dtype, t.dtype))
     if not t.is_contiguous():
         raise _lib.MvsHipError("%s must be contiguous" % name)
-    if t.device.index != torch.cuda.current_device():
+    if t.device.index != (torch.cuda.current_device() if cur is None else cur):
         # kernels are launched on the CURRENT device's current stream; a tensor of another GPU would be dereferenced there
         raise _lib.MvsHipError("%s lives on %s but the current device is cuda:%d - wrap the call in torch.cuda.device(...)"
                                % (name, t.device, torch.cuda.current_device()))
@@ -257,14 +258,60 @@ def to_channels_last_multi(feats: List[torch.Tensor]) -> List[torch.Tensor]:
     return outs
 
 
-def _cv_dense_dims(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor):
-    """The checks of a sweep A over dense channel-last ``feat [B,V,H,W,C]`` -> ``(B, V, C, D, H, W)``."""
-    _chk(feat, "features"), _chk(rt, "rt"), _chk(depth, "depth_values")
-    B, V, H, W, C = feat.shape
-    D = depth.shape[1]
-    if depth.shape != (B, D, H, W):
-        raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, D, H, W), tuple(depth.shape)))
-    return B, V, C, D, H, W
+def _view_table(view_idx, who: str):
+    """``view_idx [B,V]`` (nested sequence, numpy array or CPU integer tensor; column 0 = the reference view) -> (ctypes int array, B, V).
+    A HOST table on purpose: the C entry checks every value against the bank before it launches and passes the table by value."""
+    if isinstance(view_idx, torch.Tensor):
+        if view_idx.is_cuda or view_idx.is_floating_point():
+            raise _lib.MvsHipError("%s: view_idx is a host table of integers (list, numpy array or CPU integer tensor)" % who)
+        view_idx = view_idx.tolist()
+    elif hasattr(view_idx, "tolist"):
+        view_idx = view_idx.tolist()
+    rows = [list(r) for r in view_idx]
+    if not rows or any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) < 2:
+        raise _lib.MvsHipError("%s: view_idx must be [B,V>=2]" % who)
+    raw = [v for r in rows for v in r]
+    flat = [int(v) for v in raw]
+    if flat != raw:
+        raise _lib.MvsHipError("%s: view_idx must hold integers" % who)
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in flat):
+        raise _lib.MvsHipError("%s: view_idx value outside the int range" % who)
+    return (ctypes.c_int * len(flat))(*flat), len(rows), len(rows[0])
+
+
+def _cv_source(feat: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, who: str, weight: Optional[torch.Tensor] = None):
+    """The sweeps' two feature sources, resolved in one place.  ``view_idx`` None: ``feat`` is dense channel-last ``[B,V,H,W,C]`` (see
+    :func:`to_channels_last`); else ``feat`` is a bank ``[N,H,W,C]`` and view ``v`` of sample ``b`` is ``feat[view_idx[b][v]]``.  Checks what the
+    sweeps ask of either (``depth [B,D,H,W]``, ``rt [B,V-1,12]``, ``weight [B,V-1,H,W]`` where the sweep has one) -> ``(B, V, C, D, H, W, head)``,
+    ``head`` = the entry's leading arguments ``(feat,)`` or ``(bank, table, N)``.  The sweeps below are one body each for both: the source
+    decides only ``head`` and which of the two (entry, launch tag) pairs written out in the body is used."""
+    f32, cur = torch.float32, torch.cuda.current_device()
+    _chk(rt, "rt", f32, cur), _chk(depth, "depth_values", f32, cur)
+    if weight is not None:
+        _chk(weight, "vis_weight", f32, cur)
+    if view_idx is None:
+        _chk(feat, "features", f32, cur)
+        fshape = feat.shape
+        if len(fshape) != 5:
+            raise _lib.MvsHipError("%s: features must be channel-last [B,V,H,W,C], got %s" % (who, tuple(fshape)))
+        B, V, H, W, C = fshape
+        head = (feat.data_ptr(),)
+    else:
+        _chk(feat, "feature bank", f32, cur)
+        if feat.dim() != 4:
+            raise _lib.MvsHipError("%s: the bank must be channel-last [N,H,W,C], got %s" % (who, tuple(feat.shape)))
+        table, B, V = _view_table(view_idx, who)
+        N, H, W, C = feat.shape
+        head = (_ptr(feat), table, N)
+    dshape = depth.shape
+    D = dshape[1] if len(dshape) == 4 else -1
+    if dshape != (B, D, H, W):
+        raise _lib.MvsHipError("%s: depth_values must be [B,D,H,W]=%s, got %s" % (who, (B, "D", H, W), tuple(dshape)))
+    if rt.shape != (B, V - 1, 12):
+        raise _lib.MvsHipError("%s: rt must be [B,V-1,12]=%s, got %s" % (who, (B, V - 1, 12), tuple(rt.shape)))
+    if weight is not None and weight.shape != (B, V - 1, H, W):
+        raise _lib.MvsHipError("%s: vis_weight must be [B,V-1,H,W]=%s, got %s" % (who, (B, V - 1, H, W), tuple(weight.shape)))
+    return B, V, C, D, H, W, head
 
 
 def _cv_volume(B: int, G: int, D: int, H: int, W: int, device, want_sim_depth: bool):
@@ -285,15 +332,22 @@ def _cv_corr_out(B: int, V: int, rows: int, W: int, nbytes: int, store: Optional
     return _new(device, B, V - 1, rows, W), store
 
 
-def cv_entropy(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None) -> torch.Tensor:
-    """``feat`` is channel-last ``[B,V,H,W,C]`` (see :func:`to_channels_last`)."""
-    B, V, C, D, H, W = _cv_dense_dims(feat, rt, depth)
+def _cv_entropy(feat: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool], who: str) -> torch.Tensor:
+    """Sweep A over either source of :func:`_cv_source`: entropy ``[B,V-1,H,W]``."""
+    B, V, C, D, H, W, head = _cv_source(feat, view_idx, rt, depth, who)
     ent = _new(feat, B, V - 1, H, W)
+    bank = view_idx is not None
     # algorithmic bytes of a sweep over ALL source views: features once + hypotheses once (SURVEY.md §8d); the entropy
     # maps themselves are <1 %
-    tag = ("cv_entropy_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
-    _call("mvs_cv_entropy_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _cv_flags(exact), _stream())
+    tag = (("cv_entropy_views_kernel<%d>" if bank else "cv_entropy_kernel<%d>") % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
+    _call("mvs_cv_entropy_fwd_views" if bank else "mvs_cv_entropy_fwd", tag, *head, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent),
+          _cv_flags(exact), _stream())
     return ent
+
+
+def cv_entropy(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None) -> torch.Tensor:
+    """``feat`` is channel-last ``[B,V,H,W,C]`` (see :func:`to_channels_last`)."""
+    return _cv_entropy(feat, None, rt, depth, G, exact, "cv_entropy")
 
 
 def _vis_launch(entry: str, kernel: str, entropy: torch.Tensor, *operands) -> torch.Tensor:
@@ -349,23 +403,31 @@ def vis_x3(entropy: torch.Tensor, params: torch.Tensor, prepared: torch.Tensor) 
     return _vis_launch("mvs_vis_x3_fwd", "vis_x3_kernel", entropy, params, prepared)
 
 
-def cv_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, G: int,
-                 want_sim_depth: bool, exact: Optional[bool] = None, want_bf16: bool = False):
-    """``want_bf16``: also return the volume as bf16 channel-last ``[B,D,H,W,G]`` (written by the same launch) -> ``(vol, sim, vol16)``."""
-    _chk(feat, "features"), _chk(rt, "rt"), _chk(depth, "depth_values"), _chk(weight, "vis_weight")
-    B, V, H, W, C = feat.shape
-    D = depth.shape[1]
+def _cv_aggregate(feat: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, G: int, want_sim_depth: bool,
+                  exact: Optional[bool], want_bf16: bool, who: str):
+    """Sweep B over either source of :func:`_cv_source` -> ``(volume [B,G,D,H,W], sim_depth [B,H,W] | None)``; ``want_bf16`` (dense only:
+    the library has no bank entry for it) appends the volume as bf16 channel-last ``[B,D,H,W,G]``, written by the same launch."""
+    if weight is None:
+        raise _lib.MvsHipError("%s: vis_weight is missing" % who)
+    B, V, C, D, H, W, head = _cv_source(feat, view_idx, rt, depth, who, weight)
     vol, sim = _cv_volume(B, G, D, H, W, feat.device, want_sim_depth)
-    tag = ("cv_aggregate_kernel<%d,%s>" % (C // 4, "true" if want_sim_depth else "false"), "bytes",
+    bank = view_idx is not None
+    tag = (("cv_aggregate_views_kernel<%d,%s>" if bank else "cv_aggregate_kernel<%d,%s>") % (C // 4, "true" if want_sim_depth else "false"), "bytes",
            4.0 * B * H * W * (V * C + D + G * D))          # SURVEY.md §8d: 4*H*W*(V*C + D + G*D)
     if want_bf16:
         vol16 = _new(feat, B, D, H, W, G, dtype=torch.bfloat16)
-        _call("mvs_cv_aggregate_fwd_bf16", tag, _ptr(feat), _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W,
+        _call("mvs_cv_aggregate_fwd_bf16", tag, *head, _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W,
               _ptr(vol), _ptr(vol16), _ptr(sim), _cv_flags(exact), _stream())
         return vol, sim, vol16
-    _call("mvs_cv_aggregate_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W,
+    _call("mvs_cv_aggregate_fwd_views" if bank else "mvs_cv_aggregate_fwd", tag, *head, _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W,
           _ptr(vol), _ptr(sim), _cv_flags(exact), _stream())
     return vol, sim
+
+
+def cv_aggregate(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, G: int,
+                 want_sim_depth: bool, exact: Optional[bool] = None, want_bf16: bool = False):
+    """``want_bf16``: also return the volume as bf16 channel-last ``[B,D,H,W,G]`` (written by the same launch) -> ``(vol, sim, vol16)``."""
+    return _cv_aggregate(feat, None, rt, depth, weight, G, want_sim_depth, exact, want_bf16, "cv_aggregate")
 
 
 def cv_store_bytes(feat: torch.Tensor, D: int, G: int) -> int:
@@ -376,14 +438,7 @@ def cv_store_bytes(feat: torch.Tensor, D: int, G: int) -> int:
 
 def cv_corr(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None):
     """Sweep A', coarse stages: entropy ``[B,V-1,H,W]`` as :func:`cv_entropy` plus the per-view correlation store for :func:`cv_merge`."""
-    B, V, C, D, H, W = _cv_dense_dims(feat, rt, depth)
-    nbytes = cv_store_bytes_of(B, V, C, G, D, H, W)
-    if nbytes <= 0:
-        raise _lib.MvsHipError("stored-correlation sweeps are built for C = 32 | 64, G = 8 (got C=%d, G=%d)" % (C, G))
-    ent, store = _cv_corr_out(B, V, H, W, nbytes, None, feat.device)
-    tag = ("cv_corr_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
-    _call("mvs_cv_corr_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _ptr(store), _cv_flags(exact), _stream())
-    return ent, store
+    return _cv_corr_rows(feat, None, rt, depth, G, 0, None, None, exact, "cv_corr")
 
 
 def cv_merge(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, V: int, C: int, G: int, want_sim_depth: bool):
@@ -398,18 +453,36 @@ def cv_merge(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, V: 
     return vol, sim
 
 
+def _cv_corr_rows(feat: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, G: int, y0: int, rows: Optional[int], store: Optional[torch.Tensor],
+                  exact: Optional[bool], who: str):
+    """Sweep A' over either source of :func:`_cv_source` on the band of reference rows ``[y0, y0 + rows)`` -> band-local entropy
+    ``[B,V-1,rows,W]`` and the store; ``rows`` None: the whole image through the entry without a band.  ``store`` is reused where it holds the
+    band, replaced by a new buffer where it does not."""
+    B, V, C, D, H, W, head = _cv_source(feat, view_idx, rt, depth, who)
+    bank = view_idx is not None
+    whole = rows is None and not bank                        # the entry without a band is a dense one
+    y0, rows = int(y0), H if rows is None else int(rows)
+    if y0 < 0 or rows < 1 or y0 + rows > H:
+        raise _lib.MvsHipError("%s: rows [%d, %d) outside the image (H = %d)" % (who, y0, y0 + rows, H))
+    nbytes = cv_store_bytes_of(B, V, C, G, D, rows, W)
+    if nbytes <= 0:
+        raise _lib.MvsHipError("%s: stored-correlation sweeps are built for C = 32 | 64, G = 8 and D within the LDS limit (got C=%d, G=%d, D=%d)" % (who, C, G, D))
+    if store is not None and store.numel() * 4 >= nbytes:
+        _chk(store, "correlation store")
+    ent, store = _cv_corr_out(B, V, rows, W, nbytes, store, feat.device)
+    tag = (("cv_corr_views_kernel<%d>" if bank else "cv_corr_kernel<%d>") % (C // 4), "bytes", 4.0 * B * rows * W * (V * C + D))
+    if whole:
+        _call("mvs_cv_corr_fwd", tag, *head, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _ptr(store), _cv_flags(exact), _stream())
+    else:
+        _call("mvs_cv_corr_rows_fwd_views" if bank else "mvs_cv_corr_rows_fwd", tag, *head, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, y0, rows,
+              _ptr(ent), _ptr(store), _cv_flags(exact), _stream())
+    return ent, store
+
+
 def cv_corr_rows(feat: torch.Tensor, rt: torch.Tensor, depth: torch.Tensor, G: int, y0: int, rows: int, store: Optional[torch.Tensor] = None,
                  exact: Optional[bool] = None):
     """Sweep A' on the band of reference rows ``[y0, y0 + rows)``: band-local entropy ``[B,V-1,rows,W]`` + store (``store``: a buffer to reuse)."""
-    B, V, C, D, H, W = _cv_dense_dims(feat, rt, depth)
-    nbytes = cv_store_bytes_of(B, V, C, G, D, rows, W)
-    if nbytes <= 0:
-        raise _lib.MvsHipError("stored-correlation sweeps are not built for C=%d, G=%d, D=%d" % (C, G, D))
-    ent, store = _cv_corr_out(B, V, rows, W, nbytes, store, feat.device)
-    tag = ("cv_corr_kernel<%d>" % (C // 4), "bytes", 4.0 * B * rows * W * (V * C + D))
-    _call("mvs_cv_corr_rows_fwd", tag, _ptr(feat), _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, int(y0), int(rows), _ptr(ent), _ptr(store),
-          _cv_flags(exact), _stream())
-    return ent, store
+    return _cv_corr_rows(feat, None, rt, depth, G, y0, rows, store, exact, "cv_corr_rows")
 
 
 def cv_merge_rows(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, V: int, C: int, G: int, y0: int, r_lo: int, nrows: int,
@@ -427,85 +500,23 @@ def cv_merge_rows(store: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor
 
 
 # ----------------------------------------------------------------------------------------------- sweeps over a feature bank
-def _view_table(view_idx, who: str):
-    """``view_idx [B,V]`` (nested sequence, numpy array or CPU integer tensor; column 0 = the reference view) -> (ctypes int array, B, V).
-    A HOST table on purpose: the C entry checks every value against the bank before it launches and passes the table by value."""
-    if isinstance(view_idx, torch.Tensor):
-        if view_idx.is_cuda or view_idx.is_floating_point():
-            raise _lib.MvsHipError("%s: view_idx is a host table of integers (list, numpy array or CPU integer tensor)" % who)
-        view_idx = view_idx.tolist()
-    elif hasattr(view_idx, "tolist"):
-        view_idx = view_idx.tolist()
-    rows = [list(r) for r in view_idx]
-    if not rows or any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) < 2:
-        raise _lib.MvsHipError("%s: view_idx must be [B,V>=2]" % who)
-    raw = [v for r in rows for v in r]
-    flat = [int(v) for v in raw]
-    if flat != raw:
-        raise _lib.MvsHipError("%s: view_idx must hold integers" % who)
-    if any(not -2 ** 31 <= v < 2 ** 31 for v in flat):
-        raise _lib.MvsHipError("%s: view_idx value outside the int range" % who)
-    return (ctypes.c_int * len(flat))(*flat), len(rows), len(rows[0])
-
-
-def _chk_bank(bank: torch.Tensor, view_idx, depth: torch.Tensor, who: str, rt: Optional[torch.Tensor] = None):
-    _chk(bank, "feature bank")
-    if bank.dim() != 4:
-        raise _lib.MvsHipError("%s: the bank must be channel-last [N,H,W,C], got %s" % (who, tuple(bank.shape)))
-    table, B, V = _view_table(view_idx, who)
-    N, H, W, C = bank.shape
-    D = depth.shape[1] if depth.dim() == 4 else -1
-    if depth.shape != (B, D, H, W):
-        raise _lib.MvsHipError("depth_values must be [B,D,H,W]=%s, got %s" % ((B, "D", H, W), tuple(depth.shape)))
-    if rt is not None and rt.shape != (B, V - 1, 12):
-        raise _lib.MvsHipError("rt must be [B,V-1,12]=%s, got %s" % ((B, V - 1, 12), tuple(rt.shape)))
-    return table, B, V, N, H, W, C, D
-
-
 def cv_entropy_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, G: int, exact: Optional[bool] = None) -> torch.Tensor:
     """:func:`cv_entropy` over a bank ``[N,H,W,C]``: view ``v`` of sample ``b`` is ``bank[view_idx[b][v]]``.  Bit-identical to the dense op on
     the gathered views."""
-    _chk(rt, "rt"), _chk(depth, "depth_values")
-    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_entropy_views", rt)
-    ent = _new(bank, B, V - 1, H, W)
-    tag = ("cv_entropy_views_kernel<%d>" % (C // 4), "bytes", 4.0 * B * H * W * (V * C + D))
-    _call("mvs_cv_entropy_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, _ptr(ent), _cv_flags(exact), _stream())
-    return ent
+    return _cv_entropy(bank, view_idx, rt, depth, G, exact, "cv_entropy_views")
 
 
 def cv_aggregate_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, weight: torch.Tensor, G: int, want_sim_depth: bool,
                        exact: Optional[bool] = None):
     """:func:`cv_aggregate` over a bank (see :func:`cv_entropy_views`) -> ``(volume [B,G,D,H,W], sim_depth [B,H,W] | None)``."""
-    _chk(rt, "rt"), _chk(depth, "depth_values"), _chk(weight, "vis_weight")
-    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_aggregate_views")
-    if rt.shape != (B, V - 1, 12) or weight.shape != (B, V - 1, H, W):
-        raise _lib.MvsHipError("cv_aggregate_views: rt %s / weight %s do not match B=%d V=%d H=%d W=%d" % (tuple(rt.shape), tuple(weight.shape), B, V, H, W))
-    vol, sim = _cv_volume(B, G, D, H, W, bank.device, want_sim_depth)
-    tag = ("cv_aggregate_views_kernel<%d,%s>" % (C // 4, "true" if want_sim_depth else "false"), "bytes", 4.0 * B * H * W * (V * C + D + G * D))
-    _call("mvs_cv_aggregate_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), _ptr(weight), B, V, C, G, D, H, W, _ptr(vol), _ptr(sim),
-          _cv_flags(exact), _stream())
-    return vol, sim
+    return _cv_aggregate(bank, view_idx, rt, depth, weight, G, want_sim_depth, exact, False, "cv_aggregate_views")
 
 
 def cv_corr_rows_views(bank: torch.Tensor, view_idx, rt: torch.Tensor, depth: torch.Tensor, G: int, y0: int, rows: int,
                        store: Optional[torch.Tensor] = None, exact: Optional[bool] = None):
     """:func:`cv_corr_rows` over a bank (see :func:`cv_entropy_views`); ``y0 = 0, rows = H`` is :func:`cv_corr`.  The store is read by
     :func:`cv_merge` / :func:`cv_merge_rows`, which never see features."""
-    _chk(rt, "rt"), _chk(depth, "depth_values")
-    table, B, V, N, H, W, C, D = _chk_bank(bank, view_idx, depth, "cv_corr_rows_views", rt)
-    y0, rows = int(y0), int(rows)
-    if y0 < 0 or rows < 1 or y0 + rows > H:
-        raise _lib.MvsHipError("cv_corr_rows_views: rows [%d, %d) outside the image (H = %d)" % (y0, y0 + rows, H))
-    nbytes = cv_store_bytes_of(B, V, C, G, D, rows, W)
-    if nbytes <= 0:
-        raise _lib.MvsHipError("stored-correlation sweeps are not built for C=%d, G=%d, D=%d" % (C, G, D))
-    if store is not None and store.numel() * 4 >= nbytes:
-        _chk(store, "correlation store")
-    ent, store = _cv_corr_out(B, V, rows, W, nbytes, store, bank.device)
-    tag = ("cv_corr_views_kernel<%d>" % (C // 4), "bytes", 4.0 * B * rows * W * (V * C + D))
-    _call("mvs_cv_corr_rows_fwd_views", tag, _ptr(bank), table, N, _ptr(rt), _ptr(depth), B, V, C, G, D, H, W, y0, rows, _ptr(ent), _ptr(store),
-          _cv_flags(exact), _stream())
-    return ent, store
+    return _cv_corr_rows(bank, view_idx, rt, depth, G, y0, rows, store, exact, "cv_corr_rows_views")
 
 
 def cv_bank_store_bytes(bank: torch.Tensor, B: int, V: int, D: int, G: int) -> int:

@@ -1,5 +1,6 @@
 """GPU tests of the argument checks of ``mvsformer_amd.ops`` that share a body: the 3-D conv-layer wrappers, the residual-shape check and
-the pack / prepare wrappers.  They allocate device tensors and launch NO kernel: ``ops._call`` is replaced by a recorder, so a refusal is
+the pack / prepare wrappers, and (at the end) the checks the dense cost-volume sweeps share with the bank forms plus the sweep entries' null
+checks straight through ctypes.  They allocate device tensors and launch NO kernel: ``ops._call`` is replaced by a recorder, so a refusal is
 shown to come before anything reaches the library, and an accepted call is compared with the entry name, timer tag, work amount and
 integer arguments written out here by hand (from the wrappers as they stood before they were folded, not computed by the code under test).
 Shapes are the smallest each form's ``*_supported`` query accepts: B = 1, an 8 x 8 x 8 volume, the smallest channel pair."""
@@ -210,3 +211,72 @@ def test_pack_and_prepare_wrappers_allocate_what_the_size_query_says(calls):
         packed = run()
         assert packed.dtype == dtype and tuple(packed.shape) == (n,) and packed.device == torch.device(DEV), entry
         assert calls == [(entry, None, head + (packed.data_ptr(), stream))], entry
+
+
+# ----------------------------------------------------------------------------------------------- the cost-volume sweeps
+def _sweep_args(C=8, H=24, W=40, D=4, B=1, V=3):
+    """Dense sweep operands at the 8-channel 24 x 40 x 4 shape: channel-last features, rt, hypotheses, visibility weights."""
+    return _t(B, V, H, W, C), _t(B, V - 1, 12), _t(B, D, H, W), _t(B, V - 1, H, W)
+
+
+def test_dense_sweep_wrappers_share_the_bank_forms_checks(calls):
+    """What the dense wrappers check since they share a body with the bank forms, each refused before anything reaches the library: hypotheses
+    that are not ``[B,D,H,W]``, an ``rt`` that is not ``[B,V-1,12]``, visibility weights that are not ``[B,V-1,H,W]``, a band of rows outside
+    the image (an empty one included)."""
+    from mvsformer_amd import ops
+    from mvsformer_amd._lib import MvsHipError
+    feat, rt, depth, weight = _sweep_args()
+    sweeps = {
+        "cv_entropy": lambda rt=rt, depth=depth: ops.cv_entropy(feat, rt, depth, 8),
+        "cv_aggregate": lambda rt=rt, depth=depth, weight=weight: ops.cv_aggregate(feat, rt, depth, weight, 8, True),
+        "cv_corr": lambda rt=rt, depth=depth: ops.cv_corr(feat, rt, depth, 8),
+        "cv_corr_rows": lambda rt=rt, depth=depth, y0=0, rows=24: ops.cv_corr_rows(feat, rt, depth, 8, y0, rows),
+    }
+    for name, run in sweeps.items():
+        for bad in (_t(1, 4, 24, 39), _t(1, 4, 23, 40), _t(2, 4, 24, 40), _t(4, 24, 40)):
+            with pytest.raises(MvsHipError, match=r"^%s: depth_values must be \[B,D,H,W\]" % name):
+                run(depth=bad)
+        for bad in (_t(1, 2, 16), _t(1, 3, 12), _t(2, 12)):
+            with pytest.raises(MvsHipError, match=r"^%s: rt must be \[B,V-1,12\]" % name):
+                run(rt=bad)
+    for bad in (_t(1, 2, 24, 39), _t(1, 3, 24, 40), _t(1, 2, 23, 40), _t(2, 24, 40)):
+        with pytest.raises(MvsHipError, match=r"^cv_aggregate: vis_weight must be \[B,V-1,H,W\]"):
+            sweeps["cv_aggregate"](weight=bad)
+    for y0, rows in ((-1, 4), (0, 25), (22, 3), (3, 0), (24, 1)):
+        with pytest.raises(MvsHipError, match=r"^cv_corr_rows: rows \[-?\d+, \d+\) outside the image \(H = 24\)"):
+            sweeps["cv_corr_rows"](y0=y0, rows=rows)
+    assert calls == []
+    ent = sweeps["cv_entropy"]()                               # the same operands unbroken: one launch of the dense entry, tag and work as before
+    (name, tag, args), = calls
+    assert name == "mvs_cv_entropy_fwd" and tag == ("cv_entropy_kernel<2>", "bytes", 4.0 * 24 * 40 * (3 * 8 + 4))
+    assert args[:-1] == (feat.data_ptr(), rt.data_ptr(), depth.data_ptr(), 1, 3, 8, 8, 4, 24, 40, ent.data_ptr(), ops._cv_flags(None))
+
+
+FAKE = 0x1000                                                  # a made-up address: the entries below return before reading any pointer
+DENSE, BANK = (FAKE,), (FAKE, FAKE, 7)                         # feat | bank, view_idx, N
+# entry -> (leading arguments up to the sizes, integers between W and the outputs, output pointers, which of them must not be null)
+SWEEP_ENTRIES = {
+    "mvs_cv_entropy_fwd": (DENSE + (FAKE, FAKE), (), 1, (0,)),
+    "mvs_cv_entropy_fwd_views": (BANK + (FAKE, FAKE), (), 1, (0,)),
+    "mvs_cv_aggregate_fwd": (DENSE + (FAKE, FAKE, FAKE), (), 2, (0,)),                 # volume; sim_depth is optional
+    "mvs_cv_aggregate_fwd_bf16": (DENSE + (FAKE, FAKE, FAKE), (), 3, (0, 1)),          # volume, volume16
+    "mvs_cv_aggregate_fwd_views": (BANK + (FAKE, FAKE, FAKE), (), 2, (0,)),
+    "mvs_cv_corr_fwd": (DENSE + (FAKE, FAKE), (), 2, (0, 1)),                          # entropy, store
+    "mvs_cv_corr_rows_fwd": (DENSE + (FAKE, FAKE), (0, 24), 2, (0, 1)),
+    "mvs_cv_corr_rows_fwd_views": (BANK + (FAKE, FAKE), (0, 24), 2, (0, 1)),
+}
+
+
+@pytest.mark.parametrize("entry", sorted(SWEEP_ENTRIES))
+def test_sweep_entries_refuse_a_null_output_under_their_own_name(entry):
+    """Straight through ctypes: each of the eight sweep entries, called with one of its mandatory output pointers null, returns an error code
+    and a message that begins with THAT entry's name (``mvs_cv_aggregate_fwd_bf16`` used to answer as ``mvs_cv_aggregate_fwd``).  The null
+    check is every entry's first, so nothing is read and nothing is launched."""
+    from mvsformer_amd import _lib
+    lib = _lib.load()
+    head, ints, nout, mandatory = SWEEP_ENTRIES[entry]
+    for null_at in mandatory:
+        outs = tuple(None if i == null_at else FAKE for i in range(nout))
+        rc = getattr(lib, entry)(*head, 1, 3, 32, 8, 4, 24, 40, *ints, *outs, 0, None)        # B, V, C, G, D, H, W ... flags, stream
+        assert rc != 0, (entry, null_at)
+        assert lib.mvs_last_error().startswith(entry.encode() + b": null"), (entry, null_at, lib.mvs_last_error())

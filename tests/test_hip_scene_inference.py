@@ -74,6 +74,42 @@ def test_indexed_sweeps_equal_dense_sweeps_bitwise(dev, C, h, w, D, case, fast, 
     torch.cuda.synchronize()
 
 
+@pytest.mark.parametrize("C,h,w,D", [(32, 16, 24, 16), (64, 8, 19, 32)])
+def test_banded_stored_correlation_over_a_bank_equals_dense_bitwise(dev, C, h, w, D):
+    """The band form with a table that repeats a view: ``cv_corr_rows_views`` == ``cv_corr_rows`` on the gathered views (entropy and store) for
+    the whole image as a band, an inner band and the last three rows, and ``cv_merge_rows`` builds the same rows of the volume from either
+    store and leaves the other rows alone.  At C = 32 also ``cv_corr`` == ``cv_corr_rows(0, H)``: one body, two entries."""
+    from mvsformer_amd import ops
+    tables = TABLES["repeated"]
+    N, G, B, V = 7, 8, 1, 5
+    bank, rt, hyp = _sweep_inputs(dev, N, tables, C, h, w, D, seed=11 + C)
+    dense = bank[torch.tensor(tables, device=dev)].contiguous()
+    weight = torch.rand(B, V - 1, h, w, generator=torch.Generator().manual_seed(2)).to(dev)
+    for y0, rows in ((0, h), (2, h - 4), (h - 3, 3)):
+        e0, s0 = ops.cv_corr_rows(dense, rt, hyp, G, y0, rows)
+        e1, s1 = ops.cv_corr_rows_views(bank, tables, rt, hyp, G, y0, rows)
+        assert e0.shape == (B, V - 1, rows, w)
+        assert torch.equal(e0, e1) and torch.equal(s0, s1), (y0, rows)
+        assert torch.isfinite(e0).all() and e0.abs().max() > 0
+        wb = weight[:, :, y0:y0 + rows].contiguous()
+        merged = []
+        for store in (s0, s1):
+            vol, sim = torch.full((B, G, D, h, w), -7.0, device=dev), torch.full((B, h, w), -7.0, device=dev)
+            ops.cv_merge_rows(store, hyp, wb, V, C, G, y0, 0, rows, vol, sim)
+            merged.append((vol, sim))
+        (v0, d0), (v1, d1) = merged
+        assert torch.equal(v0, v1) and torch.equal(d0, d1), (y0, rows)
+        inside = torch.zeros(h, dtype=torch.bool, device=dev)
+        inside[y0:y0 + rows] = True
+        assert (v0[:, :, :, ~inside] == -7).all() and (d0[:, ~inside] == -7).all()
+        assert (d0[:, inside] != -7).all() and v0[:, :, :, inside].abs().max() > 0
+    if C == 32:
+        ew, sw = ops.cv_corr(dense, rt, hyp, G)
+        er, sr = ops.cv_corr_rows(dense, rt, hyp, G, 0, h)
+        assert torch.equal(ew, er) and torch.equal(sw, sr)
+    torch.cuda.synchronize()
+
+
 def test_bad_view_table_is_an_error_before_any_launch(dev):
     """An index of N or -1 (or a table too large to travel by value) is refused by the entry's host check: an error, no kernel."""
     from mvsformer_amd import ops
