@@ -30,6 +30,10 @@
  *         ONE exception: the INTERNAL activations of mvs_vis_x3_fwd are split without the clamp (csrc/split3.h split3_pair<false>):
  *         a layer-1/2 activation above 3.3895e38 - reachable only through BatchNorm statistics that scale the entropy map
  *         (range [0, ln D]) by ~1e37 - turns into NaN instead of being carried exactly; its fp32 INPUT obeys the rule above;
+ *       * the split v = h + m + l is exact for every |v| >= 2^-110 (and for 0); below that the l term would need bits under the
+ *         smallest bf16 subnormal, 2^-133, and h + m + l is v to within 2^-126 (tests/test_hip_vit_packed_edges.py).  Where the
+ *         terms are added back in fp32 the order is h + (m + l): for |v| near FLT_MAX h is the largest bf16, m rounds up and
+ *         (h + m) alone is 2^128;
  *       * subnormal operands may be flushed to zero by the matrix cores: absolute error <= K * 2^-126 * max|other operand|;
  *       * a non-finite input (+-Inf, NaN) makes exactly the outputs whose receptive field contains it non-finite; the value is NaN
  *         where IEEE fp32 arithmetic would give +-Inf (Inf - Inf in the remainder terms).
@@ -1112,7 +1116,8 @@ int mvs_attention_train_bwd_flash(const float* qkv, const float* out, const floa
  * step, fp32 accumulation), fp32-equivalent.
  *   packed X [R][K] (K % 32 == 0, rows_alloc % 16 == 0 rows allocated): piece (rt = r/16, ks = k/32, term t) = 1 KiB of 64 lanes x 8 bf16 at
  *   byte ((rt * K/32 + ks) * 3 + t) * 1024, lane = ((k%32)/8)*16 + r%16, element k%8; mvs_x3p_bytes(rows_alloc, K) bytes in all.
- *   mvs_x3p_pack / mvs_x3p_unpack: fp32 [R][K] (rows ld apart) <-> packed (rows >= R packed as zeros; unpack is exact: h + m + l).
+ *   mvs_x3p_pack / mvs_x3p_unpack: fp32 [R][K] (rows ld apart) <-> packed (rows >= R packed as zeros; unpack returns h + (m + l):
+ *       v bit for bit for every |v| >= 2^-110, FLT_MAX included, within 2^-126 below; -0 comes back as +0).
  *   mvs_layernorm_x3p: LayerNorm (vision_transformer.py:199,207 norm1 / norm2) of rows laid out [images][Np] (Np % 16 == 0), written packed;
  *       rows t >= N of an image are padding: zeros.  32 <= C <= 512, C % 32 == 0.
  *   mvs_gemm_x3p: out = epi(A . B^T) with A [M][K] and B [N][K] packed (the nn.Linear layers: attn.proj, mlp.fc1, mlp.fc2);
@@ -1123,7 +1128,10 @@ int mvs_attention_train_bwd_flash(const float* qkv, const float* out, const floa
  *       a k step permuted (element e of chunk c <-> key (e < 4 ? 4c + e : 16 + 4c + e - 4)): the order mvs_attention_x3p's accumulators
  *       produce P in.  C = heads * 64, C % 128 == 0, Np % 32 == 0.
  *   mvs_attention_x3p: P V with P = 2^(Q K^T - reference) / row sum = softmax(scale * q k^T) for Qp as above, per (image, head), flash form,
- *       keys >= N masked; output packed [images * Np][heads * 64].
+ *       keys >= N masked; output packed [images * Np][heads * 64].  Rows < N do not depend, bit for bit, on the (finite) values the rows >= N of Qp / Kp / Vtp hold.
+ *       Output rows >= N are padding: finite when the padding rows of Qp give scores of ordinary size (zero rows of x do: q = bias); a
+ *       padding query that shares a 16-row tile with real ones does not raise the softmax reference on its own account, so padding content
+ *       whose score runs more than 128 (base 2) above the tile's reference makes that padding row Inf / NaN - and only that row.
  *   mvs_cls_attention_x3p: att [image][head][N] = that softmax's CLS row: the one attention row the model reads (mvsformer_model.py:257).
  * ------------------------------------------------------------------------------------------------------- */
 int64_t mvs_x3p_bytes(int64_t rows_alloc, int K);

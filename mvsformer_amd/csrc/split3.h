@@ -5,6 +5,7 @@
 //   * |v| above the largest finite bf16 (0x7F7F0000 = 3.3895e38) would round to +-Inf: h is clamped to that value (one v_med3_f32), the
 //     remainder (< 2^120) fits m and l exactly, so finite inputs up to FLT_MAX keep the exact three-term form;
 //   * +-Inf / NaN: the remainder v - h is Inf / NaN, so at least one term is non-finite and every output the value reaches is non-finite;
+//   * |v| < 2^-110: the last term would need bits below the smallest bf16 subnormal (2^-133): h + m + l is v to within 2^-126 only;
 //   * subnormal v: h, m, l are subnormal bf16 values; the matrix cores may flush them (absolute error <= 2^-126 per operand).
 #pragma once
 #include "prims.h"

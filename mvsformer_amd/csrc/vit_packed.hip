@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void x3p_unpack_kernel(const unsigned char* __
     const bf16x8 h = *reinterpret_cast<const bf16x8*>(s), m = *reinterpret_cast<const bf16x8*>(s + PIECE), l = *reinterpret_cast<const bf16x8*>(s + 2 * PIECE);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-        if (k0 + e < K) x[(size_t)r * ld + k0 + e] = ((float)h[e] + (float)m[e]) + (float)l[e];
+        if (k0 + e < K) x[(size_t)r * ld + k0 + e] = (float)h[e] + ((float)m[e] + (float)l[e]);      // (m + l first: at FLT_MAX h + m is 2^128)
 }
 
 // ---------------------------------------------------------------------------------------------------------------- LayerNorm -> packed
@@ -529,9 +529,17 @@ __global__ __launch_bounds__(256, 2) void attention_x3p_kernel(const void* __res
     // exact running maximum: any common reference gives the same softmax.  It is raised only when some lane of the wavefront sees a score
     // more than 8 (base-2 exponent: a factor 256) above it - after the first few key steps almost never - so the cross-lane maximum, the
     // rescale of O and their LDS-crossbar waits leave the steady state (P <= 256, exact in the split).
+    // Padding queries (rows >= N of a tile that also holds real ones) do not vote: whatever lies in the padding rows, the real rows of the
+    // tile take the same sequence of raises and come out bit for bit the same.  A tile of padding only votes as usual.  The price: a padding
+    // query of a mixed tile is no longer held to P <= 256 by its own vote; its reference moves only when a real row of the tile votes, so a
+    // padding row whose score climbs more than 128 above it overflows exp2 and that row of O (one MFMA column, nothing else) becomes
+    // Inf / NaN.  Zero padding (q = bias) stays far from that, and the next LayerNorm writes padding rows as zeros again.
+    bool votes[2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) votes[qt] = (qt0 + qt) * 16 + (lane & 15) < N || (qt0 + qt) * 16 >= N;
     auto raise_ref = [&](int qt, const f32x4 (&s)[2]) {
         const float lmax = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])), fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-        if (__builtin_amdgcn_ballot_w64(lmax > mrow[qt] + 8.0f) != 0) {
+        if (__builtin_amdgcn_ballot_w64(votes[qt] && lmax > mrow[qt] + 8.0f) != 0) {
             const float mnew = fmaxf(mrow[qt], xmax32(xmax16(lmax)));
             const float alpha = __builtin_amdgcn_exp2f(mrow[qt] - mnew);          // 0 at the first step (mrow = -inf)
             mrow[qt] = mnew;

@@ -2524,6 +2524,8 @@ def conv_x3p(X: Packed, W: Packed, mode: int, images: int, H: int, Wd: int, N: i
 
 
 def x3p_unpack(p: Packed) -> torch.Tensor:
+    """``h + (m + l)`` per element: the packed value bit for bit for every ``|v| >= 2**-110`` (FLT_MAX included; below that the ``l`` term
+    would need bits under the smallest bf16 subnormal and the sum is ``v`` to within ``2**-126``); ``-0`` comes back as ``+0``."""
     x = _new(p.buf, p.rows, p.K)
     _call("mvs_x3p_unpack", "x3p_unpack", p.ptr(), _ptr(x), p.rows, p.K, p.K, p.rows_alloc, _stream())
     return x
