@@ -17,7 +17,8 @@ __all__ = ["synth", "StageNet", "DepthNet", "CostRegNet", "CostRegNet3D", "Casca
            "schedule_inverse_range", "init_range", "schedule_range", "install", "fusion", "FPNDecoder", "FPNDecoderV2", "FPNEncoder", "vit_small", "VisionTransformer",
            "VITDecoderStage4Single", "VITDecoderStage4", "VITDecoderStage4NoAtt", "DINOMVSNet", "SceneFusion", "fuse_scan", "scene", "SceneInference",
            "metrics", "Thres_metrics", "AbsDepthError_metrics", "depth_metrics", "DeviceAverageMeter", "valid_epoch",
-           "cloud_eval", "nn_distance", "voxel_downsample", "greedy_thin", "evaluate_cloud", "icp", "evaluate_tt"]
+           "cloud_eval", "nn_distance", "voxel_downsample", "greedy_thin", "evaluate_cloud", "icp", "evaluate_tt",
+           "scene_prep", "prepare_scene"]
 
 
 def __getattr__(name):
@@ -70,6 +71,12 @@ def __getattr__(name):
     if name == "evaluate_cloud":
         from . import cloud_eval
         return cloud_eval.evaluate
+    if name == "scene_prep":
+        import importlib
+        return importlib.import_module(".scene_prep", __name__)
+    if name == "prepare_scene":
+        from . import scene_prep
+        return scene_prep.prepare_scene
     if name == "install":
         from .install import install
         return install

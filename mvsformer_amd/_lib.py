@@ -63,6 +63,9 @@ def parse_header(text: str):
 
 # name -> (restype, argtypes) and the integer macros, read from the header itself: there is no second copy to drift
 SIGNATURES, DEFINES = parse_header(open(HEADER_PATH).read())
+# the scene-preparation entries (csrc/scene_prep.hip) have a header of their own, bound the same way; mvs_hip.h's table stands as it was
+SCENE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "mvs_scene_prep.h")
+SCENE_SIGNATURES, SCENE_DEFINES = parse_header(open(SCENE_HEADER_PATH).read())
 ABI_VERSION = DEFINES["MVS_ABI_VERSION"]
 ADAM_HYPER_STRIDE = DEFINES["MVS_ADAM_HYPER_STRIDE"]         # lr, weight_decay, beta1, beta2, eps, maximize, 0, 0
 
@@ -101,7 +104,7 @@ def load() -> ctypes.CDLL:
             "%s is missing: the HIP path has not been built (run `python -c \"import __graft_entry__ as g; g.build()\"` "
             "or `make -C mvsformer_amd/csrc`).  mvsformer_amd has no CPU/PyTorch fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library drift
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,7 @@ import re
 from typing import Dict, List
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
+SCENE_PUB = "../../include/mvs_scene_prep.h"    # the header of the scene-preparation entries, as scene_prep.hip includes it
 PUB = "../../include/mvs_hip.h"          # the public header as common.h includes it: a path from csrc/, so no file name inside csrc/ can collide with it
 
 # kernel-name / launch-tag prefix -> the .hip file with the __global__ function (+ the csrc/ headers it includes, directly or through another header:
@@ -30,6 +31,7 @@ _RULES = [
      r"mvs_init_range|mvs_schedule_range|mvs_conf)", ["head.hip", "common.h", PUB]),
     (r"^(proj_|mvs_proj)", ["proj.hip", "common.h", PUB]),
     (r"^(depth_metrics|mvs_depth_metrics)", ["metrics.hip", "block_ops.h", "common.h", PUB]),
+    (r"^(scene_|mvs_scene_)", ["scene_prep.hip", "block_ops.h", "common.h", SCENE_PUB, PUB]),
     (r"^(prep_|mvs_prep)", ["sample_prep.hip", "block_ops.h", "common.h", PUB]),
     (r"^(cloud_|mvs_cloud)", ["cloud_eval.hip", "block_ops.h", "common.h", PUB]),
     (r"^(fpn_level_x3s|fpn_lvl_x3|mvs_fpn_level_x3s)", ["fpn_lvl_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
@@ -61,7 +63,8 @@ def file_digests() -> Dict[str, str]:
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".h")):
             out[f] = hashlib.sha256(open(os.path.join(CSRC, f), "rb").read()).hexdigest()[:16]
-    out[PUB] = hashlib.sha256(open(os.path.join(CSRC, PUB), "rb").read()).hexdigest()[:16]
+    for pub in (PUB, SCENE_PUB):
+        out[pub] = hashlib.sha256(open(os.path.join(CSRC, pub), "rb").read()).hexdigest()[:16]
     return out
 
 

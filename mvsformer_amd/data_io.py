@@ -83,6 +83,157 @@ def read_pair_file(filename) -> List[Tuple[int, List[int]]]:
     return out
 
 
+def write_pair_file(filename, pairs, scores=None):
+    """The inverse of ``read_pair_file``: ``pairs = [(view, [source, ...])]``, ``scores`` the matching list of score lists (None: every
+    score is written as 0; the readers ignore it) -> ``filename``, so that ``read_pair_file(write_pair_file(path, x)) == x`` for every
+    ``x`` whose views all have a source (``read_pair_file`` drops the others).  Returns ``filename``."""
+    lines = [str(len(pairs))]
+    for i, (ref, srcs) in enumerate(pairs):
+        sc = [0.0] * len(srcs) if scores is None else list(scores[i])
+        if len(sc) != len(srcs):
+            raise ValueError("write_pair_file: view %d has %d sources and %d scores" % (ref, len(srcs), len(sc)))
+        lines.append(str(int(ref)))
+        lines.append(" ".join([str(len(srcs))] + ["%d %s" % (int(s), repr(float(c))) for s, c in zip(srcs, sc)]))
+    with open(filename, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return filename
+
+
+_COLMAP_PARAMS = {"SIMPLE_PINHOLE": 3, "PINHOLE": 4}         # f cx cy / fx fy cx cy
+
+
+def _quat_to_rot(q) -> np.ndarray:
+    """Unit quaternion (w, x, y, z) -> rotation matrix, float64 (normalised first)."""
+    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _rot_to_quat(R) -> np.ndarray:
+    """Rotation matrix -> unit quaternion (w, x, y, z) with w >= 0 (the branch on the largest diagonal term)."""
+    R = np.asarray(R, np.float64)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = np.sqrt(tr + 1.0) * 2
+        q = [0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
+    else:
+        i = int(np.argmax([R[0, 0], R[1, 1], R[2, 2]]))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = np.sqrt(1.0 + R[i, i] - R[j, j] - R[k, k]) * 2
+        q = [0.0, 0.0, 0.0, 0.0]
+        q[0] = (R[k, j] - R[j, k]) / s
+        q[1 + i] = 0.25 * s
+        q[1 + j] = (R[j, i] + R[i, j]) / s
+        q[1 + k] = (R[k, i] + R[i, k]) / s
+    q = np.array(q)
+    return q / np.linalg.norm(q) * (1.0 if q[0] >= 0 else -1.0)
+
+
+def _data_lines(path) -> List[str]:
+    with open(path) as f:
+        return [ln.rstrip("\n") for ln in f if not ln.lstrip().startswith("#")]
+
+
+def read_colmap_text(model_dir) -> Dict[str, object]:
+    """A COLMAP sparse model exported as text (``cameras.txt``, ``images.txt``, ``points3D.txt``) -> the arrays of
+    ``scene_prep.prepare_scene``.  The format is RECALLED, not read from a specification here:
+
+    * ``cameras.txt``: ``CAMERA_ID MODEL WIDTH HEIGHT PARAMS...``; ``SIMPLE_PINHOLE`` (f cx cy) and ``PINHOLE`` (fx fy cx cy) only - any
+      other model raises: like the original script, this needs undistorted input;
+    * ``images.txt``: two lines per image, ``IMAGE_ID QW QX QY QZ TX TY TZ CAMERA_ID NAME`` (world to camera) and the 2-D points
+      ``X Y POINT3D_ID ...`` (``-1``: no 3-D point);
+    * ``points3D.txt``: ``POINT3D_ID X Y Z R G B ERROR`` and the track ``IMAGE_ID POINT2D_IDX ...``.  ``#`` lines are comments.
+
+    Views are indexed in ascending ``IMAGE_ID``, points in ascending ``POINT3D_ID``; the observations are the track elements of
+    ``points3D.txt`` (an image named twice in a track gives two observations; a track element whose image is not in ``images.txt``
+    raises).  -> ``{"xyz" [N,3] float32, "obs_point" [M] int64, "obs_view" [M] int32, "R" [V,3,3] float32, "t" [V,3] float32,
+    "K" [V,3,3] float32, "size" [V,2] int64 (width, height), "names", "image_ids" [V], "point_ids" [N]}``."""
+    cams = {}
+    for ln in _data_lines(os.path.join(model_dir, "cameras.txt")):
+        tok = ln.split()
+        if not tok:
+            continue
+        model = tok[1]
+        if model not in _COLMAP_PARAMS:
+            raise ValueError("read_colmap_text: camera %s has model %s; only PINHOLE and SIMPLE_PINHOLE (undistorted images) are supported"
+                             % (tok[0], model))
+        p = [float(x) for x in tok[4:]]
+        if len(p) != _COLMAP_PARAMS[model]:
+            raise ValueError("read_colmap_text: camera %s: %s takes %d parameters, got %d" % (tok[0], model, _COLMAP_PARAMS[model], len(p)))
+        fx, fy, cx, cy = (p[0], p[0], p[1], p[2]) if model == "SIMPLE_PINHOLE" else p
+        cams[int(tok[0])] = (np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float64), int(tok[2]), int(tok[3]))
+    images = {}
+    lines = _data_lines(os.path.join(model_dir, "images.txt"))
+    while lines and not lines[-1].strip():
+        lines.pop()
+    if len(lines) % 2:
+        lines.append("")                                          # the last image has an empty line of 2-D points
+    for head in lines[0::2]:
+        tok = head.split()
+        if len(tok) < 10:
+            raise ValueError("read_colmap_text: images.txt: expected 'IMAGE_ID QW QX QY QZ TX TY TZ CAMERA_ID NAME', got %r" % head)
+        cam_id = int(tok[8])
+        if cam_id not in cams:
+            raise ValueError("read_colmap_text: image %s uses camera %d, which cameras.txt does not hold" % (tok[0], cam_id))
+        images[int(tok[0])] = ([float(x) for x in tok[1:5]], [float(x) for x in tok[5:8]], cam_id, " ".join(tok[9:]))
+    if not images:
+        raise ValueError("read_colmap_text: %s holds no image" % model_dir)
+    image_ids = sorted(images)
+    index = {iid: v for v, iid in enumerate(image_ids)}
+    pts = {}
+    for ln in _data_lines(os.path.join(model_dir, "points3D.txt")):
+        tok = ln.split()
+        if tok:
+            pts[int(tok[0])] = ([float(x) for x in tok[1:4]], [int(x) for x in tok[8::2]])
+    point_ids = sorted(pts)
+    obs_point, obs_view = [], []
+    for p, pid in enumerate(point_ids):
+        for iid in pts[pid][1]:
+            if iid not in index:
+                raise ValueError("read_colmap_text: point %d is tracked in image %d, which images.txt does not hold" % (pid, iid))
+            obs_point.append(p)
+            obs_view.append(index[iid])
+    return {"xyz": np.array([pts[pid][0] for pid in point_ids], np.float64).reshape(-1, 3).astype(np.float32),
+            "obs_point": np.array(obs_point, np.int64), "obs_view": np.array(obs_view, np.int32),
+            "R": np.stack([_quat_to_rot(images[i][0]) for i in image_ids]).astype(np.float32),
+            "t": np.array([images[i][1] for i in image_ids], np.float64).astype(np.float32),
+            "K": np.stack([cams[images[i][2]][0] for i in image_ids]).astype(np.float32),
+            "size": np.array([cams[images[i][2]][1:] for i in image_ids], np.int64),
+            "names": [images[i][3] for i in image_ids], "image_ids": np.array(image_ids, np.int64), "point_ids": np.array(point_ids, np.int64)}
+
+
+def write_colmap_text(model_dir, xyz, obs_point, obs_view, R, t, K, size, names=None, model: str = "PINHOLE") -> None:
+    """Writes the three text files ``read_colmap_text`` reads, one camera per image, ``IMAGE_ID`` = view + 1, ``POINT3D_ID`` = point + 1,
+    numbers with ``repr`` (they read back exactly).  It exists so that tests can round-trip a synthetic model: images carry no 2-D points
+    and tracks carry ``POINT2D_IDX`` 0.  ``model``: ``PINHOLE``, ``SIMPLE_PINHOLE`` (fx is written as f) or any other name, written with
+    the PINHOLE parameters (for the test that such a model is refused)."""
+    os.makedirs(model_dir, exist_ok=True)
+    V = len(R)
+    names = ["%08d.jpg" % v for v in range(V)] if names is None else list(names)
+    num = lambda x: repr(float(x))  # noqa: E731
+    with open(os.path.join(model_dir, "cameras.txt"), "w") as f:
+        f.write("# Camera list with one line of data per camera:\n#   CAMERA_ID, MODEL, WIDTH, HEIGHT, PARAMS[]\n")
+        for v in range(V):
+            k = np.asarray(K[v], np.float64)
+            params = [k[0, 0], k[0, 2], k[1, 2]] if model == "SIMPLE_PINHOLE" else [k[0, 0], k[1, 1], k[0, 2], k[1, 2]]
+            f.write("%d %s %d %d %s\n" % (v + 1, model, int(size[v][0]), int(size[v][1]), " ".join(num(x) for x in params)))
+    with open(os.path.join(model_dir, "images.txt"), "w") as f:
+        f.write("# Image list with two lines of data per image:\n#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME\n"
+                "#   POINTS2D[] as (X, Y, POINT3D_ID)\n")
+        for v in range(V):
+            q = _rot_to_quat(R[v])
+            f.write("%d %s %s %d %s\n\n" % (v + 1, " ".join(num(x) for x in q), " ".join(num(x) for x in t[v]), v + 1, names[v]))
+    tracks: Dict[int, List[int]] = {}
+    for p, v in zip(np.asarray(obs_point).tolist(), np.asarray(obs_view).tolist()):
+        tracks.setdefault(p, []).append(v)
+    with open(os.path.join(model_dir, "points3D.txt"), "w") as f:
+        f.write("# 3D point list with one line of data per point:\n#   POINT3D_ID, X, Y, Z, R, G, B, ERROR, TRACK[] as (IMAGE_ID, POINT2D_IDX)\n")
+        for p in range(len(xyz)):
+            track = " ".join("%d 0" % (v + 1) for v in tracks.get(p, []))
+            f.write(("%d %s 128 128 128 0.0 %s" % (p + 1, " ".join(num(x) for x in xyz[p]), track)).rstrip() + "\n")
+
+
 def _cam_2x4x4(path) -> np.ndarray:
     K, E = read_camera_parameters(path)
     cam = np.zeros((2, 4, 4), dtype=np.float32)

@@ -2781,3 +2781,78 @@ def prep_eval_resize(src, out_hw, pad_rows=0, want="f32"):
     _call("mvs_prep_eval_resize", ("prep_eval_resize", "bytes", float(V * H * W * 3) * 5), _ptr(src), V, H0, W0, H, W, int(pad_rows), _ptr(u8),
           _ptr(f32), _stream())
     return (u8, f32) if want == "both" else (u8 if want == "u8" else f32)
+
+
+# ------------------------------------------------------------------------------------- scene preparation (csrc/scene_prep.hip)
+def _chk_scene_prep(xyz, R, t):
+    _chk_cloud(xyz, "xyz"), _chk(R, "R"), _chk(t, "t")
+    n, v = xyz.shape[0], R.shape[0]
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or tuple(t.shape) != (v, 3) or v < 1 or n < 1:
+        raise _lib.MvsHipError("scene_prep: xyz %s R %s t %s (N >= 1 points, V >= 1 views)" % (tuple(xyz.shape), tuple(R.shape), tuple(t.shape)))
+    return n, v
+
+
+def _chk_prep_bits(bits, n: int, v: int):
+    _chk(bits, "bits", torch.int64)
+    if tuple(bits.shape) != (v, (n + 63) // 64):
+        raise _lib.MvsHipError("scene_prep: bits %s for V=%d N=%d must be [%d,%d]" % (tuple(bits.shape), v, n, v, (n + 63) // 64))
+
+
+def scene_visibility(obs_point, obs_view, xyz, n_views: int, wait: bool = True):
+    """``obs_point [M]`` int64, ``obs_view [M]`` int32, ``xyz [N,3]`` -> ``(bits [V, ceil(N/64)]`` int64 holding the uint64 words, ``count [V]``
+    int32, ``info [2]`` int64 on the device = (bad observations, non-finite points)``)``.  ``wait``: one host synchronisation (16 bytes) that
+    raises on a bad observation; without it nothing waits and the caller reads ``info``."""
+    _chk_cloud(xyz, "xyz"), _chk(obs_point, "obs_point", torch.int64), _chk(obs_view, "obs_view", torch.int32)
+    m, n, v = obs_point.shape[0], xyz.shape[0], int(n_views)
+    if obs_point.dim() != 1 or tuple(obs_view.shape) != (m,) or n < 1 or v < 1:
+        raise _lib.MvsHipError("scene_visibility: obs_point %s obs_view %s for N=%d V=%d" % (tuple(obs_point.shape), tuple(obs_view.shape), n, v))
+    bits = _new(xyz, v, (n + 63) // 64, dtype=torch.int64)
+    count = _new(xyz, v, dtype=torch.int32)
+    info = _new(xyz, 2, dtype=torch.int64)
+    host = (ctypes.c_int64 * 2)()
+    _call("mvs_scene_visibility", ("scene_visibility", "bytes", 24.0 * m + 12.0 * n + 8.0 * bits.numel()), _ptr(obs_point) if m else None,
+          _ptr(obs_view) if m else None, m, _ptr(xyz), n, v, _ptr(bits), _ptr(count), _ptr(info), ctypes.addressof(host) if wait else None, _stream())
+    return bits, count, info
+
+
+def scene_pair_scores(bits, xyz, R, t, theta0: float = 5.0, sigma1: float = 1.0, sigma2: float = 10.0) -> torch.Tensor:
+    """-> ``S [V,V]`` fp64, symmetric, zero diagonal: the sum of ``g(theta)`` over the points two views share (include/mvs_scene_prep.h has the
+    rule).  No atomics, no host synchronisation: two calls give the same bits."""
+    n, v = _chk_scene_prep(xyz, R, t)
+    _chk_prep_bits(bits, n, v)
+    centers = _new(xyz, v, 3, dtype=torch.float64)
+    S = _new(xyz, v, v, dtype=torch.float64)
+    _call("mvs_scene_pair_scores", "scene_pair_scores", _ptr(bits), _ptr(xyz), n, _ptr(R), _ptr(t), v, float(theta0), float(sigma1), float(sigma2),
+          _ptr(centers), _ptr(S), _stream())
+    return S
+
+
+def scene_rank_sources(S, k: int):
+    """``S [V,V]`` fp64 -> ``(src [V,k] int32, score [V,k] fp64)``: per view the other views by descending score, ties to the lower index;
+    unfilled slots (``k > V-1``) are ``-1`` / ``0``."""
+    _chk(S, "S", torch.float64)
+    if S.dim() != 2 or S.shape[0] != S.shape[1] or S.shape[0] < 1 or int(k) < 1:
+        raise _lib.MvsHipError("scene_rank_sources: S %s must be [V,V] and k=%d >= 1" % (tuple(S.shape), int(k)))
+    v, k = S.shape[0], int(k)
+    src = _new(S, v, k, dtype=torch.int32)
+    score = _new(S, v, k, dtype=torch.float64)
+    _call("mvs_scene_rank_sources", "scene_rank_sources", _ptr(S), v, k, _ptr(src), _ptr(score), _stream())
+    return src, score
+
+
+def scene_depth_ranges(bits, count, xyz, R, t, lo: float = 0.01, hi: float = 0.99, capacity: Optional[int] = None):
+    """-> ``(range [V,2] fp32, n [V] int32)``: the order statistics ``int(n * lo)`` and ``int(n * hi)`` of each view's camera-space depths.
+    ``capacity``: room for the compacted depths, at least the sum of ``count`` (the number of observations is enough); None reads the sum
+    from the device (one host synchronisation).  A view that does not fit reports ``n = -1``."""
+    n, v = _chk_scene_prep(xyz, R, t)
+    _chk_prep_bits(bits, n, v), _chk(count, "count", torch.int32)
+    if tuple(count.shape) != (v,):
+        raise _lib.MvsHipError("scene_depth_ranges: count %s must be [%d]" % (tuple(count.shape), v))
+    cap = int(count.sum().item()) if capacity is None else int(capacity)
+    offsets = _new(xyz, v + 1, dtype=torch.int64)
+    depths = _new(xyz, max(cap, 1))
+    rng = _new(xyz, v, 2)
+    nout = _new(xyz, v, dtype=torch.int32)
+    _call("mvs_scene_depth_ranges", ("scene_depth_ranges", "bytes", 8.0 * bits.numel() + 20.0 * cap), _ptr(bits), _ptr(count), _ptr(xyz), n, _ptr(R),
+          _ptr(t), v, float(lo), float(hi), _ptr(offsets), _ptr(depths), cap, _ptr(rng), _ptr(nout), _stream())
+    return rng, nout
