@@ -23,8 +23,8 @@ _RULES = [
     (r"^(x3_tail|tail_x3)", ["tail_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
     (r"^x3_small", ["conv3d_x3_small.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
     (r"^(x3_conv|x3_deconv|x3_pack|x3_deconv_pack)", ["conv3d_x3.hip", "conv_common.h", "common.h", "split3.h", "prims.h", PUB]),
-    (r"^conv3d_kernel", ["conv3d_fwd.hip", "conv_common.h", "common.h", "prims.h", PUB]),
-    (r"^(deconv3d_kernel|prob3)", ["conv3d.hip", "conv_common.h", "common.h", "prims.h", PUB]),
+    (r"^conv3d_kernel", ["conv3d_fwd.hip", "conv3d_plan.h", "conv_common.h", "common.h", "prims.h", PUB]),
+    (r"^(deconv3d_kernel|prob3)", ["conv3d.hip", "conv3d_plan.h", "conv_common.h", "common.h", "prims.h", PUB]),
     (r"^pack_deconv_s1", ["deconv3d_s1.hip", "conv_common.h", "common.h", "prims.h", PUB]),
     (r"^(reg_head|mixup_train|mvs_reg_head|mvs_mixup_train)", ["head_train.hip", "common.h", PUB]),
     (r"^(head_|prob1_kernel|mvs_prob1_fwd|init_inverse|schedule_inverse|init_range|schedule_range|conf_accumulate|mvs_head|mvs_init_inverse|mvs_schedule_inverse|"

@@ -392,8 +392,6 @@ __device__ __forceinline__ bf16x8 frag_tr(const unsigned short* p0, const unsign
     return __builtin_bit_cast(bf16x8, (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
 }
 
-constexpr int WG_PW = 16;                                   // patch columns
-
 template <int TA, int TB>                                   // channel tiles per block
 __device__ __forceinline__ void wgrad_body(const WgradArgs& a, const int bx, const int by) {
     constexpr int TT = TA * TB;
@@ -966,51 +964,6 @@ extern "C" int mvs_bf16_conv3d_stats(const void* x, const void* wpacked, void* y
     o.stats_part = reinterpret_cast<float*>(workspace), o.groups = groups, o.sums = sums;
     return bf16_conv3d_impl(x, wpacked, y, B, Cin, Cout, Di, Hi, Wi, gather, sd, shw, 27, conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, 27, 1), o, stream);
 }
-
-namespace {
-struct WgradPlan { int PH, npr, npc, npatch, dseg, nseg, TA, TB, gy, blocks; size_t lds; };
-constexpr size_t WG_RING_B = 56 * 1024;                      // budget of the 4-plane Bt ring (bytes)
-int wgrad_nseg(int columns, int Dp, int target) {            // depth segments per column: enough work items, >= 2 depths each
-    int nseg = (target + columns - 1) / columns;
-    const int cap = Dp / 2 > 1 ? Dp / 2 : 1;
-    if (nseg > cap) nseg = cap;
-    return nseg < 1 ? 1 : nseg;
-}
-// grouped: a job of a GROUP launch - the jobs fill the chip together, so each takes fewer blocks (= slabs the reduce reads back) than a
-// launch of its own needs: 256 for the single-tile instance, 128 for the others (measured on config 3's step, kernel time per step of
-// the instances <1,1> / <2,2> / <1,4> / <2,1> at 512: 0.46 / 0.30 / 0.16 / 0.13 ms, at 256: 0.41 / 0.23 / 0.10 / 0.10, at 128: 0.42 / 0.15 /
-// 0.11 / <0.09, at 64: 0.71 / 0.13 / 0.15 / 0.11; block counts proportional to the jobs' patch x depth steps were slower than either).
-WgradPlan wgrad_plan(int nbatch, int CA, int CB, int Dp, int Hp, int Wp, int shw, bool grouped = false) {
-    WgradPlan p;
-    const int nA = (CA + 15) / 16, nB = (CB + 15) / 16;
-    p.TB = nB;                                               // one block sees all of CB (nB <= 4)
-    p.TA = nA < 4 / nB ? nA : 4 / nB;
-    if (p.TA > 2) p.TA = 2;                                  // the A tile is staged as two 16-byte pieces per thread: 32 channels at most
-    if (p.TA < 1) p.TA = 1;                                  // (64 x <=16 channels - no layer of the networks - runs as two channel groups)
-    p.gy = (nA + p.TA - 1) / p.TA;
-    const int b_row = CB < p.TB * 16 ? CB : p.TB * 16, a_row = CA < p.TA * 16 ? CA : p.TA * 16;
-    p.PH = 8;
-    while (p.PH > 2 && (size_t)4 * (p.PH * shw + 2) * (WG_PW * shw + 2) * b_row * 2 > WG_RING_B) p.PH >>= 1;
-    p.npr = (Hp + p.PH - 1) / p.PH;
-    p.npc = (Wp + WG_PW - 1) / WG_PW;
-    // two resident blocks per CU over all channel groups (three for the single-tile instance was measured: no faster, and every block
-    // writes a slab the reduce kernel reads back)
-    static const int gblocks = mvs::env_int("MVS_WGRAD_GROUP_BLOCKS", 0);       // diagnostics
-    const int target = (grouped ? (gblocks > 0 ? gblocks : p.TA * p.TB == 1 ? 256 : 128) : 512) / p.gy;
-    p.nseg = wgrad_nseg(nbatch * p.npr * p.npc, Dp, target);
-    p.dseg = (Dp + p.nseg - 1) / p.nseg;
-    p.nseg = (Dp + p.dseg - 1) / p.dseg;
-    p.npatch = nbatch * p.npr * p.npc * p.nseg;
-    // the slab (= block) count must not depend on the stride (the workspace is sized without it): the count at PH = 8
-    const int col8 = nbatch * ((Hp + 7) / 8) * p.npc;
-    const int seg8 = wgrad_nseg(col8, Dp, target), d8 = (Dp + seg8 - 1) / seg8;
-    const int least = col8 * ((Dp + d8 - 1) / d8);
-    p.blocks = target < least ? target : least;
-    if (p.blocks < 1) p.blocks = 1;
-    p.lds = ((size_t)p.PH * WG_PW * a_row + 64 + (size_t)4 * (p.PH * shw + 2) * (WG_PW * shw + 2) * b_row + 64) * 2;
-    return p;
-}
-}  // namespace
 
 extern "C" int64_t mvs_bf16_conv3d_wgrad_workspace_bytes(int nbatch, int CA, int CB, int Dp, int Hp, int Wp) {
     if (!chan_ok(CA) || !chan_ok(CB) || nbatch < 1 || Dp < 1 || Hp < 1 || Wp < 1) return -1;

@@ -15,14 +15,13 @@
 // wavefront always owns an even+odd pair in each strided dimension so that all wavefronts do equal work.
 //
 // Algorithmic FLOPs per layer: 2*27*Cin*Cout per output voxel (conv) / per input voxel (deconv).
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 namespace {
 using namespace mvsconv;
 using mvs_rsrc_t = rsrc_t;
 __device__ __forceinline__ mvs_rsrc_t mvs_make_rsrc(const float* b, unsigned n) { return make_rsrc(b, n); }
 __device__ __forceinline__ float mvs_buf_load(mvs_rsrc_t r, unsigned v, unsigned s) { return buf_load(r, v, s); }
-constexpr int CC_DECONV = 8;                                                  // input channels per LDS chunk
 
 // --------------------------------------------------------------------------------------------------------
 // weight packing: one zero-padded image per layer, [cin/4 slabs][tap 27][c 4][NP].  A kernel that stages CC
@@ -357,21 +356,14 @@ __global__ __launch_bounds__(256) void prob3_blocked_kernel(const float* __restr
 }
 
 template <int NT, int SD>
-size_t deconv_lds_bytes() {
-    constexpr int ID = (SD == 1) ? 4 : 2, IW = 32 + 1;
-    return (size_t)(CC_DECONV * pad_cs(ID * 3 * IW, 1) + (CC_DECONV / 4) * 27 * 4 * np_of(NT)) * sizeof(float);
-}
-
-template <int NT, int SD>
-int launch_deconv(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y, int B,
-                  int Cin, int Cout, int Di, int Hi, int Wi, int relu, hipStream_t s) {
-    const size_t lds = deconv_lds_bytes<NT, SD>();
-    if (lds > 48 * 1024) {
-        const int rc = mvs::ensure_dynamic_lds(reinterpret_cast<const void*>(deconv3d_kernel<NT, SD>), (int)lds, "mvs_deconv3d_fwd");
+int launch_deconv(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y, int Cin, int Cout,
+                  int Di, int Hi, int Wi, int relu, const Deconv3dPlan& p, hipStream_t s) {
+    if (p.lds > 48 * 1024) {
+        const int rc = mvs::ensure_dynamic_lds(reinterpret_cast<const void*>(deconv3d_kernel<NT, SD>), (int)p.lds, "mvs_deconv3d_fwd");
         if (rc != MVS_OK) return rc;
     }
-    dim3 grid(mvs::ceil_div(Wi, 32), mvs::ceil_div(Hi, 2), B * ((SD == 1) ? mvs::ceil_div(Di, 2) : Di));
-    hipLaunchKernelGGL((deconv3d_kernel<NT, SD>), grid, dim3(256), lds, s, x, wp, scale, shift, res, y, Cin, Cout, Di, Hi, Wi, relu);
+    hipLaunchKernelGGL((deconv3d_kernel<NT, SD>), dim3(p.gx, p.gy, p.gz), dim3(256), p.lds, s, x, wp, scale, shift, res, y, Cin, Cout, Di, Hi,
+                       Wi, relu);
     return mvs::finish_launch("mvs_deconv3d_fwd");
 }
 
@@ -405,12 +397,15 @@ extern "C" int mvs_deconv3d_fwd(const float* x, const float* wpacked, const floa
     MVS_REQUIRE(sd == 1 || sd == 2, "mvs_deconv3d_fwd: depth stride %d not built", sd);
     MVS_REQUIRE((int64_t)B * Di <= 65535, "mvs_deconv3d_fwd: grid.z limit");
     hipStream_t s = MVS_STREAM(stream);
-    if (sd == 1 && deconv_s1_supported(Cout))
+    const Deconv3dPlan p = deconv3d_plan(B, Cin, Cout, Di, Hi, Wi, sd);
+    if (p.s1) {
+        MVS_REQUIRE(deconv_s1_supported(Cout), "mvs_deconv3d_fwd: no split-form kernel for Cout=%d", Cout);
         return deconv_s1_launch(x, wpacked, scale, shift, residual, y, B, Cin, Cout, Di, Hi, Wi, relu, s);
-    const int nt = nt_of(Cout);
-#define MVS_DECONV(NTV)                                                                                                     \
-    if (sd == 1) return launch_deconv<NTV, 1>(x, wpacked, scale, shift, residual, y, B, Cin, Cout, Di, Hi, Wi, relu, s);   \
-    return launch_deconv<NTV, 2>(x, wpacked, scale, shift, residual, y, B, Cin, Cout, Di, Hi, Wi, relu, s)
+    }
+    const int nt = p.NT;
+#define MVS_DECONV(NTV)                                                                                                      \
+    if (sd == 1) return launch_deconv<NTV, 1>(x, wpacked, scale, shift, residual, y, Cin, Cout, Di, Hi, Wi, relu, p, s);   \
+    return launch_deconv<NTV, 2>(x, wpacked, scale, shift, residual, y, Cin, Cout, Di, Hi, Wi, relu, p, s)
     if (nt == 1) { MVS_DECONV(1); }
     if (nt == 2) { MVS_DECONV(2); }
     MVS_DECONV(4);

@@ -17,25 +17,10 @@
 // LDS channel strides are padded to == 16 (mod 32) words (unit-stride fragments) or odd (stride-2 fragments), packed
 // weight rows to == 16 (mod 32), so the two k-halves of every 32-lane ds_read_b32 group hit disjoint banks
 // (SQ_LDS_BANK_CONFLICT = 0 in profiles/r01_pmc_reg_stage4_v2.txt).
-#include <stdlib.h>
-#include <string.h>
-
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 namespace {
 using namespace mvsconv;
-
-// input channels per chunk: 8 if tile + weights fit in ~96 KiB of LDS, else 4
-constexpr int tile_cs(int SD, int SHW, int TD, int TH, int MT) {
-    return pad_cs(((TD - 1) * SD + 3) * ((TH - 1) * SHW + 3) * ((16 * MT - 1) * SHW + 3), SHW);
-}
-constexpr int pick_cc(int NP, int SD, int SHW, int TD, int TH, int MT) {
-    return (8 * tile_cs(SD, SHW, TD, TH, MT) + 2 * 27 * 4 * NP) * 4 <= 96 * 1024 ? 8 : 4;
-}
-constexpr size_t lds_bytes(int NP, int SD, int SHW, int TD, int TH, int MT) {
-    const int cc = pick_cc(NP, SD, SHW, TD, TH, MT);
-    return (size_t)(cc * tile_cs(SD, SHW, TD, TH, MT) + (cc / 4) * 27 * 4 * NP) * 4;
-}
 
 // NT = 16-channel N tiles computed by one block (all of Cout, or 1 when the output channels are split over blocks
 // for small volumes), NP = packed weight row length (depends on the layer's full Cout), MT = 16-voxel M tiles per row.
@@ -198,72 +183,35 @@ struct ConvArgs {
     hipStream_t s;
 };
 
-template <int NT, int NP, int SD, int SHW, int TD, int TH, int MT>
-int launch(const ConvArgs& a) {
-    constexpr size_t lds = lds_bytes(NP, SD, SHW, TD, TH, MT);
-    static_assert(lds <= 160 * 1024, "tile does not fit in LDS");
-    if (lds > 48 * 1024) {
-        const int rc = mvs::ensure_dynamic_lds(reinterpret_cast<const void*>(conv3d_kernel<NT, NP, SD, SHW, TD, TH, MT>), (int)lds, "mvs_conv3d_fwd");
+// One template instance per (NT, NP, stride, form); grid and LDS bytes are the plan's.
+template <int NT, int NP, int SD, int SHW, ConvForm F>
+int launch(const ConvArgs& a, const Conv3dPlan& p) {
+    constexpr ConvTile t = conv_tile(F);
+    static_assert(lds_bytes(NP, SD, SHW, t.TD, t.TH, t.MT) <= 160 * 1024, "tile does not fit in LDS");
+    const auto kernel = conv3d_kernel<NT, NP, SD, SHW, t.TD, t.TH, t.MT>;
+    if (p.lds > 48 * 1024) {
+        const int rc = mvs::ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)p.lds, "mvs_conv3d_fwd");
         if (rc != MVS_OK) return rc;
     }
-    const int nsplit = mvs::ceil_div(nt_of(a.Cout), NT);
-    dim3 grid(mvs::ceil_div(a.Wo, 16 * MT) * nsplit, mvs::ceil_div(a.Ho, TH), a.B * mvs::ceil_div(a.Do, TD));
-    hipLaunchKernelGGL((conv3d_kernel<NT, NP, SD, SHW, TD, TH, MT>), grid, dim3(256), lds, a.s, a.x, a.wp, a.scale, a.shift, a.res,
-                       a.y, a.Cin, a.Cout, a.Di, a.Hi, a.Wi, a.Do, a.Ho, a.Wo, a.relu);
+    hipLaunchKernelGGL(kernel, dim3(p.gx, p.gy, p.gz), dim3(256), p.lds, a.s, a.x, a.wp, a.scale, a.shift, a.res, a.y, a.Cin, a.Cout, a.Di,
+                       a.Hi, a.Wi, a.Do, a.Ho, a.Wo, a.relu);
     return mvs::finish_launch("mvs_conv3d_fwd");
 }
 
-// Tile choice (measured with tools/bench_conv.py on config-2 shapes, profiles/r01_conv_layers_*.txt):
-//   * NTF == 1 (Cout 8/16) on large volumes: 4x2-row tiles, one block per CU — the weight fragment is reused by 8 MFMAs
-//     and the halo re-read drops from 4.1x to 2.3x (2x faster for the stride-(1,2,2) conv1);
-//   * NTF >= 2: 2x2-row tiles at 2 blocks per CU are as fast or faster;
-//   * small volumes (deep U-Net levels of the coarse stages, < 256 blocks): 32-voxel tiles and one 16-channel N tile per
-//     block, so a 64->64 layer on 4x18x24 voxels becomes 72 short blocks instead of 18 long ones.
+// The template instance of the form conv3d_plan (conv3d_plan.h) chose.  The 4x2-row form is built for stride-1 depth only; with one
+// channel tile the split 64-voxel form is the instance of the unsplit one.
 template <int NTF, int SD, int SHW>
-int dispatch_tile(const ConvArgs& a) {
+int dispatch_tile(const ConvArgs& a, const Conv3dPlan& p) {
     constexpr int NP = np_of(NTF);
-    auto blocks = [&](int td, int th, int tw) {
-        return (long)mvs::ceil_div(a.Wo, tw) * mvs::ceil_div(a.Ho, th) * mvs::ceil_div(a.Do, td) * a.B;
-    };
-    static const char* force = mvs::env_str("MVS_CONV_TILE");     // tuning knob for tools/bench_conv.py: 42 | 22 | 22s
-    if (force) {
-        if constexpr (SD == 1) { if (!strcmp(force, "42") && a.Do >= 3) return launch<NTF, NP, SD, SHW, 4, 2, 4>(a); }
-        if (!strcmp(force, "22")) return launch<NTF, NP, SD, SHW, 2, 2, 4>(a);
-        if (!strcmp(force, "22s")) return launch<1, NP, SD, SHW, 2, 2, 2>(a);
+    switch (p.form) {
+        case ConvForm::F22S: return launch<1, NP, SD, SHW, ConvForm::F22S>(a, p);
+        case ConvForm::F22S64: return launch<1, NP, SD, SHW, ConvForm::F22S64>(a, p);
+        case ConvForm::F42:
+            if constexpr (SD == 1) return launch<NTF, NP, SD, SHW, ConvForm::F42>(a, p);
+            break;
+        case ConvForm::F22: break;
     }
-    // cost model: the matrix pipe of a CU is the shared resource, so time ~ (blocks per CU, rounded up) x (MFMA cycles
-    // per block + per-chunk staging overhead, which is exposed when only one block fits on the CU)
-    auto model = [&](int td, int th, int mt, int ntb, size_t lds, int cc) {
-        const double chunks = mvs::ceil_div(a.Cin, cc);
-        const double mfma = 27.0 * (cc / 4) * (td * th / 4) * mt * ntb * 32.0;
-        const double ovh = (lds > 80 * 1024) ? 3500.0 : 1200.0;
-        const long nb = blocks(td, th, 16 * mt) * mvs::ceil_div(NTF, ntb);
-        return (double)((nb + 255) / 256) * chunks * (mfma + ovh);
-    };
-    double best = 1e300;
-    int pick = 1;
-    {   // 1: 2x2 rows, 64 voxels, all channels
-        const double c = model(2, 2, 4, NTF, lds_bytes(NP, SD, SHW, 2, 2, 4), pick_cc(NP, SD, SHW, 2, 2, 4));
-        if (c < best) { best = c; pick = 1; }
-    }
-    if constexpr (NTF == 1 && SD == 1) {
-        if (a.Do >= 3) {   // 2: 4x2 rows
-            const double c = model(4, 2, 4, NTF, lds_bytes(NP, SD, SHW, 4, 2, 4), pick_cc(NP, SD, SHW, 4, 2, 4)) * (SHW == 2 ? 0.6 : 0.95);
-            if (c < best) { best = c; pick = 2; }
-        }
-    }
-    if constexpr (NTF > 1) {   // 3: channels split over blocks, 64 voxels
-        const double c = model(2, 2, 4, 1, lds_bytes(NP, SD, SHW, 2, 2, 4), pick_cc(NP, SD, SHW, 2, 2, 4)) * 1.1;
-        if (c < best) { best = c; pick = 3; }
-    }
-    {   // 4: channels split, 32 voxels
-        const double c = model(2, 2, 2, 1, lds_bytes(NP, SD, SHW, 2, 2, 2), pick_cc(NP, SD, SHW, 2, 2, 2)) * 1.15;
-        if (c < best || a.Wo <= 32) { best = c; pick = 4; }
-    }
-    if (pick == 4) return launch<1, NP, SD, SHW, 2, 2, 2>(a);
-    if constexpr (NTF > 1) { if (pick == 3) return launch<1, NP, SD, SHW, 2, 2, 4>(a); }
-    if constexpr (NTF == 1 && SD == 1) { if (pick == 2) return launch<NTF, NP, SD, SHW, 4, 2, 4>(a); }
-    return launch<NTF, NP, SD, SHW, 2, 2, 4>(a);
+    return launch<NTF, NP, SD, SHW, ConvForm::F22>(a, p);
 }
 
 }  // namespace
@@ -275,14 +223,15 @@ extern "C" int mvs_conv3d_fwd(const float* x, const float* wpacked, const float*
     if (int rc = check_conv_args("mvs_conv3d_fwd", B, Cin, Cout, Di, Hi, Wi)) return rc;
     MVS_REQUIRE((sd == 1 && shw == 1) || (sd == 2 && shw == 2) || (sd == 1 && shw == 2),
                 "mvs_conv3d_fwd: stride (%d,%d,%d) not built", sd, shw, shw);
-    ConvArgs a{x, wpacked, scale, shift, residual, y, B, Cin, Cout, Di, Hi, Wi, (Di - 1) / sd + 1, (Hi - 1) / shw + 1,
-               (Wi - 1) / shw + 1, relu, MVS_STREAM(stream)};
+    static const char* force = mvs::env_str("MVS_CONV_TILE");
+    const Conv3dPlan p = conv3d_plan(B, Cin, Cout, Di, Hi, Wi, sd, shw, force);
+    ConvArgs a{x, wpacked, scale, shift, residual, y, B, Cin, Cout, Di, Hi, Wi, p.Do, p.Ho, p.Wo, relu, MVS_STREAM(stream)};
     MVS_REQUIRE((int64_t)B * mvs::ceil_div(a.Do, 2) <= 65535, "mvs_conv3d_fwd: grid.z limit");
     const int nt = nt_of(Cout);
-#define MVS_CONV(NTV)                                              \
-    if (sd == 1 && shw == 1) return dispatch_tile<NTV, 1, 1>(a);   \
-    if (sd == 2) return dispatch_tile<NTV, 2, 2>(a);               \
-    return dispatch_tile<NTV, 1, 2>(a)
+#define MVS_CONV(NTV)                                                 \
+    if (sd == 1 && shw == 1) return dispatch_tile<NTV, 1, 1>(a, p);   \
+    if (sd == 2) return dispatch_tile<NTV, 2, 2>(a, p);               \
+    return dispatch_tile<NTV, 1, 2>(a, p)
     if (nt == 1) { MVS_CONV(1); }
     if (nt == 2) { MVS_CONV(2); }
     MVS_CONV(4);

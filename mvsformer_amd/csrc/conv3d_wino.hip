@@ -22,7 +22,7 @@
 // accumulated magnitude (tests/test_hip_parity.py::test_wino_conv_matches_direct).
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv3d_plan.h"
 #include "prims.h"
 
 namespace {
@@ -38,7 +38,6 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
     return pk_fma(b, f32x2{m1, m1}, a);
 }
 
-constexpr int WTY = 4;                       // tile rows per block = wavefronts
 constexpr int RROWS = 2 * WTY + 2;           // staged input rows (halo 1 each side)
 // LDS row = the 34 staged columns c = x - (x0-1) split by parity: E[j] = column 2j (j = 0..16), O[j] = column 2j+1.
 // Tile i needs columns 2i..2i+3 = E[i], O[i], E[i+1], O[i+1]: unit stride over the 16 tile lanes, and with a channel
@@ -255,20 +254,15 @@ __global__ __launch_bounds__(256) void wino_conv3d_kernel(const float* __restric
 }
 
 template <int NT>
-int launch_wino(const float* x, const float* U, const float* scale, const float* shift, const float* res, float* y, int B, int Cin,
-                int Cout, int D, int H, int W, int relu, hipStream_t s) {
-    const int ngroups = Cout / (16 * NT);
-    dim3 grid(D * ngroups, mvs::ceil_div(W, 32), mvs::ceil_div(H, 2 * WTY) * B);
-    hipLaunchKernelGGL(wino_conv3d_kernel<NT>, grid, dim3(256), 0, s, x, U, scale, shift, res, y, Cin, Cout, D, H, W, relu);
+int launch_wino(const float* x, const float* U, const float* scale, const float* shift, const float* res, float* y, int Cin, int Cout, int D,
+                int H, int W, int relu, const WinoPlan& p, hipStream_t s) {
+    hipLaunchKernelGGL(wino_conv3d_kernel<NT>, dim3(p.gx, p.gy, p.gz), dim3(256), 0, s, x, U, scale, shift, res, y, Cin, Cout, D, H, W, relu);
     return mvs::finish_launch("mvs_conv3d_wino_fwd");
 }
 
 }  // namespace
 
-extern "C" int mvs_conv3d_wino_supported(int Cin, int Cout, int D, int H, int W) {
-    return Cin >= 4 && Cin % 4 == 0 && Cout >= 16 && Cout % 16 == 0 && Cout <= 64 && D >= 1 && H >= 1 && W >= 4 && W % 4 == 0 &&
-           (int64_t)4 * D * H * W * 4 < ((int64_t)1 << 31);
-}
+extern "C" int mvs_conv3d_wino_supported(int Cin, int Cout, int D, int H, int W) { return wino_supported(Cin, Cout, D, H, W); }
 
 extern "C" int64_t mvs_conv3d_wino_packed_floats(int Cin, int Cout) {
     if (Cin < 4 || Cin % 4 || Cout < 16 || Cout % 16 || Cout > 64) return 0;
@@ -287,13 +281,12 @@ extern "C" int mvs_conv3d_wino_pack_weights(const float* w, int Cin, int Cout, f
 extern "C" int mvs_conv3d_wino_fwd(const float* x, const float* wpacked, const float* scale, const float* shift, const float* residual,
                                    float* y, int B, int Cin, int Cout, int D, int H, int W, int relu, mvs_stream_t stream) {
     MVS_REQUIRE(x && wpacked && y, "mvs_conv3d_wino_fwd: null pointer");
-    MVS_REQUIRE(B >= 1 && mvs_conv3d_wino_supported(Cin, Cout, D, H, W),
+    const WinoPlan p = wino_plan(B, Cin, Cout, D, H, W, mvs::env_int("MVS_WINO_NT", 0));
+    MVS_REQUIRE(B >= 1 && p.supported,
                 "mvs_conv3d_wino_fwd: unsupported shape B=%d Cin=%d Cout=%d D=%d H=%d W=%d (Cin%%4, Cout%%16, Cout<=64, W%%4)", B, Cin, Cout, D,
                 H, W);
     hipStream_t s = MVS_STREAM(stream);
-    // all output channels in one block up to 32 (128 accumulator registers); 48/64 channels split over blocks
-    const int nt = (mvs::env_int("MVS_WINO_NT", 0) == 2 && Cout % 32 == 0) ? 2 : 1;
     MVS_REQUIRE((int64_t)B * mvs::ceil_div(H, 8) <= 65535 && mvs::ceil_div(W, 32) <= 65535, "mvs_conv3d_wino_fwd: grid limit");
-    if (nt == 2) return launch_wino<2>(x, wpacked, scale, shift, residual, y, B, Cin, Cout, D, H, W, relu, s);
-    return launch_wino<1>(x, wpacked, scale, shift, residual, y, B, Cin, Cout, D, H, W, relu, s);
+    if (p.NT == 2) return launch_wino<2>(x, wpacked, scale, shift, residual, y, Cin, Cout, D, H, W, relu, p, s);
+    return launch_wino<1>(x, wpacked, scale, shift, residual, y, Cin, Cout, D, H, W, relu, p, s);
 }

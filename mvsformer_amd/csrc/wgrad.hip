@@ -12,7 +12,7 @@
 // fp32 atomics once (a few thousand atomics per wavefront instead of one per voxel).
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv3d_plan.h"
 
 namespace {
 using namespace mvsconv;
@@ -107,8 +107,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ A,
 // ---------------------------------------------------------------------------------------------------------------
 template <int MT, int SHW>
 struct WgTile {
-    static constexpr int SEG = SHW == 1 ? 64 : 32;
-    static constexpr int TH = SHW == 2 ? 4 : (MT == 1 ? 8 : (MT == 2 ? 4 : 2));
+    static constexpr int SEG = mvsconv::wg_seg(SHW), TH = mvsconv::wg_th(MT, SHW);      // conv3d_plan.h
     static constexpr int TBR = TH * SHW + 2, TBC = SEG * SHW + 2;     // Bt tile rows / columns (10 x 66 at most)
     static constexpr int TBCP = 68;                                   // Bt row stride (== 4 mod 32)
     static constexpr int BPS = TBR * TBCP + ((12 - (TBR * TBCP) % 32) + 32) % 32;   // (channel, kd) plane stride == 12 (mod 32)
@@ -272,19 +271,14 @@ __global__ __launch_bounds__(256) void wgrad_tiled_kernel(const float* __restric
 
 template <int MT, int SHW>
 int launch_wgrad_tiled(const float* A, const float* Bt, float* dW, int nbatch, int CA, int CB, int Dp, int Hp, int Wp, int Db, int Hb,
-                        int Wb, int sd, hipStream_t s) {
+                        int Wb, int sd, const mvsconv::WgradTiledPlan& p, hipStream_t s) {
     using T = WgTile<MT, SHW>;
-    const int nchunk = mvs::ceil_div(CB, 4);
-    const long long ntiles = (long long)nbatch * Dp * mvs::ceil_div(Hp, T::TH) * mvs::ceil_div(Wp, T::SEG);
-    long long gy = mvs::ceil_div(512, nchunk);                        // ~2 blocks per CU in total: few adders per dW address (256: slower)
-    if (gy > ntiles) gy = ntiles;
-    if (gy < 1) gy = 1;
     constexpr size_t lds = (size_t)(T::NA + T::NBF) * sizeof(float);
     if (lds > 48 * 1024) {
         const int rc = mvs::ensure_dynamic_lds(reinterpret_cast<const void*>(wgrad_tiled_kernel<MT, SHW>), (int)lds, "mvs_conv3d_wgrad");
         if (rc != MVS_OK) return rc;
     }
-    hipLaunchKernelGGL((wgrad_tiled_kernel<MT, SHW>), dim3(nchunk, (unsigned)gy), dim3(256), lds, s, A, Bt, dW, CA, CB, Dp, Hp, Wp, Db, Hb,
+    hipLaunchKernelGGL((wgrad_tiled_kernel<MT, SHW>), dim3(p.nchunk, (unsigned)p.gy), dim3(256), lds, s, A, Bt, dW, CA, CB, Dp, Hp, Wp, Db, Hb,
                        Wb, sd, nbatch);
     return MVS_OK;
 }
@@ -300,12 +294,12 @@ extern "C" int mvs_conv3d_wgrad(const float* A, const float* Bt, float* dW, int 
                 "mvs_conv3d_wgrad: one batch item exceeds the 2 GiB buffer window");
     if (!mvs::env_int("MVS_WGRAD_V1", 0)) {
         hipStream_t s2 = MVS_STREAM(stream);
-        const int mt2 = mvs::ceil_div(CA, 16);
+        const mvsconv::WgradTiledPlan p = mvsconv::wgrad_tiled_plan(nbatch, CA, CB, Dp, Hp, Wp, shw);
         int rc2 = MVS_OK;
 #define MVS_WGT(M)                                                                                                       \
-    if (shw == 1) rc2 = launch_wgrad_tiled<M, 1>(A, Bt, dW, nbatch, CA, CB, Dp, Hp, Wp, Db, Hb, Wb, sd, s2);              \
-    else rc2 = launch_wgrad_tiled<M, 2>(A, Bt, dW, nbatch, CA, CB, Dp, Hp, Wp, Db, Hb, Wb, sd, s2)
-        switch (mt2) {
+    if (shw == 1) rc2 = launch_wgrad_tiled<M, 1>(A, Bt, dW, nbatch, CA, CB, Dp, Hp, Wp, Db, Hb, Wb, sd, p, s2);           \
+    else rc2 = launch_wgrad_tiled<M, 2>(A, Bt, dW, nbatch, CA, CB, Dp, Hp, Wp, Db, Hb, Wb, sd, p, s2)
+        switch (p.MT) {
             case 1: MVS_WGT(1); break;
             case 2: MVS_WGT(2); break;
             case 3: MVS_WGT(3); break;
@@ -315,16 +309,11 @@ extern "C" int mvs_conv3d_wgrad(const float* A, const float* Bt, float* dW, int 
         if (rc2 != MVS_OK) return rc2;
         return mvs::finish_launch("mvs_conv3d_wgrad");
     }
-    const int nchunk = mvs::ceil_div(CB, 4);
-    const int rows = nbatch * Dp * Hp;
-    int gy = mvs::ceil_div(1024, nchunk);
-    if (gy > mvs::ceil_div(rows, mvsconv::NWAVES)) gy = mvs::ceil_div(rows, mvsconv::NWAVES);
-    if (gy < 1) gy = 1;
-    dim3 grid(nchunk, gy);
+    const mvsconv::WgradV1Plan p = mvsconv::wgrad_v1_plan(nbatch, CA, CB, Dp, Hp);
+    dim3 grid(p.nchunk, p.gy);
     hipStream_t s = MVS_STREAM(stream);
-    const int mt = mvs::ceil_div(CA, 16);
 #define MVS_WG(M) hipLaunchKernelGGL(wgrad_kernel<M>, grid, dim3(256), 0, s, A, Bt, dW, CA, CB, Dp, Hp, Wp, Db, Hb, Wb, sd, shw, nbatch)
-    switch (mt) {
+    switch (p.MT) {
         case 1: MVS_WG(1); break;
         case 2: MVS_WG(2); break;
         case 3: MVS_WG(3); break;

@@ -40,13 +40,15 @@ import itertools
 import torch
 import torch.nn.functional as F
 
+import conv_plan_reader
+
 U32 = 2.0 ** -24
 UBF = 2.0 ** -8
 C_ACC = 2.0
 SUM_CHAIN = 256
 OLD_RTOL = 1e-2                 # the criterion of test_conv_bf16_fn / test_deconv_bf16_fn: max|err| / max|want| < 1e-2
-KSPLIT_ITEMS = 768              # default of MVS_BF16_KSPLIT_ITEMS (csrc/bf16_conv_plan.h)
-WG_PW, WG_RING_B = 16, 56 * 1024
+_CONSTS = conv_plan_reader.fields("bf16_consts")
+KSPLIT_ITEMS, WG_PW = _CONSTS["KSPLIT_ITEMS"], _CONSTS["WG_PW"]      # the largest launch that splits K; patch columns of the weight gradient
 
 
 def bf(x):
@@ -67,51 +69,17 @@ def from_cl(y):
 ConvPlan = collections.namedtuple("ConvPlan", "Do Ho Wo wpar nwchunks items_per_sample items ksplit block_rows samples rows_per_sample")
 
 
-def conv_plan(B, Cin, Di, Hi, Wi, gather, sd, shw, taps=27, groups=1):
-    """``mvsplan::conv_plan`` of csrc/bf16_conv_plan.h, formula by formula."""
-    if gather == 0:
-        Do, Ho, Wo = ((Di - 1) // 2 + 1 if sd == 2 else Di), ((Hi - 1) // 2 + 1 if shw == 2 else Hi), ((Wi - 1) // 2 + 1 if shw == 2 else Wi)
-    else:
-        Do, Ho, Wo = Di * sd, Hi * shw, Wi * shw
-    wpar = gather == 1 and shw == 2
-    nwchunks = (Wo + 127) // 128 if wpar else (Wo + 63) // 64
-    ips = Do * Ho * nwchunks * (2 if wpar else 1)
-    items = ips * B
-    ksplit = taps == 27 and Cin >= 32 and items <= KSPLIT_ITEMS
-    block_rows = items if ksplit else (items + 3) // 4
-    samples = 1 if (B == 1 or groups == 1) else B
-    rps = block_rows if samples == 1 else ips if ksplit else ips // 4 if ips % 4 == 0 else -1
-    return ConvPlan(Do, Ho, Wo, wpar, nwchunks, ips, items, ksplit, block_rows, samples, rps)
+def plan_conv(B, Cin, Di, Hi, Wi, gather, sd, shw, taps=27, groups=1):
+    """``mvsplan::conv_plan`` of csrc/bf16_conv_plan.h, asked of the header itself (tests/conv_plan_tool.cpp)."""
+    return conv_plan_reader.plan(ConvPlan, "bf16_conv", B, Cin, Di, Hi, Wi, gather, sd, shw, taps, groups)
 
 
 WgradPlan = collections.namedtuple("WgradPlan", "PH npr npc npatch dseg nseg TA TB gy blocks")
 
 
-def _wgrad_nseg(columns, Dp, target):
-    return max(1, min(-(-target // columns), max(Dp // 2, 1)))
-
-
-def wgrad_plan(nbatch, CA, CB, Dp, Hp, Wp, shw):
-    """``wgrad_plan`` of csrc/bf16_train.hip for a layer of its own (not grouped)."""
-    nA, nB = (CA + 15) // 16, (CB + 15) // 16
-    TB = nB
-    TA = max(1, min(nA, 4 // nB, 2))
-    gy = -(-nA // TA)
-    b_row = min(CB, TB * 16)
-    PH = 8
-    while PH > 2 and 4 * (PH * shw + 2) * (WG_PW * shw + 2) * b_row * 2 > WG_RING_B:
-        PH >>= 1
-    npr, npc = -(-Hp // PH), -(-Wp // WG_PW)
-    target = 512 // gy
-    nseg = _wgrad_nseg(nbatch * npr * npc, Dp, target)
-    dseg = -(-Dp // nseg)
-    nseg = -(-Dp // dseg)
-    npatch = nbatch * npr * npc * nseg
-    col8 = nbatch * ((Hp + 7) // 8) * npc
-    seg8 = _wgrad_nseg(col8, Dp, target)
-    d8 = -(-Dp // seg8)
-    blocks = max(1, min(target, col8 * -(-Dp // d8)))
-    return WgradPlan(PH, npr, npc, npatch, dseg, nseg, TA, TB, gy, blocks)
+def plan_wgrad(nbatch, CA, CB, Dp, Hp, Wp, shw):
+    """``mvsplan::wgrad_plan`` for a layer of its own (not grouped)."""
+    return conv_plan_reader.plan(WgradPlan, "bf16_wgrad", nbatch, CA, CB, Dp, Hp, Wp, shw, 0)
 
 
 # ------------------------------------------------------------------------------------------------------------------- convolution cases
@@ -198,7 +166,7 @@ KSPLIT_CASES = [_cc("ksplit-c%d" % cin, 2, cin, 16, 0, (1, 1), 3, 129, 5) for ci
 
 
 def out_dims(c):
-    p = conv_plan(c.B, c.cin, c.D, c.H, c.W, c.gather, c.stride[0], c.stride[1], c.taps)
+    p = plan_conv(c.B, c.cin, c.D, c.H, c.W, c.gather, c.stride[0], c.stride[1], c.taps)
     return p.Do, p.Ho, p.Wo
 
 
@@ -341,7 +309,7 @@ REFUSED_CASE = StatCase("st-refused", 2, 2, 8, 8, 0, (1, 1), 1, 3, 20, 27, "refu
 
 
 def stat_plan(c):
-    return conv_plan(c.B, c.cin, c.D, c.H, c.W, c.gather, c.stride[0], c.stride[1], c.taps, c.groups)
+    return plan_conv(c.B, c.cin, c.D, c.H, c.W, c.gather, c.stride[0], c.stride[1], c.taps, c.groups)
 
 
 def nice_bn4(groups, cout, g):
@@ -528,7 +496,7 @@ MANY_ITEMS_CASES = ["wg-items260-blocks256-int", "wg-items260-blocks256-tail"]
 
 def wgrad_item_region(c, item):
     """Work item -> ``(n, depth slice, row slice, column slice)`` of ``A``, decoded as ``wgrad_body`` decodes ``col``."""
-    p = wgrad_plan(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
+    p = plan_wgrad(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
     seg, r = item % p.nseg, item // p.nseg
     pcx, r = r % p.npc, r // p.npc
     pry, n = r % p.npr, r // p.npr
@@ -556,7 +524,7 @@ def wgrad_inputs(name):
     A = bf(torch.randn(c.nb, c.Dp, c.Hp, c.Wp, c.CA, generator=g) * sd + c.offset)
     Bt = bf(torch.randn(c.nb, Db, Hb, Wb, c.CB, generator=g) * sd + c.offset)
     if c.data == "tail":
-        p = wgrad_plan(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
+        p = plan_wgrad(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
         keep = torch.zeros(c.nb, c.Dp, c.Hp, c.Wp, 1)
         for item in range(p.blocks, p.npatch):
             n, d, h, w = wgrad_item_region(c, item)
@@ -651,7 +619,7 @@ def mutate_drop_item(name, item):
 
 def mutate_drop_last_segment(name):
     c = WGRAD_CASE[name]
-    p = wgrad_plan(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
+    p = plan_wgrad(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
     assert p.nseg > 1
     A, Bt = wgrad_inputs(name)
     A = A.clone()

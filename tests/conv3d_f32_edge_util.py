@@ -1,4 +1,4 @@
-"""Plan mirrors, case tables, float64 references, per-element bounds and mutation helpers for the fp32 training convolutions:
+"""Plans (read from the launchers' own planner), case tables, float64 references, per-element bounds and mutation helpers for the fp32 training convolutions:
 ``conv3d_kernel`` (csrc/conv3d_fwd.hip), ``deconv3d_kernel`` (csrc/conv3d.hip), ``wino_conv3d_kernel`` (csrc/conv3d_wino.hip) and
 ``wgrad_tiled_kernel`` / ``wgrad_kernel`` (csrc/wgrad.hip).  No GPU code: used by ``tests/test_hip_conv3d_f32_edges.py`` and
 ``tests/conv3d_f32_edge_child.py`` (MI355X) and checked by ``tests/test_conv3d_f32_edge_refs.py`` (CPU).
@@ -46,6 +46,7 @@ import itertools
 import torch
 import torch.nn.functional as F
 
+import conv_plan_reader
 from bf16_conv_edge_util import C_ACC, U32, epilogue, inside, share          # noqa: F401  (re-exported for the tests)
 
 GUARD = 777.25
@@ -60,148 +61,70 @@ def _gen(name):
     return torch.Generator().manual_seed(sum((i + 1) * ord(ch) for i, ch in enumerate(name)) % (2 ** 31))
 
 
-# ===================================================================================================================== plan mirrors
-# ---- csrc/conv_common.h:16-21
-def np_of(nt):
-    return 16 if nt == 1 else (48 if nt == 2 else 80)
-
-
-def pad_cs(raw, shw):
-    return raw + ((16 - raw % 32) + 32) % 32 if shw == 1 else raw + (1 if raw % 2 == 0 else 0)
-
-
-def nt_of(cout):
-    nt = (cout + 15) // 16
-    return 4 if nt == 3 else nt
-
-
-# ---- csrc/conv3d_fwd.hip:29-38
-def tile_cs(sd, shw, td, th, mt):
-    return pad_cs(((td - 1) * sd + 3) * ((th - 1) * shw + 3) * ((16 * mt - 1) * shw + 3), shw)
-
-
-def pick_cc(NP, sd, shw, td, th, mt):
-    return 8 if (8 * tile_cs(sd, shw, td, th, mt) + 2 * 27 * 4 * NP) * 4 <= 96 * 1024 else 4
-
-
-def lds_bytes(NP, sd, shw, td, th, mt):
-    cc = pick_cc(NP, sd, shw, td, th, mt)
-    return (cc * tile_cs(sd, shw, td, th, mt) + (cc // 4) * 27 * 4 * NP) * 4
-
-
+# ===================================================================================================================== plans
+# What the launchers do, asked of csrc/conv3d_plan.h itself through tests/conv_plan_tool.cpp (conv_plan_reader).
 ConvPlan = collections.namedtuple("ConvPlan", "form NT TD TH MT TW CC NP nsplit Do Ho Wo grid nblocks chunks")
 FORMS = ("22", "42", "22s64", "22s")          # 2x2x64 all channels | 4x2x64 | 2x2x64 channels split | 2x2x32 channels split
-_FORM_TILE = {"22": (2, 2, 4), "42": (4, 2, 4), "22s64": (2, 2, 4), "22s": (2, 2, 2)}
 
 
-def conv_plan(B, Cin, Cout, Di, Hi, Wi, sd, shw, force=None):
-    """``mvs_conv3d_fwd`` + ``dispatch_tile`` (csrc/conv3d_fwd.hip:222-267, 278-288) -> the form launched and its grid; ``force`` =
-    MVS_CONV_TILE.  The model's arithmetic is evaluated in the source's order, in double."""
-    Do, Ho, Wo = (Di - 1) // sd + 1, (Hi - 1) // shw + 1, (Wi - 1) // shw + 1
-    NTF = nt_of(Cout)
-    NP = np_of(NTF)
-
-    def blocks(td, th, tw):
-        return ceil_div(Wo, tw) * ceil_div(Ho, th) * ceil_div(Do, td) * B
-
-    form = None
-    if force:                                                  # :229-233
-        if sd == 1 and force == "42" and Do >= 3:
-            form = "42"
-        elif force == "22":
-            form = "22"
-        elif force == "22s":
-            form = "22s"
-    if form is None:
-        def model(td, th, mt, ntb):                            # :236-242
-            lds, cc = lds_bytes(NP, sd, shw, td, th, mt), pick_cc(NP, sd, shw, td, th, mt)
-            chunks = float(ceil_div(Cin, cc))
-            mfma = 27.0 * (cc // 4) * (td * th // 4) * mt * ntb * 32.0
-            ovh = 3500.0 if lds > 80 * 1024 else 1200.0
-            nb = blocks(td, th, 16 * mt) * ceil_div(NTF, ntb)
-            return float((nb + 255) // 256) * chunks * (mfma + ovh)
-        best, form = model(2, 2, 4, NTF), "22"                 # :245-248
-        if NTF == 1 and sd == 1 and Do >= 3:                   # :249-254
-            c = model(4, 2, 4, NTF) * (0.6 if shw == 2 else 0.95)
-            if c < best:
-                best, form = c, "42"
-        if NTF > 1:                                            # :255-258
-            c = model(2, 2, 4, 1) * 1.1
-            if c < best:
-                best, form = c, "22s64"
-        c = model(2, 2, 2, 1) * 1.15                           # :259-262
-        if c < best or Wo <= 32:
-            best, form = c, "22s"
-    td, th, mt = _FORM_TILE[form]
-    NT = NTF if form in ("22", "42") else 1                    # :263-266
-    cc = pick_cc(NP, sd, shw, td, th, mt)
-    nsplit = ceil_div(nt_of(Cout), NT)                         # launch(), :209-210
-    grid = (ceil_div(Wo, 16 * mt) * nsplit, ceil_div(Ho, th), B * ceil_div(Do, td))
-    return ConvPlan(form, NT, td, th, mt, 16 * mt, cc, NP, nsplit, Do, Ho, Wo, grid, grid[0] * grid[1] * grid[2], ceil_div(Cin, cc))
+def form_tw(form):
+    """Output voxels along W of a block of ``form``."""
+    return conv_plan_reader.fields("conv_tile", form)["TW"]
 
 
-# ---- csrc/conv3d.hip:59-90, 365-374, 408-416
+def plan_conv(B, Cin, Cout, Di, Hi, Wi, sd, shw, force=None):
+    """``mvs_conv3d_fwd``: the form launched and its grid; ``force`` = MVS_CONV_TILE."""
+    return conv_plan_reader.plan(ConvPlan, "conv", B, Cin, Cout, Di, Hi, Wi, sd, shw, force or "-")
+
+
 DeconvPlan = collections.namedtuple("DeconvPlan", "route NT TWI THI TDI Do Ho Wo grid chunks")
 
 
 def deconv_plan(B, Cin, Cout, Di, Hi, Wi, sd):
-    """``mvs_deconv3d_fwd`` / ``launch_deconv``: a block covers 32 input columns (+1 halo), 2 input rows and, SD == 1, 2 output depths
-    (= input depths), SD == 2, 1 input depth; 8 input channels per chunk.  ``route`` "s1": stride-1 depth with 8 / 16 output channels
-    goes to the split-form kernel of csrc/deconv3d_s1.hip, which is not this module's subject."""
-    route = "s1" if (sd == 1 and Cout in (8, 16)) else "deconv3d_kernel"
-    tdi = 2 if sd == 1 else 1
-    grid = (ceil_div(Wi, 32), ceil_div(Hi, 2), B * ceil_div(Di, tdi))
-    return DeconvPlan(route, nt_of(Cout), 32, 2, tdi, Di * sd, Hi * 2, Wi * 2, grid, ceil_div(Cin, 8))
+    """``mvs_deconv3d_fwd``: a block covers 32 input columns (+1 halo), 2 input rows and, SD == 1, 2 output depths (= input depths), SD == 2,
+    1 input depth; 8 input channels per chunk.  ``route`` "s1": stride-1 depth with 8 / 16 output channels goes to the split-form kernel of
+    csrc/deconv3d_s1.hip, which is not this module's subject."""
+    return conv_plan_reader.plan(DeconvPlan, "deconv", B, Cin, Cout, Di, Hi, Wi, sd)
 
 
-# ---- csrc/conv3d_wino.hip:257-263, 268-271, 294-298
 WinoPlan = collections.namedtuple("WinoPlan", "NT ngroups grid chunks prefetch")
 
 
 def wino_supported(Cin, Cout, D, H, W):
-    return Cin >= 4 and Cin % 4 == 0 and Cout >= 16 and Cout % 16 == 0 and Cout <= 64 and D >= 1 and H >= 1 and W >= 4 and W % 4 == 0
+    return conv_plan_reader.fields("wino", 1, Cin, Cout, D, H, W, 0)["supported"]
 
 
 def wino_plan(B, Cin, Cout, D, H, W, env_nt=None):
-    """A block = 4 tile rows (8 output rows) x 32 output columns of one depth plane x 16 NT channels; ``env_nt`` = MVS_WINO_NT."""
-    assert wino_supported(Cin, Cout, D, H, W)
-    NT = 2 if (env_nt == "2" and Cout % 32 == 0) else 1
-    ngroups = Cout // (16 * NT)
-    return WinoPlan(NT, ngroups, (D * ngroups, ceil_div(W, 32), ceil_div(H, 8) * B), Cin // 4, Cin // 4 > 1)
+    """A block = 4 tile rows (8 output rows) x 32 output columns of one depth plane x 16 NT channels; ``env_nt`` = MVS_WINO_NT.
+    ``prefetch``: the kernel fetches the next chunk of 4 input channels under the current one's MFMAs when there is more than one."""
+    got = conv_plan_reader.fields("wino", B, Cin, Cout, D, H, W, int(env_nt or 0))
+    assert got["supported"]
+    return conv_plan_reader.plan(WinoPlan, "wino", B, Cin, Cout, D, H, W, int(env_nt or 0), prefetch=got["chunks"] > 1)
 
 
-# ---- csrc/wgrad.hip:108-120, 273-290, 303-313
 WgPlan = collections.namedtuple("WgPlan", "MT SHW TH SEG nchunk hblocks wblocks ntiles gy tiles_min tiles_max vec_a")
 
 
-def wg_tile(mt, shw):
-    """``WgTile<MT,SHW>``: (TH, SEG)."""
-    return (4 if shw == 2 else (8 if mt == 1 else (4 if mt == 2 else 2))), (64 if shw == 1 else 32)
+def plan_wgrad(nbatch, CA, CB, Dp, Hp, Wp, shw):
+    """``wgrad_tiled_kernel``.  Block y walks tiles y, y + gy, ..: ``tiles_min`` / ``tiles_max`` per block; ``vec_a``: the kernel loads A
+    in 128-bit pieces when rows are 16-byte aligned."""
+    got = conv_plan_reader.fields("wgrad", nbatch, CA, CB, Dp, Hp, Wp, shw)
+    return conv_plan_reader.plan(WgPlan, "wgrad", nbatch, CA, CB, Dp, Hp, Wp, shw, tiles_min=got["ntiles"] // got["gy"],
+                                 tiles_max=ceil_div(got["ntiles"], got["gy"]), vec_a=Wp % 4 == 0)
 
 
-def wgrad_plan(nbatch, CA, CB, Dp, Hp, Wp, shw):
-    MT = min(ceil_div(CA, 16), 4)
-    TH, SEG = wg_tile(MT, shw)
-    nchunk = ceil_div(CB, 4)
-    hb, wb = ceil_div(Hp, TH), ceil_div(Wp, SEG)
-    ntiles = nbatch * Dp * hb * wb
-    gy = max(1, min(ceil_div(512, nchunk), ntiles))
-    return WgPlan(MT, shw, TH, SEG, nchunk, hb, wb, ntiles, gy, ntiles // gy, ceil_div(ntiles, gy), Wp % 4 == 0)
-
-
-# ---- csrc/wgrad.hip:50-52, 318-323
 WgV1Plan = collections.namedtuple("WgV1Plan", "MT nchunk rows gy rows_per_wave")
 
 
 def wgrad_v1_plan(nbatch, CA, CB, Dp, Hp):
-    nchunk, rows = ceil_div(CB, 4), nbatch * Dp * Hp
-    gy = max(1, min(ceil_div(1024, nchunk), ceil_div(rows, 4)))
-    return WgV1Plan(min(ceil_div(CA, 16), 4), nchunk, rows, gy, ceil_div(rows, 4 * gy))
+    """``wgrad_kernel``: a block's four wavefronts walk rows 4 y + wave, + 4 gy, .."""
+    got = conv_plan_reader.fields("wgrad_v1", nbatch, CA, CB, Dp, Hp)
+    return conv_plan_reader.plan(WgV1Plan, "wgrad_v1", nbatch, CA, CB, Dp, Hp, rows_per_wave=ceil_div(got["rows"], 4 * got["gy"]))
 
 
 # ===================================================================================================================== conv cases
 # kind: conv | dgrad (ops.conv3d with the "dgrad" pack of a [cin, cout] layer weight) | deconv | wino | wino-dgrad
-# force: MVS_CONV_TILE (conv, dgrad) or MVS_WINO_NT (wino); None = unset.  want: plan fields the mirror must show for this case.
+# force: MVS_CONV_TILE (conv, dgrad) or MVS_WINO_NT (wino); None = unset.  want: plan fields the planner must show for this case.
 Case = collections.namedtuple("Case", "name kind force B cin cout stride D H W scale relu residual data want claim")
 
 
@@ -228,7 +151,7 @@ def _tile_edge_cases(form, force, tag, strides, dos):
     six cases Ho = 1 meets Cin 4, 8, 12 and Ho = 3 meets Cin 16, 4, 8 (the next stride the other way round); stride-2 extents alternate
     odd / even per Wo.  EVERY stride-(1,1) case has a "dgrad" twin on the same shape with cin != cout: Ho in {1, 3}, Cin in {4, 8, 12, 16}."""
     out, k = [], 0
-    TW = _FORM_TILE[form][2] * 16
+    TW = form_tw(form)
     for stride in strides:
         for Wo in (TW - 1, TW, TW + 1):
             for rep in range(2):
@@ -266,8 +189,8 @@ def _forced_cases():
 
 def _default_cases():
     """In-process cases (MVS_CONV_TILE unset).  The edge table of the 32-voxel form once more, unforced (Wo <= 32 forces that form; at
-    Wo = 33 the model decides and the mirror says what ran).  Then the shapes on which the model picks a 64-voxel form by itself although the
-    32-voxel form would need more than one round of 256 blocks (``BIG_DEFAULT``; the refs test asserts both through the mirror), the
+    Wo = 33 the model decides and the planner says what ran).  Then the shapes on which the model picks a 64-voxel form by itself although the
+    32-voxel form would need more than one round of 256 blocks (``BIG_DEFAULT``; the refs test asserts both through the planner), the
     epilogue in all eight combinations on three shapes, and the integer cases."""
     out = _tile_edge_cases("22s", None, "d22s", STRIDES, (1, 2, 3, 5))
     big = [
@@ -379,7 +302,7 @@ def forced_cases(force):
 
 def case_plan(c):
     if c.kind in ("conv", "dgrad"):
-        return conv_plan(c.B, c.cin, c.cout, c.D, c.H, c.W, c.stride[0], c.stride[1], c.force)
+        return plan_conv(c.B, c.cin, c.cout, c.D, c.H, c.W, c.stride[0], c.stride[1], c.force)
     if c.kind == "deconv":
         return deconv_plan(c.B, c.cin, c.cout, c.D, c.H, c.W, c.stride[0])
     return wino_plan(c.B, c.cin, c.cout, c.D, c.H, c.W, c.force)
@@ -520,8 +443,8 @@ def _wg_edge_cases():
     out, k = [], 0
     for shw in (1, 2):
         for CA in (8, 16, 24, 40, 48, 64):
-            MT = min(ceil_div(CA, 16), 4)
-            TH, SEG = wg_tile(MT, shw)
+            tile = plan_wgrad(1, CA, 1, 1, 1, 1, shw)
+            MT, TH, SEG = tile.MT, tile.TH, tile.SEG
             for dw in (-1, 0, 1, 4):
                 Wp, Hp = SEG + dw, (1, TH, TH + 1)[k % 3]
                 CB, sd, nb = (1, 4, 5, 8, 64)[k % 5], 1 + (k // 2) % 2, (1, 3)[(k // 3) % 2]
@@ -567,7 +490,7 @@ WG_V1_CASES = WG_CASES                        # the first kernel runs every edge
 
 
 def wg_plan(c):
-    return wgrad_plan(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
+    return plan_wgrad(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
 
 
 def bt_dims(c):
@@ -591,7 +514,7 @@ def wg_inputs(name):
 def wgrad_sum(A, Bt, stride, dtype=torch.float64):
     """``dW[a][b][kd][kh][kw] = sum_{n,p} A[n][a][p] Bt[n][b][p s - 1 + k]`` (zero outside ``Bt``) as plain sums in ``dtype``.  With
     ``A = dY, Bt = X`` this is ``nn.Conv3d.weight.grad`` ``[Cout,Cin,3,3,3]``, with ``A = X, Bt = dY`` ``nn.ConvTranspose3d.weight.grad``
-    ``[Cin,Cout,3,3,3]`` (csrc/wgrad.hip:1-5)."""
+    ``[Cin,Cout,3,3,3]`` (the two orientations of csrc/wgrad.hip)."""
     A, Bt = A.to(dtype), Bt.to(dtype)
     N, CA, Dp, Hp, Wp = A.shape
     _, CB, Db, Hb, Wb = Bt.shape
@@ -619,7 +542,7 @@ def wg_expect(name):
 
 
 def wg_tile_region(c, tile):
-    """Tile index -> ``(n, d, row slice, column slice)`` of ``A``, decoded as ``fetch`` decodes ``tl`` (csrc/wgrad.hip:161-164)."""
+    """Tile index -> ``(n, d, row slice, column slice)`` of ``A``, decoded as ``fetch`` of ``wgrad_tiled_kernel`` decodes ``tl``."""
     p = wg_plan(c)
     w0 = (tile % p.wblocks) * p.SEG
     h0 = ((tile // p.wblocks) % p.hblocks) * p.TH

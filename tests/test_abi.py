@@ -464,3 +464,23 @@ def test_bf16_conv_plan_matches_the_replaced_formulas_under_sanitizers(tmp_path)
                            os.path.join(REPO, "tests", "bf16_conv_plan_check.cpp"), "-o", exe])
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip() == "ok" and not run.stderr.strip(), (run.returncode, run.stdout, run.stderr)
+
+
+def test_conv_plans_match_the_replaced_launch_arithmetic_under_sanitizers(tmp_path):
+    """tests/conv_plan_tool.cpp in check mode: a stand-alone host program (its own main, host code only, sanitizers on the host side only,
+    as env_reader_check.cpp) that sweeps every plan of csrc/conv3d_plan.h and the weight-gradient plan of csrc/bf16_conv_plan.h over the tile
+    edges - widths and heights around 16 / 32 / 64 / 128, depths 1 .. 5, the three strides, channels across the NT boundaries, every
+    MVS_CONV_TILE value - against the launch arithmetic they replaced, kept there verbatim: equal field by field.  The same program in print
+    mode is where the edge tests read their plans from (tests/conv_plan_reader.py), so it answers a request here as well."""
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "conv_plan_tool")
+    subprocess.check_call([hipcc, "-std=c++17", "-x", "hip", "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           os.path.join(REPO, "tests", "conv_plan_tool.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok" and not run.stderr.strip(), (run.returncode, run.stdout, run.stderr)
+    run = subprocess.run([exe, "print"], input="conv 1 8 24 3 43 65 1 1 -\nwgrad_v1 2 16 256 6 13\nnonsense\n", capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr.strip(), (run.returncode, run.stderr)
+    lines = run.stdout.splitlines()
+    assert lines[0].split()[:6] == ["form=22s64", "NT=1", "TD=2", "TH=2", "MT=4", "TW=64"] and "grid=4,22,2" in lines[0].split()
+    assert lines[1] == "MT=1 nchunk=64 rows=156 gy=16" and lines[2] == "error=request"

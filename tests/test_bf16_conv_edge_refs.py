@@ -1,6 +1,6 @@
 """CPU-side checks of tests/test_hip_bf16_conv_edges.py (no GPU): the float64 references of ``bf16_conv_edge_util`` agree with torch
 autograd through ``conv3d`` / ``conv_transpose3d``, the case tables reach the branches of ``mvsplan::conv_plan`` and ``wgrad_plan`` they claim
-(recomputed here with the same formulas), correct outputs in other precisions stay inside every bound, and eight subtly wrong kernels - built
+(read from the launchers' own planner), correct outputs in other precisions stay inside every bound, and eight subtly wrong kernels - built
 by perturbing the reference's own result, never a kernel - land outside them (the seventh and eighth: a dropped voxel, and a block that
 skips its second work item, on the case with more work items than blocks)."""
 import pytest
@@ -11,11 +11,11 @@ import bf16_conv_edge_util as U
 
 
 def _plan(c):
-    return U.conv_plan(c.B, c.cin, c.D, c.H, c.W, c.gather, c.stride[0], c.stride[1], c.taps)
+    return U.plan_conv(c.B, c.cin, c.D, c.H, c.W, c.gather, c.stride[0], c.stride[1], c.taps)
 
 
 def _wplan(c):
-    return U.wgrad_plan(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
+    return U.plan_wgrad(c.nb, c.CA, c.CB, c.Dp, c.Hp, c.Wp, c.stride[1])
 
 
 # ------------------------------------------------------------------------------------------------------------------- the references
@@ -74,12 +74,12 @@ def test_wgrad_sum_2d_and_short_operand():
 
 # ------------------------------------------------------------------------------------------------------------------- what the tables reach
 def test_conv_plan_formulas_on_known_shapes():
-    p = U.conv_plan(2, 64, 3, 129, 5, 0, 1, 1)
+    p = U.plan_conv(2, 64, 3, 129, 5, 0, 1, 1)
     assert (p.Do, p.Ho, p.Wo, p.nwchunks, p.items_per_sample, p.items, p.ksplit, p.block_rows) == (3, 129, 5, 1, 387, 774, False, 194)
-    p = U.conv_plan(2, 16, 2, 3, 65, 1, 2, 2, 27, 2)
+    p = U.plan_conv(2, 16, 2, 3, 65, 1, 2, 2, 27, 2)
     assert (p.Do, p.Ho, p.Wo, p.wpar, p.nwchunks, p.items_per_sample, p.rows_per_sample, p.samples) == (4, 6, 130, True, 2, 96, 24, 2)
-    assert U.conv_plan(2, 8, 1, 3, 20, 0, 1, 1, 27, 2).rows_per_sample == -1 and U.conv_plan(2, 8, 1, 3, 20, 0, 1, 1, 27, 1).rows_per_sample == 2
-    assert U.conv_plan(1, 32, 4, 4, 64, 0, 1, 1, 9).ksplit is False
+    assert U.plan_conv(2, 8, 1, 3, 20, 0, 1, 1, 27, 2).rows_per_sample == -1 and U.plan_conv(2, 8, 1, 3, 20, 0, 1, 1, 27, 1).rows_per_sample == 2
+    assert U.plan_conv(1, 32, 4, 4, 64, 0, 1, 1, 9).ksplit is False
 
 
 def test_row_chunk_cases_reach_their_edges():

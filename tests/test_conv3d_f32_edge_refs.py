@@ -1,5 +1,5 @@
 """CPU checks of ``tests/conv3d_f32_edge_util.py``: the float64 references against naive loops, every case against the plan property it
-claims (through the mirrors of the launchers), the coverage of tile forms / MT / SHW / CC / NT, and the bounds: the fp32-rounded reference
+claims (through the launchers' own planner, ``conv_plan_reader``), the coverage of tile forms / MT / SHW / CC / NT, and the bounds: the fp32-rounded reference
 lies inside every bound with no element excluded, and each mutation - what a subtly wrong kernel would produce - violates it."""
 import itertools
 
@@ -57,7 +57,7 @@ def test_references_match_naive_loops(stride):
     xs = x[:, :, :2, :2, :3]
     yt = F.conv_transpose3d(xs, wt, None, stride=s3, padding=1, output_padding=tuple(v - 1 for v in s3))
     assert (yt - _naive_deconv(xs, wt, s3)).abs().max() < 1e-12
-    # both orientations of csrc/wgrad.hip:1-5 against autograd and against the loop
+    # both orientations of csrc/wgrad.hip against autograd and against the loop
     xg, wg = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
     dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
     F.conv3d(xg, wg, None, stride=s3, padding=1).backward(dy)
@@ -120,7 +120,7 @@ def test_big_default_cases_leave_the_first_round():
     """On each of them the 32-voxel form would need more than 256 blocks, and the model picks a 64-voxel form by itself."""
     for name in U.BIG_DEFAULT:
         c = U.CASE[name]
-        assert U.conv_plan(c.B, c.cin, c.cout, c.D, c.H, c.W, c.stride[0], c.stride[1], "22s").nblocks > 256, name
+        assert U.plan_conv(c.B, c.cin, c.cout, c.D, c.H, c.W, c.stride[0], c.stride[1], "22s").nblocks > 256, name
         assert U.case_plan(c).TW == 64
         assert c.cin <= 16
     assert {U.CASE[n].stride for n in U.BIG_DEFAULT} == set(U.STRIDES)

@@ -1,11 +1,11 @@
 """The fp32 training convolutions - ``conv3d_kernel`` in its four tile forms (csrc/conv3d_fwd.hip), ``deconv3d_kernel`` (csrc/conv3d.hip),
 ``wino_conv3d_kernel`` with one and two N tiles (csrc/conv3d_wino.hip), ``wgrad_tiled_kernel`` with single-tile and multi-tile blocks and the
-first ``wgrad_kernel`` (csrc/wgrad.hip) - through ``mvsformer_amd.ops`` against float64, element by element, at tile edges.  Cases, plan
-mirrors, references and the derivation of the bounds: ``tests/conv3d_f32_edge_util.py``; that the cases reach what they claim and that the
+first ``wgrad_kernel`` (csrc/wgrad.hip) - through ``mvsformer_amd.ops`` against float64, element by element, at tile edges.  Cases, plans
+(read from the launchers' planner), references and the derivation of the bounds: ``tests/conv3d_f32_edge_util.py``; that the cases reach what they claim and that the
 bounds reject the mutations: ``tests/test_conv3d_f32_edge_refs.py`` (CPU); the runner and the guard planes: ``tests/conv3d_f32_edge_child.py``.
 
 MVS_CONV_TILE is read once per process: the forms it forces run in one fresh child process each; everything else runs here, where the
-dispatcher's own choice (mirrored by ``conv_plan``) reaches all four forms.  MVS_WINO_NT and MVS_WGRAD_V1 are read per call.
+dispatcher's own choice (read back by ``plan_conv``) reaches all four forms.  MVS_WINO_NT and MVS_WGRAD_V1 are read per call.
 
 Every check prints ``F32EDGE family case max|err| ratio`` (ratio = the largest |err| / bound over ALL elements).  Largest ratio per family
 when recorded on an MI355X:
@@ -34,7 +34,7 @@ CHILD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv3d_f32_edg
 @pytest.fixture(scope="module")
 def dev():
     assert torch.cuda.is_available()
-    assert os.environ.get("MVS_CONV_TILE") is None             # conv_plan(force=None) describes what runs in this process
+    assert os.environ.get("MVS_CONV_TILE") is None             # plan_conv(force=None) describes what runs in this process
     return torch.device("cuda:0")
 
 
