@@ -114,7 +114,13 @@ __device__ __forceinline__ GeoView geo_view(const ViewXf& t, const float* __rest
     const V3 cs = pix_to_cam(t.Kri, t.r2s, px, py, dref);
     const V3 q = cam_to_img(t.Ks, cs);
     float wx = q.x / (float)W * 2.0f - 1.0f, wy = q.y / (float)H * 2.0f - 1.0f;
-    wx = fminf(fmaxf(wx, -1.1f), 1.1f);              // clamp(-1.1, 1.1); NaN propagates like torch.clamp
+    // clamp(-1.1, 1.1).  Non-finite depths: fmaxf / fminf return their other operand for a NaN, so a NaN coordinate (a NaN or infinite
+    // reference depth) becomes -1.1 where torch.clamp keeps the NaN.  Either way the pixel is out of range and its mask is 0, which is the
+    // contract: in_range = 0 and m = 0 for a non-finite reference depth, m = 0 for every pixel whose blend reads a non-finite source depth
+    // (NaN compares false), pixels that read no such value are untouched.  The reprojected triple of an affected pixel is unspecified: here
+    // it is the blend at the -1.1 corner (for W or H <= 20 that still reaches tap row / column 0), in the reference whatever grid_sample
+    // makes of a NaN coordinate.  The tap index is bounds-checked below, so nothing is read outside the map in any case.
+    wx = fminf(fmaxf(wx, -1.1f), 1.1f);
     wy = fminf(fmaxf(wy, -1.1f), 1.1f);
     GeoView o;
     o.inr = (-1.0f <= wx && wx <= 1.0f && -1.0f <= wy && wy <= 1.0f) ? 1.0f : 0.0f;
